@@ -21,7 +21,13 @@ committed successor is one of them and is not re-executed) divided by the wall t
 ranks / max over ranks.  Inputs are resident in HBM when the timed region starts (c2; c4 uploads 80 KB of weights
 and a 1 MB schedule per generation, as the GA driver does).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|rollout] [--deck D] [--games G] [--lanes U] [--rounds R] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|rollout] [--deck D] [--games G] [--lanes U] [--rounds R]
+                  [--dump-outputs DIR] [--full [--no-cpu]]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes time of its own
+beyond that: the CPU baseline of c2 (the CPU replay oracle on the host cores; --no-cpu leaves it out again).
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB in
+all: larger outputs are cut to a fixed, seeded sample of their rows, whose indices are sample_rows.npy); the inputs
+depend on the arguments alone, so two builds can be compared output for output.
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself (one process per
 GPU through torch.distributed.run, before anything here touches a GPU) and relays rank 0's line; under
 torch.distributed.run it is one of the ranks.
@@ -48,6 +54,25 @@ REFERENCE_PYTHON = {"value": 315.0, "range": [280.0, 350.0], "unit": "env-steps/
                     "where": "build container (BASELINE.md §2), not this box",
                     "sample": "2 N12M heuristic self-play games to 200 decisions, look-ahead steps included"}
 METRIC = "env-steps/sec (whole node) at 65536 concurrent games; bit-exact vs CPU replay"
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (exact for the integer outputs, which are at most
+    32 bits wide), <name>_rank<r>.npy for each rank of a multi-GPU run.  Arrays of one length (one row per game or
+    individual) that exceed DUMP_BYTES in all are cut to the same fixed, seeded sample of rows."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        rows = max(len(a) for a in arrays.values())
+        per_row = 8 + sum(a.nbytes // rows for a in arrays.values() if len(a) == rows)   # + 8: the row's index
+        fixed = sum(a.nbytes for a in arrays.values() if len(a) != rows) + 256 * (len(arrays) + 1)   # + the .npy headers
+        keep = np.sort(np.random.RandomState(0).choice(rows, (DUMP_BYTES - fixed) // per_row, replace=False))
+        arrays = {k: a[keep] if len(a) == rows else a for k, a in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
 
 
 def recorded_traffic():
@@ -93,7 +118,7 @@ def cpu_baseline(sample_games, max_turns, threads):
 
 class FakeEngine:
     """TEST HOOK (MONSOON_BENCH_FAKE=1, tests/test_distributed_cpu.py only): stands in for the HIP engine so that the
-    launcher, the rank plumbing and the all-reduce of this file run on CPU ranks with the gloo backend.  It plays no
+    launcher, the rank plumbing, the all-reduce and --dump-outputs of this file run on CPU (ranks: gloo backend).  It plays no
     game and its numbers mean nothing; bench.py never selects it by itself."""
 
     def __init__(self, n):
@@ -125,6 +150,18 @@ class FakeEngine:
     def kernel_time(self):
         return 1.0 * self.rounds, self.rounds
 
+    def state_hash(self):
+        return np.arange(len(self.seeds), dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(self.rounds)
+
+    def status(self):
+        return np.zeros((len(self.seeds), 4), dtype=np.int32)
+
+    def features(self):
+        return np.zeros((len(self.seeds), 10))
+
+    def game_faults(self):
+        return np.zeros(len(self.seeds), dtype=np.uint8)
+
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -137,7 +174,10 @@ def parse_args(argv=None):
     ap.add_argument("--lanes", type=int, default=0, help="candidate lanes per game (0 = build default)")
     ap.add_argument("--rounds", type=int, default=8, help="c2: decisions every game advances per step (one launch)")
     ap.add_argument("--stack", type=int, default=0, help="per-lane scratch stack bytes (0 = library default)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes time of its own: the CPU baseline (c2)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB)")
     ap.add_argument("--cpu-sample", type=int, default=32768)
     ap.add_argument("--cpu-threads", type=int, default=16)
     args = ap.parse_args(argv)
@@ -309,7 +349,14 @@ def bench_c2(args, rank, world, local_rank, fake, barrier, all_sum, all_max):
     }
     if ceilings:   # offline, from the same rocprofv3 passes as `traffic`: the ceilings that bind this integer, LDS-resident kernel
         line["roofline"].update(ceilings)
-    if not args.no_cpu and world == 1 and rank == 0 and not fake:
+    if args.dump_outputs:
+        # what a caller of the path reads back after the last step: every game's state (its canonical hash as two 32-bit
+        # halves), {to_play, have_winner, base_first, base_second}, the 10 features and the fault code
+        h = eng.state_hash()
+        dump_outputs(args.dump_outputs, {"state_hash": np.stack([h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)], axis=1),
+                                         "status": eng.status(), "features": eng.features(), "game_faults": eng.game_faults()},
+                     rank, world)
+    if args.full and not args.no_cpu and world == 1 and rank == 0 and not fake:
         line["cpu_baseline"] = cpu_baseline(args.cpu_sample, 200, args.cpu_threads)
     return line
 
@@ -349,7 +396,7 @@ def bench_rollout(args, rank, world, local_rank, barrier, all_sum, all_max):
     t0 = time.perf_counter()
     decisions = 0
     for k in range(args.steps):
-        _, _, steps = one(args.warmup + k)
+        counts, results, steps = one(args.warmup + k)
         decisions += int(steps.sum())
     barrier()
     dt = time.perf_counter() - t0
@@ -357,6 +404,8 @@ def bench_rollout(args, rank, world, local_rank, barrier, all_sum, all_max):
     kms, launches = eng.kernel_time()
     tot_look, tot_dec = all_sum([st["lookahead_steps"], decisions])
     max_dt = all_max(dt)
+    if args.dump_outputs:   # monsoon_rollout's outputs for the last step's games: {wins, draws, games} per weight vector, result and length per game
+        dump_outputs(args.dump_outputs, {"counts": counts, "results": results, "steps": steps}, rank, world)
     return {
         "metric": METRIC, "value": tot_look / max_dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1000.0 * max_dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -411,6 +460,8 @@ def bench_ga(args, rank, world, local_rank, barrier, all_sum, all_max):
     max_dt = all_max(dt)
     alg = BYTES_LOOKAHEAD * ev.total_env_steps + BYTES_COMMIT * ev.total_decisions
     achieved = alg / max(kms / 1000.0, 1e-9) / 1e9
+    if args.dump_outputs:   # evaluate_population's result for the last generation: every individual's fitness
+        dump_outputs(args.dump_outputs, {"fitness": fit}, rank, world)
     return {
         "metric": METRIC,
         "value": tot_steps / max_dt,

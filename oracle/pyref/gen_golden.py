@@ -17,6 +17,8 @@ by running it here and committing inputs + expected outputs (data only, no refer
                                chosen action, best score, score hash, state hash per decision
   initial_states.npz       G2  canonical records right after construction
   population_seed42.npz        GA driver: initial population + first offspring for config.seed=42
+  trace_live_*.npz             the difffuzz.py runs of tests/test_reference_live.py (features at every step)
+  checkpoint_reference.pkl     the reference's own Population.save_population checkpoint (mu = lambda = 12, seed 9)
 
 Usage: PYTHONHASHSEED=0 python oracle/pyref/gen_golden.py [--only NAME] [--jobs N]
 """
@@ -215,6 +217,29 @@ def gen_pool(n_games, steps, jobs, ext=False):
     with ProcessPoolExecutor(jobs) as ex:
         results = list(ex.map(random_trace, tasks))
     pack_traces("trace_pool_ext.npz" if ext else "trace_pool.npz", jobs, results, decks0, decks1)
+
+
+def gen_live(name, n_games, steps, seed0, jobs, ext=False, must=(), deck=None, deck2=None, expert=False):
+    """The slices of difffuzz.py that tests/test_reference_live.py replays: the same games (seeds, decks drawn as
+    difffuzz.py draws them, policy seed + 1000), the same comparands (legal list, state, observation, features, reward,
+    done after every step), recorded here so that the test needs no reference tree."""
+    pool = [c for c in H.CARD_IDS if (ext or c not in UNSUPPORTED) and c not in FAULT_CARDS]
+    tasks, decks0, decks1 = [], [], []
+    for k in range(n_games):
+        seed = seed0 + k
+        if deck is None:
+            rs = np.random.RandomState(seed ^ 0x9E3779B9)
+            rest = [c for c in pool if c not in must]
+            d0 = list(must) + list(rs.choice(rest, 12 - len(must), replace=False))
+            d1 = list(must) + list(rs.choice(rest, 12 - len(must), replace=False))
+        else:
+            d0, d1 = H.DECKS[deck], H.DECKS[deck2 or deck]
+        tasks.append((seed, d0, d1, steps, True, expert))
+        decks0.append(idx(d0))
+        decks1.append(idx(d1))
+    with ProcessPoolExecutor(jobs) as ex:
+        results = list(ex.map(random_trace, tasks))
+    pack_traces(name, jobs, results, decks0, decks1)
 
 
 def gen_pool_up(n_games, steps, jobs):
@@ -437,6 +462,20 @@ def gen_population():
                         off_weights=np.array([i.get_weights() for i in off]), off_sigmas=np.array([i.get_sigmas() for i in off]))
 
 
+def gen_checkpoint():
+    """The reference's own checkpoint (Population.save_population, evo/population.py:280-294) of the population that
+    tests/test_reference_live.py exports with Population.save_reference_checkpoint: mu = lambda = 12, seed 9, generation 7,
+    fitness i / 12.  The test compares the two pickles' classes and contents without the reference tree."""
+    from evo.config import EvolutionaryConfig
+    from evo.population import Population
+    with contextlib.redirect_stdout(io.StringIO()):
+        pop = Population(EvolutionaryConfig(mu=12, lambda_=12, seed=9))
+        pop.initialize_population(10)
+        pop.fitness_scores = [i / 12 for i in range(12)]
+        pop.generation = 7
+        pop.save_population(os.path.join(GOLD, "checkpoint_reference.pkl"))
+
+
 def gen_decks():
     """utils.generate_random_deck / DeckEvolutionConfig of the reference, Python's global `random` seeded per case."""
     import json
@@ -501,6 +540,12 @@ def main():
                                                      [264, 1374, 2103, 2458, 2649, 3525, 3540, 6149, 3691, 4215, 4593, 5070, 29409], 200, args.jobs),
         "heuristic_IRONCLAD": lambda: gen_heuristic(12, 120, args.jobs, "IRONCLAD", "SWARM", 400),
         "decks": gen_decks,
+        # tests/test_reference_live.py: the difffuzz.py runs it replays
+        "live_pool": lambda: gen_live("trace_live_pool.npz", 30, 300, 88000, args.jobs),
+        "live_pool_ext": lambda: gen_live("trace_live_pool_ext.npz", 30, 300, 89000, args.jobs, ext=True),
+        "live_b005": lambda: gen_live("trace_live_b005.npz", 40, 300, 90000, args.jobs, ext=True, must=("b005",)),
+        "live_expert": lambda: gen_live("trace_live_expert.npz", 12, 300, 91000, args.jobs, deck="IRONCLAD", deck2="SWARM", expert=True),
+        "checkpoint": gen_checkpoint,
     }
     for name, fn in todo.items():
         if args.only and args.only != name:

@@ -4,7 +4,7 @@
 TAG=${1:-r03}
 mkdir -p gpurun_out
 O=gpurun_out/validate_${TAG}
-timeout -k 10 300 python bench.py > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err; echo "bench rc=$?"
 for w in c3 c4 c5; do
   timeout -k 10 300 python bench.py --workload $w > ${O}_bench_$w.json 2> ${O}_bench_$w.err; echo "bench $w rc=$?"
 done

@@ -121,6 +121,35 @@ def test_bench_refuses_more_gpus_than_the_machine_has():
     assert "refusing" in err
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: after the timed steps, the last step's outputs as float64 .npy files, the same from run to run,
+    at most 64 MB in all (a larger batch is cut to a fixed sample of its rows); the stand-in's state shows that exactly
+    --steps steps were timed.  CPU: bench.py's stand-in engine (MONSOON_BENCH_FAKE, a test hook)."""
+    env = {"MONSOON_BENCH_FAKE": "1"}
+    shapes = {"state_hash": (64, 2), "status": (64, 4), "features": (64, 10), "game_faults": (64,)}
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        rc, lines, err = _run_bench(["--steps", "3", "--warmup", "1", "--games", "64", "--dump-outputs", str(out)], env)
+        assert rc == 0, err[-2000:]
+        assert len(lines) == 1 and lines[0]["steps"] == 3 and lines[0]["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == sorted(f"{n}.npy" for n in shapes)
+        runs.append({n: np.load(out / f"{n}.npy") for n in shapes})
+        for n, shape in shapes.items():
+            assert runs[-1][n].dtype == np.float64 and runs[-1][n].shape == shape, n
+    for n in shapes:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+    h = np.arange(64, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(8 * 3)   # the stand-in's hash after 3 steps of 8 rounds
+    assert np.array_equal(runs[0]["state_hash"].astype(np.uint64), np.stack([h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)], axis=1))
+    out = tmp_path / "big"
+    rc, lines, err = _run_bench(["--steps", "1", "--warmup", "0", "--games", "600000", "--dump-outputs", str(out)], env)
+    assert rc == 0, err[-2000:]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+    rows = np.load(out / "sample_rows.npy")
+    assert len(rows) > 400000 and np.all(np.diff(rows) > 0) and rows[-1] < 600000
+    assert np.load(out / "features.npy").shape == (len(rows), 10)
+
+
 def test_replace_capacity_faulted_rewrites_only_the_overflowing_rows():
     """Host logic of the replay tier (monsoon_amd/fitness.py): rows with a fault code >= 16 are replaced by the replay's,
     their first attempt's contribution to the per-individual counts is taken out, everything else is untouched."""
