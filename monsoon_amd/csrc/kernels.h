@@ -1,21 +1,23 @@
 // kernels.h -- device code shared by every translation unit of libmonsoon_hip.so: per-game buffers, stream-block
-// maintenance, and the hot kernel k_play as a template over {candidate lanes per game U, waves per SIMD W} (the builds'
-// default is its sibling k_play_reg, kernels_reg.h: the same decision loop with the game's record in registers).  Each
+// maintenance, and the hot kernel k_play as a template over {candidate lanes per game U, waves per SIMD W}.  Each
 // instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
 // (variant.hip, built in parallel by the Makefile); monsoon_hip.hip holds the API kernels and the host side.
 //
 // Execution model
 //   * Hot kernel k_play<U,W>: ONE WAVEFRONT PER GAME at a time (a persistent grid of resident wavefronts, each popping
-//     game indices from its range's counter).  The game's record is staged from HBM into LDS once and stays there
-//     for up to `rounds` decisions.  Per decision: the legal-action mask is evaluated on that shared copy (LDS
-//     broadcast reads); then up to U candidate actions are advanced at once, lane l stepping its own private copy
-//     of the state.  The private copies are interleaved across lanes in 16-byte granules (granule c of lane l at
-//     (c*U + l)*16), so lanes touching the same field hit distinct LDS banks and a whole entity is one
-//     ds_read_b128.  Scores are reduced with shuffles over the U candidate lanes (first maximum in ascending action
-//     order = np.argmax over the sorted legal list) and the winner's column becomes the game's record.  Nothing
-//     is re-executed: the committed successor IS one of the look-ahead results (when the legal set needs several
-//     passes of U lanes, the best successor so far is parked in the game's HBM record), and its features are the next
-//     decision's "before" features.
+//     game indices from its range's counter).  The game's record is loaded from HBM into REGISTERS once and stays
+//     there for up to `rounds` decisions: a record is SG granules of 16 bytes, and lane l keeps granules l, l + 64, ...
+//     of the current record (v_par) and of the best successor found so far in this decision (v_best) -- one granule =
+//     four VGPRs each on the standard record.  Per decision: up to U candidate actions are advanced at once, lane l
+//     stepping its own private copy of the state in LDS.  The private copies are interleaved across lanes in 16-byte
+//     granules (granule c of lane l at (c*U + l)*16), so lanes touching the same field hit distinct LDS banks and a
+//     whole entity is one ds_read_b128; cloning is U 16-byte LDS writes per lane straight from registers.  The
+//     functions that read the current record (end of game, legal mask, features, stream cursor) find its image in
+//     candidate column 0, written there from the registers before they run (Col0Mem, state.h).  Scores are reduced
+//     with shuffles over the U candidate lanes (first maximum in ascending action order = np.argmax over the sorted
+//     legal list); a new best is one 16-byte LDS read per lane into v_best, and the commit is a register move.
+//     Nothing is re-executed: the committed successor IS one of the look-ahead results, also when the legal set
+//     needs several passes of U lanes, and its features are the next decision's "before" features.
 //   * The game's MT19937 stream lives in HBM as two blocks of tempered outputs (current + next) plus the raw
 //     state; candidate steps read it through a private cursor, the committed cursor travels with the record and
 //     the wave regenerates a block (twist in LDS) when it is used up.
@@ -83,8 +85,8 @@ static_assert(SKW >= SK_NEED + 9 && SKW * 4 >= 80, "room for the largest frame +
 constexpr int OVF_WORDS = SK_CAP;   // per stepping lane
 
 enum { ST_LOOKAHEAD = 0, ST_DECISIONS = 1, ST_FINISHED = 2, ST_FAULTS = 3, ST_CAPFAULTS = 4, ST_LACAPFAULTS = 5, ST_N = 6, ST_PROF = 8, ST_WORDS = 32, PROF_WORDS = 138 };
-// Phase timing of k_decide (profiling build only, -DMSB_PROF=1 -> libmonsoon_hip_prof.so; never the product):
-// wave cycles per phase accumulated into stats[ST_PROF + phase].
+// Phase timing of k_play (profiling build only, -DMSB_PROF=1 -> libmonsoon_hip_prof.so; never the product):
+// wave cycles per phase (PROF_MARK(0..7) in play_game) accumulated into the game's row of b.prof.
 #if defined(MSB_PROF) && MSB_PROF
 #define PROF_DECL()                                                                                   \
   unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                          \
@@ -195,11 +197,12 @@ __device__ inline void lane_commit_rng(const DevBuffers& b, int g, GameMeta& m, 
 constexpr int LDS_ORIGIN = LDS_RECORDS;
 
 // ------------------------------------------------------------------------------------------------
-// Hot kernel: a wavefront takes a game, keeps its record in LDS and plays up to `rounds` decisions of it (look-ahead +
-// score + argmax + commit each) before it writes the record back and takes the next game.
-// Dynamic LDS map (bytes): weight table | [PRIV, +SG*U*16) candidate records, lane-interleaved in 16-byte granules |
-// the game's current record | 10 weights + 10 "before" + 10 "best after" features |
-// the candidates' "after" features | the candidates' work stacks (SKW words each, interleaved word by word)
+// Hot kernel: a wavefront takes a game, keeps its record in registers and plays up to `rounds` decisions of it
+// (look-ahead + score + argmax + commit each) before it writes the record back and takes the next game.
+// Dynamic LDS map (bytes): weight table | [PRIV, +SG*U*16) candidate records, lane-interleaved in 16-byte granules
+// (column 0 doubles as the image of the current record, the whole area as the twist buffer) |
+// 10 weights + 10 "before" + 10 "best after" features | the candidates' work stacks (SKW words each, interleaved word by
+// word), which hold their "after" features once a pass has stepped
 // ------------------------------------------------------------------------------------------------
 __device__ MSB_INL int nth_set_bit(const uint64_t mask[3], int k) {
   for (int w = 0; w < 3; w++) {
@@ -214,30 +217,30 @@ __device__ MSB_INL int nth_set_bit(const uint64_t mask[3], int k) {
   return -1;
 }
 
-template <int U>
-struct DecideLds {
-  static constexpr int PRIV = LDS_ORIGIN;
-  static constexpr int PRIV_BYTES = SG * U * 16 > MT_N * 4 ? SG * U * 16 : ((MT_N * 4 + 15) & ~15);   // doubles as the twist buffer
-  static constexpr int PAR = PRIV + PRIV_BYTES;      // the game's current record
-  static constexpr int WF = PAR + SG * 16;           // 10 weights + 10 "before" features + 10 features of the best successor (f64)
-  static constexpr int SKB = WF + 240;               // work stacks of the U candidate lanes ...
-  static constexpr int CF = SKB;                     // ... and, once a pass has stepped (stacks empty), their ten "after" features each (f64)
-  static constexpr int TOTAL = SKB + U * SKW * 4;
-};
-
 __device__ MSB_INL unsigned long long uni64(unsigned long long v) {   // a wave-uniform 64-bit value into scalar registers
   unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
   unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
   return ((unsigned long long)hi << 32) | lo;
 }
 
-// Up to `rounds` decisions of game g by the calling wavefront.  The record lives in LDS from the first decision to
-// the last; HBM sees one read and one write of it per call.
+template <int U>
+struct PlayLds {
+  static constexpr int PRIV = LDS_ORIGIN;
+  static constexpr int PRIV_BYTES = SG * U * 16 > MT_N * 4 ? SG * U * 16 : ((MT_N * 4 + 15) & ~15);   // doubles as the twist buffer
+  static constexpr int WF = PRIV + PRIV_BYTES;       // 10 weights + 10 "before" features + 10 features of the best successor (f64)
+  static constexpr int SKB = WF + 240;               // work stacks of the U candidate lanes ...
+  static constexpr int CF = SKB;                     // ... and, once a pass has stepped (stacks empty), their ten "after" features each (f64)
+  static constexpr int TOTAL = SKB + U * SKW * 4;
+};
+
+// Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
+// to the last; HBM sees one read and one write of it per call.
 template <int U>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores) {
-  typedef DecideLds<U> L;
-  typedef Engine<SharedMem<L::PAR>> ParEngine;
+  typedef PlayLds<U> L;
+  typedef Engine<Col0Mem<U, L::PRIV>> ParEngine;
   typedef Engine<LaneMem<U, L::PRIV, L::SKB, SKW>> CandEngine;
+  constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
   GameMeta meta = b.meta[g];
   if (meta.result != -2) {
     if (lane == 0) {
@@ -247,23 +250,33 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     return;
   }
   PROF_DECL();
-  MSB_AS_LDS u32x4* par = (MSB_AS_LDS u32x4*)(uintptr_t)L::PAR;
   MSB_AS_LDS u32x4* priv = (MSB_AS_LDS u32x4*)(uintptr_t)L::PRIV;
   MSB_AS_LDS double* wf = (MSB_AS_LDS double*)(uintptr_t)L::WF;
   MSB_AS_LDS double* cf = (MSB_AS_LDS double*)(uintptr_t)(L::CF + (lane < U ? lane : 0) * 80);   // this candidate lane's features
   u32x4* grec = (u32x4*)(b.state + (size_t)g * SW);
-  for (int c = lane; c < SG; c += 64) par[c] = grec[c];   // one coalesced 16-B-per-lane pass
-  __syncthreads();
+  u32x4 v_par[GPL], v_best[GPL];   // granules lane, lane + 64, ... of the current record / of the best successor so far
+#define MSB_EACH_GRANULE(body_)                   \
+  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) { \
+    const int gr_ = lane + 64 * j_;               \
+    if (gr_ < SG) { body_; }                      \
+  }
+  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
+  MSB_EACH_GRANULE(v_par[j_] = grec[gr_])   // coalesced 16-B-per-lane loads, straight into registers
+  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) v_best[j_] = v_par[j_];
   ParEngine pe;
   CandEngine ce;
+  // the image of the current record in column 0; with the stream window attached it is also what the clones start from
+  MSB_EACH_GRANULE(priv[gr_ * U] = v_par[j_])
+  __syncthreads();
   if (lane == 0) attach_rng(pe, b, g, meta.rng);
   __syncthreads();
+  MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])
   bool have_before = false;   // wf[10..19] holds the features of the CURRENT state (the committed successor's)
   double last_score = NAN;
   int played = 0;
   PROF_MARK(0);   // stage
 
-  for (int round = 0; round < rounds; round++) {
+  for (int round = 0; round < rounds; round++) {   // (column 0 == v_par here)
     // rollout contract: while not have_winner() and steps < max_turns
     if (pe.have_winner() || meta.steps >= max_turns) {
       int b0 = pe.pl_base(0), b1 = pe.pl_base(1);
@@ -304,18 +317,13 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     __syncthreads();
     PROF_MARK(2);   // before-features
 
-    // Running best over the passes (uniform across the wave).  When the legal set needs more than
-    // one pass, the best successor so far is parked in the game's record in HBM so that nothing is replayed.
-    // (Parking it in its own column and running later passes on the other U - 1 columns saves that record and the
-    // copy, but measured 6 % slower: more passes.)
+    // Running best over the passes (uniform across the wave); its record is v_best.
     constexpr int NONE_A = 1 << 20;
     double run_s = 0.0;
     int run_a = NONE_A;
     int cfault = 0;
     int feat_ok = 0;                  // wf[20..29] holds the features of the best successor so far
     int la_fault = 0;                 // first build-limit fault a look-ahead of this decision hit
-    int wl = 0;                       // column (lane) holding the committed successor
-    const bool multi = n_legal > U;
     for (int base = 0; base < n_legal; base += U) {
       int k = base + lane;
       double s = 0.0;   // except Exception -> 0.0 (evo/heuristic_agent.py:48-51)
@@ -324,13 +332,10 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       int my_feat = 0;
       int f = 0;
       bool raises = false;
-      // copy.deepcopy (stream window included) for the whole pass, by all 64 lanes: granule idx of the interleaved
-      // candidate image is record granule idx / U for column idx % U
-      {
+      {   // copy.deepcopy (stream window included) for the whole pass: lane l writes granule l of every column in use
         const int n_act = n_legal - base < U ? n_legal - base : U;
         __syncthreads();
-        for (int idx = lane; idx < SG * U; idx += 64)
-          if ((idx & (U - 1)) < n_act) priv[idx] = par[idx / U];
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
       }
       const bool active = lane < U && k < n_legal;
@@ -351,8 +356,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 #endif
         const int n_act = n_legal - base < U ? n_legal - base : U;
         __syncthreads();
-        for (int idx = lane; idx < SG * U; idx += 64)
-          if ((idx & (U - 1)) < n_act) priv[idx] = par[idx / U];
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
       }
 #endif
@@ -365,8 +369,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       PROF_MARK(4);   // step
       if (active) {
         if (f == 0 && !before_raises && !raises) {
-          // the ten values go to LDS for the winner's sake (argmax below) and feed the score from registers; they are
-          // dead before the shuffles, so they never sit in registers across them
+          // the ten values go to LDS for the winner's sake (argmax below) and feed the score from registers
           double fa[10];
 #if defined(MSB_STUDY_FEATURES)
           {   // study build: the candidate's features and its score computed once more
@@ -410,32 +413,19 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         run_s = cs;
         run_a = ca;
         unsigned long long bal = __ballot(a == ca);
-        wl = __ffsll((long long)bal) - 1;
+        const int wl = __ffsll((long long)bal) - 1;
         cfault = __builtin_amdgcn_readlane(my_fault, wl);
         feat_ok = __builtin_amdgcn_readlane(my_feat, wl);
         if (feat_ok && lane < 10)   // the winner keeps its features: the next decision's "before" side
           wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl * 10 + lane];
-        if (multi) {
-          // park it in the game's record in HBM: that slot is free while the live record sits in LDS (one coalesced
-          // 16-byte-per-lane store; a spare LDS record here would cost every wavefront a record's worth of LDS = two wavefronts per CU)
-          __syncthreads();
-          for (int c = lane; c < SG; c += 64) grec[c] = priv[c * U + wl];
-        }
+        __syncthreads();
+        MSB_EACH_GRANULE(v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
       }
-      PROF_MARK(6);   // argmax + park
+      PROF_MARK(6);   // argmax + new best into registers
     }
-    __syncthreads();
     // commit: adapter = adapter.apply_action(best).  The successor carries its own stream cursor (H_RNGPOS).
-    if (multi) {
-      // read back what this wavefront parked: agent-scope loads, so that the per-CU vector cache cannot answer with an
-      // older line of the record
-      for (int c = lane; c < 2 * SG; c += 64) {
-        unsigned long long v = __hip_atomic_load((unsigned long long*)grec + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ((MSB_AS_LDS unsigned long long*)par)[c] = v;
-      }
-    } else {
-      for (int c = lane; c < SG; c += 64) par[c] = priv[c * U + wl];
-    }
+    __syncthreads();
+    MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])
     __syncthreads();
     {
       uint32_t new_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe.rng_pos());
@@ -443,6 +433,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if (new_pos >= (uint32_t)MT_N) {
         new_pos -= MT_N;
         wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);   // the used-up block becomes the new "next" block
+        MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])               // (the twist buffer is the column area)
+        __syncthreads();
         cur ^= 1;
         if (lane == 0) pe.rng_block_advance();
       }
@@ -452,6 +444,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       have_before = feat_ok != 0;
       if (have_before && lane < 10) wf[10 + lane] = wf[20 + lane];
       __syncthreads();
+      MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])
     }
     meta.steps++;
     meta.last_action = (uint8_t)run_a;
@@ -468,8 +461,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       break;
     }
   }
-  __syncthreads();
-  for (int c = lane; c < SG; c += 64) grec[c] = par[c];
+  MSB_EACH_GRANULE(grec[gr_] = v_par[j_])
+#undef MSB_EACH_GRANULE
   if (lane == 0) {
     b.meta[g] = meta;
     if (b.best) b.best[g] = last_score;
@@ -515,8 +508,6 @@ __global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_t
 // What the host needs to launch one variant (variant.hip defines one getter per instantiation).
 struct VariantOps {
   int lanes, wpe;           // U, W
-  int kind;                 // variants.def's third column: 1 k_play, 2 / 4 k_play_multi, 10 k_play_reg
-  int games;                // games a wavefront plays at once (k_play_multi: 2 or 4; else 1)
   int lds_bytes;            // dynamic LDS of one workgroup
   hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
   void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,

@@ -31,7 +31,7 @@ constexpr int NUM_ENT = 254;  // the LARGE record: every slot id a byte can name
 constexpr int NUM_ENT = 64;
 #else
 // 20 tiles + 4 transient (dead / displaced / spawned this step).  Round 3: 24 instead of 28 -- a 752-byte record, which
-// together with the best successor parked in HBM lets 20 instead of 17 wavefronts share a CU's LDS.  No step of 68 000
+// let 20 instead of 17 wavefronts of the LDS-record kernel of that time share a CU's LDS.  No step of 68 000
 // heuristic games on five deck families (N12M, S12, N12V, Ironclad vs Swarm, 20 000 random 107-card deck pairs) needs a
 // 25th slot (22 slots: one game does, 21: 30 games; scripts/capacity_standard.py); a game that ever does reports
 // FAULT_CAPACITY and the rollout path plays it again on the extended record (64 slots), like any other record limit.
@@ -391,42 +391,9 @@ struct TraceLaneMem : LaneMem<LANES, BASE, SKB, SKW> {
     }
   }
 };
-template <int BASE>
-struct SharedMem {   // one contiguous record read by every lane of the wave (LDS broadcast)
-  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* b(int o) { return (MSB_AS_LDS uint8_t*)(uintptr_t)(BASE + o); }
-  MSB_HD MSB_INL static int ld8(int o) { return *b(o); }
-  MSB_HD MSB_INL static void st8(int o, int v) { *b(o) = (uint8_t)v; }
-  MSB_HD MSB_INL static int ld16(int o) { return *(MSB_AS_LDS const int16_t*)b(o); }
-  MSB_HD MSB_INL static void st16(int o, int v) { *(MSB_AS_LDS int16_t*)b(o) = (int16_t)v; }
-  MSB_HD MSB_INL static uint32_t ld32(int o) { return *(MSB_AS_LDS const uint32_t*)b(o); }
-  MSB_HD MSB_INL static void st32(int o, uint32_t v) { *(MSB_AS_LDS uint32_t*)b(o) = v; }
-  MSB_HD MSB_INL static double ldf(int o) { return *(MSB_AS_LDS const double*)b(o); }
-  MSB_HD MSB_INL static void stf(int o, double v) { *(MSB_AS_LDS double*)b(o) = v; }
-  MSB_HD MSB_INL static uint64_t ld64(int o) { return *(MSB_AS_LDS const uint64_t*)b(o); }
-  MSB_HD MSB_INL static void st64(int o, uint64_t v) { *(MSB_AS_LDS uint64_t*)b(o) = v; }
-  MSB_HD MSB_INL static msb_u32x4 ld128(int o) { return *(MSB_AS_LDS const msb_u32x4*)b(o); }
-  MSB_HD MSB_INL static void st128(int o, msb_u32x4 v) { *(MSB_AS_LDS msb_u32x4*)b(o) = v; }
-  MSB_HD MSB_INL static int ld8g(int g, int k) { return ld8(g * 16 + k); }
-  MSB_HD MSB_INL static void st8g(int g, int k, int v) { st8(g * 16 + k, v); }
-  MSB_HD MSB_INL static int ld16g(int g, int k) { return ld16(g * 16 + k); }
-  MSB_HD MSB_INL static void st16g(int g, int k, int v) { st16(g * 16 + k, v); }
-  MSB_HD MSB_INL static msb_u32x4 ld128g(int g) { return ld128(g * 16); }
-  MSB_HD MSB_INL static void st128g(int g, msb_u32x4 v) { st128(g * 16, v); }
-  MSB_HD MSB_INL static uint32_t ld32g(int g, int k) { return ld32(g * 16 + k); }
-  MSB_HD MSB_INL static void st32g(int g, int k, uint32_t v) { st32(g * 16 + k, v); }
-  MSB_HD MSB_INL static double ldfg(int g, int k) { return ldf(g * 16 + k); }
-  MSB_HD MSB_INL static void stfg(int g, int k, double v) { stf(g * 16 + k, v); }
-  MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
-  MSB_HD MSB_INL static void trace_ability(int, int) {}
-  // the shared copy is only read (legal mask, features): nothing is ever stepped through it
-  static constexpr int SKW = SK_CAP;
-  MSB_HD MSB_INL static uint32_t sk_ld(int) { return 0; }
-  MSB_HD MSB_INL static void sk_st(int, uint32_t) {}
-  MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }
-  MSB_HD MSB_INL static void ovf_st(int, uint32_t) {}
-};
-// Column 0 of a lane-interleaved image (LaneMem<LANES, BASE, ..>), addressed by every lane alike: where kernels_reg.h keeps
-// the LDS image of the game's current record (the record itself lives in registers there).  Read-mostly like SharedMem.
+// Column 0 of a lane-interleaved image (LaneMem<LANES, BASE, ..>), addressed by every lane alike: where the hot kernel
+// (kernels.h) keeps the LDS image of the game's current record (the record itself lives in registers there).  Only read:
+// nothing is stepped through it.
 template <int LANES, int BASE>
 struct Col0Mem {
   MSB_HD MSB_INL static MSB_AS_LDS uint8_t* b(int o) { return (MSB_AS_LDS uint8_t*)(uintptr_t)(BASE + (o >> 4) * (LANES * 16) + (o & 15)); }
@@ -456,43 +423,6 @@ struct Col0Mem {
   MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
   MSB_HD MSB_INL static void trace_ability(int, int) {}
   static constexpr int SKW = SK_CAP;   // (nothing is stepped through it)
-  MSB_HD MSB_INL static uint32_t sk_ld(int) { return 0; }
-  MSB_HD MSB_INL static void sk_st(int, uint32_t) {}
-  MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }
-  MSB_HD MSB_INL static void ovf_st(int, uint32_t) {}
-};
-// The same for a wavefront that plays several games at once (kernels_multi.h): lanes [k*U, (k+1)*U) belong to game slot k,
-// whose current record sits at BASE + k*STRIDE.
-template <int BASE, int STRIDE, int U>
-struct GroupMem {
-  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* b(int o) {
-    return (MSB_AS_LDS uint8_t*)(uintptr_t)(BASE + ((int)__builtin_amdgcn_workitem_id_x() / U) * STRIDE + o);
-  }
-  MSB_HD MSB_INL static int ld8(int o) { return *b(o); }
-  MSB_HD MSB_INL static void st8(int o, int v) { *b(o) = (uint8_t)v; }
-  MSB_HD MSB_INL static int ld16(int o) { return *(MSB_AS_LDS const int16_t*)b(o); }
-  MSB_HD MSB_INL static void st16(int o, int v) { *(MSB_AS_LDS int16_t*)b(o) = (int16_t)v; }
-  MSB_HD MSB_INL static uint32_t ld32(int o) { return *(MSB_AS_LDS const uint32_t*)b(o); }
-  MSB_HD MSB_INL static void st32(int o, uint32_t v) { *(MSB_AS_LDS uint32_t*)b(o) = v; }
-  MSB_HD MSB_INL static double ldf(int o) { return *(MSB_AS_LDS const double*)b(o); }
-  MSB_HD MSB_INL static void stf(int o, double v) { *(MSB_AS_LDS double*)b(o) = v; }
-  MSB_HD MSB_INL static uint64_t ld64(int o) { return *(MSB_AS_LDS const uint64_t*)b(o); }
-  MSB_HD MSB_INL static void st64(int o, uint64_t v) { *(MSB_AS_LDS uint64_t*)b(o) = v; }
-  MSB_HD MSB_INL static msb_u32x4 ld128(int o) { return *(MSB_AS_LDS const msb_u32x4*)b(o); }
-  MSB_HD MSB_INL static void st128(int o, msb_u32x4 v) { *(MSB_AS_LDS msb_u32x4*)b(o) = v; }
-  MSB_HD MSB_INL static int ld8g(int g, int k) { return ld8(g * 16 + k); }
-  MSB_HD MSB_INL static void st8g(int g, int k, int v) { st8(g * 16 + k, v); }
-  MSB_HD MSB_INL static int ld16g(int g, int k) { return ld16(g * 16 + k); }
-  MSB_HD MSB_INL static void st16g(int g, int k, int v) { st16(g * 16 + k, v); }
-  MSB_HD MSB_INL static msb_u32x4 ld128g(int g) { return ld128(g * 16); }
-  MSB_HD MSB_INL static void st128g(int g, msb_u32x4 v) { st128(g * 16, v); }
-  MSB_HD MSB_INL static uint32_t ld32g(int g, int k) { return ld32(g * 16 + k); }
-  MSB_HD MSB_INL static void st32g(int g, int k, uint32_t v) { st32(g * 16 + k, v); }
-  MSB_HD MSB_INL static double ldfg(int g, int k) { return ldf(g * 16 + k); }
-  MSB_HD MSB_INL static void stfg(int g, int k, double v) { stf(g * 16 + k, v); }
-  MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
-  MSB_HD MSB_INL static void trace_ability(int, int) {}
-  static constexpr int SKW = SK_CAP;   // (read only, like SharedMem: nothing is stepped through it)
   MSB_HD MSB_INL static uint32_t sk_ld(int) { return 0; }
   MSB_HD MSB_INL static void sk_st(int, uint32_t) {}
   MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""k_play phase timing (wave cycles per phase) with the profiling build libmonsoon_hip_prof.so.
+"""k_play phase timing (wave cycles per phase) with the profiling build libmonsoon_hip_prof.so, whose one variant is
+the standard build's default (8 lanes, 5 waves per SIMD): the phase profile times the kernel that ships.
 
     make -C monsoon_amd/csrc prof && gpurun -- python scripts/phase_profile.py [--games 65536]
 The profiling library is a diagnostics build of the same source (-DMSB_PROF=1); the package never loads it.
@@ -19,7 +20,7 @@ L.LIB_PATH = os.path.join(REPO, "monsoon_amd", os.environ.get("MSB_PROF_LIB", "l
 from monsoon_amd.cards import deck_indices  # noqa: E402
 from monsoon_amd.engine import BatchEngine  # noqa: E402
 
-PHASES = ["stage", "legal mask", "before-features", "clone", "step", "after-features+score", "argmax+park", "commit+refill"]
+PHASES = ["stage", "legal mask", "before-features", "clone", "step", "after-features+score", "argmax+new best", "commit+refill"]
 
 
 def main():

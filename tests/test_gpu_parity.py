@@ -174,8 +174,9 @@ def test_heuristic_two_weight_vectors_vs_reference(engines, gold):
 
 @pytest.mark.parametrize("lanes", [4, 8, 16, 32, 64])
 def test_rollout_vs_oracle_2048_games(engines, lanes):
-    """Every hot-kernel variant of the build (candidate lanes per game; 4 and 8 lanes force several passes per decision
-    and the parked-best path) gives the oracle's games, played to the end inside one launch."""
+    """Every hot-kernel variant of the build (candidate lanes per game; 4 and 8 lanes force several passes per decision,
+    the best successor so far carried across them in registers) gives the oracle's games, played to the end inside one
+    launch."""
     n = 2048
     deck = deck_indices("N12M")
     eng = engines(n, lanes)
@@ -196,19 +197,16 @@ def test_rollout_vs_oracle_2048_games(engines, lanes):
     assert st["capacity_faults"] == 0 and st["lookahead_capacity_faults"] == 0
 
 
-@pytest.mark.parametrize("games_per_wave", [1, 2, 4])
-def test_the_other_kinds_of_hot_kernel_give_the_same_games(monkeypatch, games_per_wave):
-    """The standard build's default hot kernel keeps a game's record in registers (csrc/kernels_reg.h).  The other kinds at
-    8 lanes -- k_play with the record in LDS (kind 1, the kernel of the other builds and lane counts) and k_play_multi
-    (csrc/kernels_multi.h: a wavefront plays 2 or 4 games at once, lanes [8k, 8k+8) game slot k; slower,
-    profiles/r03_ab_games_per_wave.txt) -- play the same games: whole rollouts, a ragged tail, a schedule of two weight
-    vectors and the 8-decisions-per-launch form all equal the CPU replay and the default kernel."""
+def test_ragged_tail_and_persistent_rounds_give_the_same_games():
+    """The default hot kernel plays whole rollouts of a ragged batch with a schedule of two weight vectors as the CPU
+    replay does, and its 8-decisions-per-launch persistent form plays the same games as the 4-lane variant (same games,
+    several passes per decision)."""
     from monsoon_amd.engine import BatchEngine
-    monkeypatch.setenv("MONSOON_GAMES_PER_WAVE", str(games_per_wave))
-    n = 3001   # not a multiple of the slots: the last wavefront of the non-persistent form has empty slots
+    n = 3001   # a ragged batch size
     deck = deck_indices("N12M")
     eng = BatchEngine(8192)
     try:
+        assert eng.variant()[0] == 8
         w2 = np.stack([W0, np.random.RandomState(5).uniform(0, 1, 10)])
         matches = np.zeros(n, dtype=[("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", "<u4")])
         matches["seed"] = np.arange(n) + 300000
@@ -223,11 +221,11 @@ def test_the_other_kinds_of_hot_kernel_give_the_same_games(monkeypatch, games_pe
             ores[i], osteps[i], ohash[i] = r["result"], r["steps"], orc.canon_hash(i)
         assert np.array_equal(results, ores) and np.array_equal(steps, osteps) and np.array_equal(hashes[:n], ohash)
         assert counts[0, 2] == n
-        # decision rounds of 8 192 games (the persistent form: more games than slots), 8 per launch, against the default kernel
-        monkeypatch.delenv("MONSOON_GAMES_PER_WAVE")
-        ref = BatchEngine(8192)
+        # decision rounds of 8 192 games (the persistent form: more games than resident wavefronts), 8 per launch, against
+        # the 4-lane variant
+        ref = BatchEngine(8192, lanes_per_game=4)
         try:
-            assert ref.variant()[0] == 8
+            assert ref.variant()[0] == 4
             for e in (eng, ref):
                 e.reset(np.arange(8192, dtype=np.uint32) + 7, np.stack([deck, deck]))
                 e.reset_stats()
