@@ -201,7 +201,8 @@ int monsoon_ga_offspring(monsoon_t* h, monsoon_np_state* st, const double* paren
                          int64_t* out_tries);
 int monsoon_ga_select(monsoon_t* h, const double* fitness, int32_t n, int32_t* out_order);
 
-/* Diagnostics: 192 raw counter words (words 0-4 back monsoon_get_stats; a profiling build (-DMSB_PROF=1,
+/* Diagnostics: 192 raw counter words (words 0-4 back monsoon_get_stats; words 6 / 7 count the vector env's committed
+ * agent / bot steps since monsoon_env_reset; a profiling build (-DMSB_PROF=1,
  * scripts only) adds k_decide phase cycles at 8..15, per-function cycles / calls at 32..63 / 64..95, last-launch
  * occupancy at 96..101 and call entry / exit cycles at 128..159 / 160..191; the rest is zero).
  * No reference counterpart. */
@@ -225,6 +226,63 @@ int monsoon_kernel_time(monsoon_t* h, double* total_ms, int64_t* launches);
  * stream of its own (one handle = one device + one stream; independent handles are independent).  MONSOON_OWN_STREAM=0
  * in the environment puts all handles on the device's default stream (returned as NULL), as round 2 had to. */
 void* monsoon_stream(monsoon_t* h);
+
+/* Device-resident vector environment (Seam G, batched: games/abstract_game.py step / to_play / legal_actions / reset /
+ * expert_agent): n independent slots, each an endless sequence of episodes.  monsoon_env_step_dev checks every action
+ * against its slot's legal set, steps it, lets the reference's scripted bot answer (opponent 1), ends finished episodes,
+ * starts the next one in the same slot and writes the observation and legal mask of the state each slot is now in -- all
+ * on the handle's stream, without a host round trip, so a caller can capture it into a graph.
+ *
+ * Episode k of slot i starts from seed seed0[i] + k * seed_stride (mod 2^32).  Without a pool it is
+ * monsoon_reset(seed, decks[i], factions) with factions[i] for episode 0 and {0, 0} (monsoon_reset's NULL factions) for
+ * the later ones; episode 0 equals monsoon_reset(seed0[i], decks[i], factions[i]) bit for bit.  With a pool, every
+ * episode (episode 0 included) plays the decks monsoon_draw_decks draws from seed ^ 0x9E3779B9 (configuration C5).
+ *
+ * An episode ends after a committed step (the agent's or the bot's) that faults, whose observation would raise
+ * (FAULT_INT_CARD: the reference's step returns get_observation()), that leaves a winner (have_winner), or that brings its
+ * committed steps to max_steps (truncated).  A bot whose expert_action raises ends it with that fault.  The bot plays at
+ * most 64 actions per call: a bot still to play after that ends the episode with fault 27 (a guard of this library: the
+ * reference's bot can pick a USE whose index does nothing and costs nothing -- action 64 + 21 * c + 20 -- over and over
+ * and never end its turn; the tests require every fault 27 to be such a turn).  An episode can also end before the agent acts (the bot's opening turn,
+ * or a first state whose observation raises): the slot then reports that end at the next step, whatever its action. */
+typedef struct {
+  int32_t opponent;      /* 0 = none (the caller acts for whichever side is to play), 1 = the reference's scripted bot */
+  int32_t agent_side;    /* with opponent 1: 0 = agent plays FIRST, 1 = SECOND (the bot plays the other side) */
+  uint32_t seed_stride;  /* episode k of slot i starts from seed0[i] + k * seed_stride (mod 2^32); 0 = n */
+  int32_t max_steps;     /* an episode reaching this many committed steps (agent + bot) ends truncated; 0 = no limit, <= 65535 */
+  int32_t pool_n;        /* 0 = every episode of slot i uses the slot's reset decks; 12..128 = fresh decks per episode */
+  uint8_t pool[128];     /*   drawn as monsoon_draw_decks draws them, from the episode seed ^ 0x9E3779B9 */
+} monsoon_env_config;
+
+typedef struct {          /* caller-owned DEVICE buffers, n entries each; any may be NULL except done; obs and legal 4-byte aligned */
+  int32_t* obs;           /* n*540: observation of the state the slot is now in (after auto-reset / the bot's turn); 0 where it raises */
+  uint8_t* legal;         /* n*156 bytes 0/1 (viewable as torch.bool) */
+  uint8_t* obs_raises;    /* as monsoon_observe's raises */
+  uint8_t* to_play;
+  int8_t*  reward;        /* the reference's reward of the AGENT's own step, {0,1} (games/stormbound.py:366) */
+  uint8_t* done;          /* the episode ended in this call (winner, fault or truncation) */
+  int8_t*  winner;        /* at done: 0 FIRST, 1 SECOND, -1 draw/fault/truncated (rollout contract); -2 otherwise */
+  uint8_t* truncated;
+  uint8_t* fault;         /* fault code that ended the episode (msb_base.h), 0 = none */
+  uint8_t* illegal;       /* the action was not legal: the slot was left untouched */
+  int32_t* episode;       /* episodes completed by the slot so far */
+  uint64_t* final_hash;   /* at done: FNV-1a 64 of the canonical record the episode ended in (as monsoon_state_hash); 0 otherwise */
+} monsoon_env_views;
+
+/* Allocates the env's workspace, binds the views (kept until the next monsoon_env_reset), loads episode 0 of every slot
+ * (with opponent 1 and agent_side 1 the bot's opening turn is played) and writes its observation and legal mask; the
+ * per-call views read as after a step that ended nothing.  Host arguments: seed0[n], decks[n][2][12] (NULL, and only NULL,
+ * with a pool), factions[n][2] or NULL.  A deck or pool card this build does not support is refused (MONSOON_ERR_ARG).
+ * Synchronises.  The env's slots are the handle's loaded games: monsoon_state_hash, monsoon_observe, monsoon_state_save
+ * and the rest work on them; monsoon_reset or monsoon_rollout ends env mode. */
+int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon_env_views* views, int32_t n,
+                      const uint32_t* seed0, const uint8_t* decks, const uint8_t* factions);
+/* One step of every slot; actions_dev = n bytes of DEVICE memory: 255 leaves the slot untouched, 155 (PASS) is always
+ * accepted, any other action must be legal, else illegal[i] = 1 and the slot is left untouched.  A slot whose episode
+ * ended gets done / winner / truncated / fault / final_hash of that episode, episode[i] + 1, and the observation and legal
+ * mask of its next episode's first state.  Asynchronous: enqueues three launches on the handle's stream (no allocation,
+ * copy or synchronisation); MONSOON_ERR_STATE without a preceding monsoon_env_reset or after monsoon_reset. */
+int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,16 @@ class NpState(ctypes.Structure):   # monsoon_np_state: numpy.random.RandomState.
     _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_int32), ("has_gauss", ctypes.c_int32), ("gauss", ctypes.c_double)]
 
 
+class EnvConfig(ctypes.Structure):   # monsoon_env_config
+    _fields_ = [("opponent", ctypes.c_int32), ("agent_side", ctypes.c_int32), ("seed_stride", ctypes.c_uint32),
+                ("max_steps", ctypes.c_int32), ("pool_n", ctypes.c_int32), ("pool", ctypes.c_uint8 * 128)]
+
+
+class EnvViews(ctypes.Structure):    # monsoon_env_views: caller-owned device buffers (NULL = not wanted, except done)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "legal", "obs_raises", "to_play", "reward", "done", "winner",
+                                                      "truncated", "fault", "illegal", "episode", "final_hash")]
+
+
 SIGNATURES = {
     "monsoon_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "monsoon_destroy": (None, [ctypes.c_void_p]),
@@ -93,6 +103,9 @@ SIGNATURES = {
     "monsoon_reset_stats": (ctypes.c_int, [ctypes.c_void_p]),
     "monsoon_kernel_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     "monsoon_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "monsoon_env_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvViews), ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 

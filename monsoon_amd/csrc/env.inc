@@ -1,0 +1,218 @@
+// env.inc -- the device-resident vector environment (monsoon_env_reset / monsoon_env_step_dev, include/monsoon.h).
+// Included by monsoon_hip.hip inside its anonymous namespace, after the lane-per-game API kernels whose layout it uses
+// (ApiEngine, API_LANES, api_load / api_store, attach_rng / lane_commit_rng), so all three record builds get it.
+//
+//   k_env_step    lane per slot: ONE record load for the legality check, the agent's step, the scripted bot's turn, the
+//                 end of the episode (winner / fault / truncation, final hash) and, for slots still live, the observation,
+//                 legal bytes and to_play; one store.  Marks the slots whose episode ended.
+//   k_env_reseed  wavefront per slot (grid n): marked slots only -- the next episode's stream (k_seed's code) and, with a
+//                 pool, its decks (k_draw_decks' code).
+//   k_env_init    lane per slot, marked slots only: init_game, the bot's opening turn when the agent is SECOND, then the
+//                 observation, legal bytes and to_play of the new episode's first state.
+//
+// A slot's episode is over when its GameMeta.result is no longer -2 (flags b1 = truncated); k_env_init starts every
+// episode with result -2.  Nothing here synchronises with the host: the three launches can be captured into a graph.
+
+constexpr int ENV_BOT_BOUND = 64;              // bot actions per call before FAULT_BOT_BOUND (a guard, include/monsoon.h)
+constexpr uint32_t ENV_POOL_XOR = 0x9E3779B9u;   // the decks' pre-stream (configuration C5, monsoon_draw_decks)
+
+struct EnvDev {
+  monsoon_env_views v;      // the caller's views (any pointer but done may be null)
+  const uint32_t* seed0;    // [n]
+  uint8_t* decks;           // [n][24]: the decks of the slot's current episode
+  const uint8_t* factions;  // [n][2]: episode 0's factions (later episodes: 0, 0)
+  int32_t* episode;         // [n]: episodes completed
+  uint8_t* mark;            // [n]: 1 = the slot's episode ended, k_env_reseed / k_env_init start the next one
+  uint32_t* agent_steps;    // [n]: committed steps of the agent since monsoon_env_reset (monsoon_debug_counters word 6)
+  uint32_t* bot_steps;      // [n]: ... of the scripted bot (word 7)
+  const uint8_t* pool;      // [128]
+  int pool_n, opponent, agent_side, max_steps;
+  uint32_t stride;
+};
+
+__device__ MSB_INL uint32_t env_seed(const EnvDev& v, int g) { return v.seed0[g] + (uint32_t)v.episode[g] * v.stride; }
+
+// The stream cursor after an engine call that drew from it (as k_step / k_expert commit it), re-attached for the next call.
+__device__ MSB_INL void env_commit_rng(ApiEngine& e, const DevBuffers& b, int g, GameMeta& m) {
+  if (e.rng_pos() >= (uint32_t)MT_N) e.rng_block_advance();
+  lane_commit_rng(b, g, m, e.rng_pos());
+  attach_rng(e, b, g, m.rng);
+}
+
+__device__ MSB_INL void env_end(GameMeta& m, int result, int fault, bool truncated) {
+  m.result = (int8_t)result;
+  m.fault = (uint8_t)fault;
+  if (truncated) m.flags |= 2;
+}
+
+// After a committed step of either side: true when it ended the episode.  A fault first (the reference raises; its step
+// returns get_observation(), so an observation that would raise is one too), then a winner (rollout contract, DESIGN.md
+// §1), then truncation.
+__device__ MSB_INL bool env_after_step(ApiEngine& e, const DevBuffers& b, int g, GameMeta& m, int action, int max_steps) {
+  env_commit_rng(e, b, g, m);
+  m.steps++;
+  m.last_action = (uint8_t)action;
+  int f = e.fault();
+  if (!f && e.observation_raises()) f = FAULT_INT_CARD;
+  if (f) {
+    env_end(m, -1, f, false);
+  } else if (e.have_winner()) {
+    const int b0 = e.pl_base(0), b1 = e.pl_base(1);
+    env_end(m, (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1, 0, false);
+    m.flags |= 1;
+  } else if (max_steps && m.steps >= max_steps) {
+    env_end(m, -1, 0, true);
+  }
+  return m.result != -2;
+}
+
+// The reference's scripted bot (games/stormbound.py:563-637) plays while it is to play: expert_action, then step.
+// Returns the steps it committed.
+__device__ inline int env_bot_turn(ApiEngine& e, const DevBuffers& b, int g, GameMeta& m, const EnvDev& v) {
+  for (int k = 0; k < ENV_BOT_BOUND; k++) {
+    if (e.local() == v.agent_side) return k;
+    const int a = e.expert_action();
+    const int f = e.fault();
+    env_commit_rng(e, b, g, m);
+    if (f) {   // random.choice([]) inside the bot
+      env_end(m, -1, f, false);
+      return k;
+    }
+    e.step(a);
+    if (env_after_step(e, b, g, m, a, v.max_steps)) return k + 1;
+  }
+  if (e.local() != v.agent_side) env_end(m, -1, FAULT_BOT_BOUND, false);
+  return ENV_BOT_BOUND;
+}
+
+// The views that describe the state slot g is now in: to_play, legal bytes, observation (0 where it raises).
+__device__ MSB_INL void env_write_state(ApiEngine& e, const EnvDev& v, int g) {
+  if (v.v.to_play) v.v.to_play[g] = (uint8_t)e.local();
+  if (v.v.legal) {
+    const msb_u64x4 mask = e.legal_mask_v();
+    uint32_t* out = (uint32_t*)(v.v.legal + (size_t)g * MONSOON_NUM_ACTIONS);   // 156 = 39 words; 4-byte aligned (checked at reset)
+    for (int w = 0; w < MONSOON_NUM_ACTIONS / 4; w++) {
+      const uint64_t word = mask[w >> 4];
+      const int sh = (4 * w) & 63;
+      out[w] = (uint32_t)((word >> sh) & 1) | (uint32_t)((word >> (sh + 1)) & 1) << 8 | (uint32_t)((word >> (sh + 2)) & 1) << 16 |
+               (uint32_t)((word >> (sh + 3)) & 1) << 24;
+    }
+  }
+  if (v.v.obs || v.v.obs_raises) {
+    const bool r = e.observation_raises();
+    if (v.v.obs_raises) v.v.obs_raises[g] = r ? 1 : 0;
+    if (v.v.obs) {
+      int32_t* out = v.v.obs + (size_t)g * MONSOON_OBS_INTS;
+      if (r) {
+        for (int i = 0; i < MONSOON_OBS_INTS; i++) out[i] = 0;
+      } else {
+        e.observe(out);
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64) k_env_step(DevBuffers b, EnvDev v, int n, const uint8_t* actions) {
+  API_GAME_INDEX();
+  ApiEngine e;
+  api_load(b.state + (size_t)g * SW);
+  GameMeta m = b.meta[g];
+  const int a = actions[g];
+  int reward = 0, illegal = 0;
+  bool stepped = false;
+  if (m.result == -2 && a != 255) {   // an episode that ended before the agent could act is reported whatever the action
+    const msb_u64x4 mask = e.legal_mask_v();
+    const uint64_t word = a < 64 ? mask[0] : (a < 128 ? mask[1] : mask[2]);
+    // PASS (155) is always accepted, as k_step accepts it
+    if (a >= MONSOON_NUM_ACTIONS || (a != 155 && !((word >> (a & 63)) & 1))) {
+      illegal = 1;
+    } else {
+      attach_rng(e, b, g, m.rng);
+      reward = e.step(a) & 1;
+      stepped = true;
+      const int bot = (!env_after_step(e, b, g, m, a, v.max_steps) && v.opponent) ? env_bot_turn(e, b, g, m, v) : 0;
+      v.agent_steps[g] += 1;
+      v.bot_steps[g] += (uint32_t)bot;
+    }
+  }
+  const bool ended = m.result != -2;
+  const int ep = v.episode[g] + (ended ? 1 : 0);
+  v.episode[g] = ep;
+  v.mark[g] = ended ? 1 : 0;
+  v.v.done[g] = ended ? 1 : 0;
+  if (v.v.reward) v.v.reward[g] = (int8_t)reward;
+  if (v.v.illegal) v.v.illegal[g] = (uint8_t)illegal;
+  if (v.v.episode) v.v.episode[g] = ep;
+  if (v.v.winner) v.v.winner[g] = ended ? m.result : (int8_t)-2;
+  if (v.v.truncated) v.v.truncated[g] = (ended && (m.flags & 2)) ? 1 : 0;
+  if (v.v.fault) v.v.fault[g] = ended ? m.fault : 0;
+  if (v.v.final_hash) {
+    uint64_t hsh = 0;
+    if (ended) {
+      uint8_t rec[CANON_MAX];
+      hsh = fnv1a64(rec, canon_record(e, peek_u32(b, g, m.rng), rec));
+    }
+    v.v.final_hash[g] = hsh;
+  }
+  if (stepped) {
+    b.meta[g] = m;
+    api_store(b.state + (size_t)g * SW);
+  }
+  if (!ended) env_write_state(e, v, g);
+}
+
+// k_env_step marked the slots whose episode ended: the next episode's stream and decks.  One wavefront per slot.
+__global__ void __launch_bounds__(64) k_env_reseed(DevBuffers b, EnvDev v, int n) {
+  __shared__ uint32_t mt[MT_N];
+  __shared__ uint32_t words[2 * MT_N];
+  __shared__ uint8_t perm[128];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  if (g >= n || !v.mark[g]) return;
+  const uint32_t seed = env_seed(v, g);
+  MSB_AS_LDS uint32_t* t = (MSB_AS_LDS uint32_t*)mt;
+  if (v.pool_n) {
+    // the 1 248 outputs run out for no realistic seed (expected use: 270); k_draw_decks reports it, the env cannot
+    (void)wave_draw_decks(seed ^ ENV_POOL_XOR, v.pool, v.pool_n, v.decks + (size_t)g * 24, t, (MSB_AS_LDS uint32_t*)words,
+                          (MSB_AS_LDS uint8_t*)perm, lane);
+    __syncthreads();
+  }
+  wave_seed_game(b, g, seed, t, lane);
+}
+
+// The first state of the next episode of every marked slot (k_init's code), the bot's opening turn, the slot's views.
+// first = 1 (monsoon_env_reset): every slot is marked and the per-call views are cleared too.
+__global__ void __launch_bounds__(64) k_env_init(DevBuffers b, EnvDev v, int n, int first) {
+  API_GAME_INDEX();
+  if (!v.mark[g]) return;
+  ApiEngine e;
+  GameMeta m = GameMeta{};   // stream block 0, cursor 0: as k_env_reseed left it
+  attach_rng(e, b, g, m.rng);
+  const int ep = v.episode[g];
+  uint8_t d0[12], d1[12];
+  for (int i = 0; i < 12; i++) {
+    d0[i] = v.decks[(size_t)g * 24 + i];
+    d1[i] = v.decks[(size_t)g * 24 + 12 + i];
+  }
+  const int f0 = ep == 0 ? v.factions[2 * g] : 0, f1 = ep == 0 ? v.factions[2 * g + 1] : 0;
+  e.init_game(d0, d1, f0, f1, env_seed(v, g));
+  env_commit_rng(e, b, g, m);
+  m.result = -2;
+  m.last_action = 255;
+  int f = e.fault();
+  if (!f && e.observation_raises()) f = FAULT_INT_CARD;   // the reference's reset() returns get_observation()
+  if (f) env_end(m, -1, f, false);
+  else if (v.opponent && e.local() != v.agent_side) v.bot_steps[g] += (uint32_t)env_bot_turn(e, b, g, m, v);
+  b.meta[g] = m;
+  api_store(b.state + (size_t)g * SW);
+  if (first) {
+    v.v.done[g] = 0;
+    if (v.v.reward) v.v.reward[g] = 0;
+    if (v.v.illegal) v.v.illegal[g] = 0;
+    if (v.v.episode) v.v.episode[g] = 0;
+    if (v.v.winner) v.v.winner[g] = -2;
+    if (v.v.truncated) v.v.truncated[g] = 0;
+    if (v.v.fault) v.v.fault[g] = 0;
+    if (v.v.final_hash) v.v.final_hash[g] = 0;
+  }
+  env_write_state(e, v, g);
+}

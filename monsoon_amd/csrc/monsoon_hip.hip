@@ -58,6 +58,29 @@ __device__ MSB_INL void api_store(uint32_t* dst) {
   for (int c = 0; c < SG; c++) d4[c] = *(MSB_AS_LDS const u32x4*)ApiMem::b(c * 16);
 }
 
+// init_genrand(seed) into t[0..623] (a serial recurrence: lane 0)
+__device__ inline void wave_init_genrand(MSB_AS_LDS uint32_t* t, uint32_t seed, int lane) {
+  if (lane == 0) {
+    uint32_t x = seed;
+    t[0] = x;
+    for (int i = 1; i < MT_N; i++) {
+      x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
+      t[i] = x;
+    }
+  }
+  __syncthreads();
+}
+
+// game g's stream = RandomState(seed): the raw state and its first two tempered blocks (t = 624 words of LDS)
+__device__ inline void wave_seed_game(const DevBuffers& b, int g, uint32_t seed, MSB_AS_LDS uint32_t* t, int lane) {
+  wave_init_genrand(t, seed, lane);
+  uint32_t* mt = b.rng_mt + (size_t)g * MT_N;
+  for (int k = lane; k < MT_N; k += 64) mt[k] = t[k];
+  __syncthreads();
+  wave_refill(b, g, 0, t, lane);
+  wave_refill(b, g, 1, t, lane);
+}
+
 __global__ void __launch_bounds__(64) k_seed(DevBuffers b, int g0, int n, const uint32_t* seeds) {
   // one wavefront per game (games g0 .. g0+n-1, seeds[0..n-1]): init_genrand is a serial recurrence (lane 0), the two
   // twists are wave-cooperative
@@ -66,21 +89,7 @@ __global__ void __launch_bounds__(64) k_seed(DevBuffers b, int g0, int n, const 
   if ((int)blockIdx.x >= n) return;
   int g = g0 + blockIdx.x;
   seeds -= g0;
-  MSB_AS_LDS uint32_t* t = (MSB_AS_LDS uint32_t*)tmp;
-  if (lane == 0) {
-    uint32_t x = seeds[g];
-    t[0] = x;
-    for (int i = 1; i < MT_N; i++) {
-      x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-      t[i] = x;
-    }
-  }
-  __syncthreads();
-  uint32_t* mt = b.rng_mt + (size_t)g * MT_N;
-  for (int k = lane; k < MT_N; k += 64) mt[k] = t[k];
-  __syncthreads();
-  wave_refill(b, g, 0, t, lane);
-  wave_refill(b, g, 1, t, lane);
+  wave_seed_game(b, g, seeds[g], (MSB_AS_LDS uint32_t*)tmp, lane);
 }
 
 __global__ void __launch_bounds__(64) k_init(DevBuffers b, int n, const uint8_t* decks, const uint8_t* factions, const uint32_t* seeds) {
@@ -414,28 +423,17 @@ __global__ void k_blob(DevBuffers b, int g, uint32_t* blob, int load) {
 // to a deck (player.py:28).  One wavefront per seed: init_genrand is a serial recurrence (lane 0), the two twists that
 // yield the first 1 248 outputs are wave-cooperative, the 2 x (len(pool) - 1) draws serial again.  A seed whose draws
 // need more than 1 248 outputs (expected: 270) is reported, never truncated.
-__global__ void __launch_bounds__(64) k_draw_decks(int n, const uint32_t* seeds, const uint8_t* pool, int pool_n, uint8_t* out, int* overrun) {
-  __shared__ uint32_t mt[MT_N];
-  __shared__ uint32_t words[2 * MT_N];
-  __shared__ uint8_t perm[128];
-  const int lane = threadIdx.x, g = blockIdx.x;
-  if (g >= n) return;
-  MSB_AS_LDS uint32_t* t = (MSB_AS_LDS uint32_t*)mt;
-  if (lane == 0) {
-    uint32_t x = seeds[g];
-    t[0] = x;
-    for (int i = 1; i < MT_N; i++) {
-      x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-      t[i] = x;
-    }
-  }
-  __syncthreads();
+// One seed's two draws (t: 624 words, words: 1 248 words, perm: 128 bytes of LDS); out24 = P1's deck, then P2's.
+// Returns true (lane 0) when the draws needed more than the 1 248 outputs.
+__device__ inline bool wave_draw_decks(uint32_t seed, const uint8_t* pool, int pool_n, uint8_t* out24, MSB_AS_LDS uint32_t* t,
+                                       MSB_AS_LDS uint32_t* words, MSB_AS_LDS uint8_t* perm, int lane) {
+  wave_init_genrand(t, seed, lane);
   for (int blk = 0; blk < 2; blk++) {
     wave_twist_lds(t, lane);
     for (int k = lane; k < MT_N; k += 64) words[blk * MT_N + k] = mt_temper(t[k]);
     __syncthreads();
   }
-  if (lane != 0) return;
+  if (lane != 0) return false;
   int pos = 0;
   bool over = false;
   for (int side = 0; side < 2; side++) {
@@ -458,10 +456,24 @@ __global__ void __launch_bounds__(64) k_draw_decks(int n, const uint32_t* seeds,
       perm[i] = perm[v];
       perm[v] = tmp;
     }
-    for (int k = 0; k < 12; k++) out[(size_t)g * 24 + side * 12 + k] = pool[perm[k]];
+    for (int k = 0; k < 12; k++) out24[side * 12 + k] = pool[perm[k]];
   }
+  return over;
+}
+
+__global__ void __launch_bounds__(64) k_draw_decks(int n, const uint32_t* seeds, const uint8_t* pool, int pool_n, uint8_t* out, int* overrun) {
+  __shared__ uint32_t mt[MT_N];
+  __shared__ uint32_t words[2 * MT_N];
+  __shared__ uint8_t perm[128];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  if (g >= n) return;
+  const bool over = wave_draw_decks(seeds[g], pool, pool_n, out + (size_t)g * 24, (MSB_AS_LDS uint32_t*)mt, (MSB_AS_LDS uint32_t*)words,
+                                    (MSB_AS_LDS uint8_t*)perm, lane);
   if (over) atomicAdd(overrun, 1);
 }
+
+// the vector env (monsoon_env_reset / monsoon_env_step_dev)
+#include "env.inc"
 
 // ------------------------------------------------------------------------------------------------
 // GA operators.  The reference's (mu + lambda) step draws everything from ONE global numpy
@@ -623,6 +635,11 @@ struct monsoon {
   size_t ev_used = 0;
   double kernel_ms = 0;
   long long kernel_launches = 0;
+  // vector env (monsoon_env_reset): workspace of max_games slots, allocated once; env_on until monsoon_reset / rollout
+  uint8_t* d_env = nullptr;   // seed0 u32 | episode i32 | agent steps u32 | bot steps u32 | decks [24] | factions [2] | mark | pool [128]
+  EnvDev env;
+  int env_n = 0;
+  bool env_on = false;
 };
 
 static std::string g_create_error;
@@ -701,7 +718,7 @@ void monsoon_destroy(monsoon_t* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps};
+                  h->d_counts, h->d_results, h->d_steps, h->d_env};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (auto& pr : h->ev_pool) {
@@ -862,6 +879,7 @@ int monsoon_reset(monsoon_t* h, int32_t n, const uint32_t* seeds, const uint8_t*
     if (h) h->err = "monsoon_reset: bad argument";
     return MONSOON_ERR_ARG;
   }
+  h->env_on = false;   // the env's slots are about to be replaced
   int rc = check_decks(h, decks, (size_t)n * 24, "monsoon_reset");
   if (rc) return rc;
   HIP_TRY(h, bind_device(h));
@@ -1480,6 +1498,7 @@ int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, 
                     int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                     int32_t* out_counts, int8_t* out_results, int32_t* out_steps) {
   if (!h) return MONSOON_ERR_ARG;
+  h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
       max_turns > 30000) {
     h->err = "monsoon_rollout: bad argument";
@@ -1623,6 +1642,16 @@ int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
     int rc = total_stats(h, out);
     if (rc) return rc;
   }
+  if (h->d_env && h->env_n > 0) {   // the vector env's committed agent / bot steps since monsoon_env_reset
+    const size_t cap = (size_t)h->cfg.max_games;
+    std::vector<uint32_t> st(2 * (size_t)h->env_n);
+    HIP_TRY(h, hipMemcpy(st.data(), h->d_env + 8 * cap, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(st.data() + h->env_n, h->d_env + 12 * cap, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < h->env_n; i++) {
+      out[6] += st[i];
+      out[7] += st[h->env_n + i];
+    }
+  }
 #if defined(MSB_PROF) && MSB_PROF
   {
     std::vector<unsigned long long> v((size_t)h->cfg.max_games * PROF_WORDS);
@@ -1699,5 +1728,89 @@ int monsoon_kernel_time(monsoon_t* h, double* total_ms, int64_t* launches) {
 }
 
 void* monsoon_stream(monsoon_t* h) { return h ? (void*)h->stream : nullptr; }
+
+// ---- vector env (env.inc) -----------------------------------------------------------------------
+int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon_env_views* views, int32_t n, const uint32_t* seed0,
+                      const uint8_t* decks, const uint8_t* factions) {
+  if (!h) return MONSOON_ERR_ARG;
+  const char* bad = nullptr;
+  if (!cfg || !views || !seed0 || n <= 0 || n > h->cfg.max_games) bad = "bad argument (1 <= n <= max_games)";
+  else if (!views->done) bad = "views.done is required";
+  else if (cfg->opponent != 0 && cfg->opponent != 1) bad = "opponent must be 0 (none) or 1 (scripted bot)";
+  else if (cfg->agent_side != 0 && cfg->agent_side != 1) bad = "agent_side must be 0 or 1";
+  else if (cfg->max_steps < 0 || cfg->max_steps > 65535) bad = "0 <= max_steps <= 65535";
+  else if (cfg->pool_n != 0 && (cfg->pool_n < 12 || cfg->pool_n > 128)) bad = "pool_n must be 0 or 12..128";
+  else if (!cfg->pool_n && !decks) bad = "decks are required without a pool";
+  else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
+  else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
+  if (bad) {
+    h->err = std::string("monsoon_env_reset: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  int rc = cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)") : check_decks(h, decks, (size_t)n * 24, "monsoon_env_reset");
+  if (rc) return rc;
+  HIP_TRY(h, bind_device(h));
+  rc = fold_stats(h);   // statistics live in the per-game rows that are about to be cleared
+  if (rc) return rc;
+  h->env_on = false;
+  const size_t cap = (size_t)h->cfg.max_games;
+  if (!h->d_env) HIP_TRY(h, hipMalloc(&h->d_env, 44 * cap + 128));
+  EnvDev& v = h->env;
+  uint8_t* base = h->d_env;
+  v.v = *views;
+  v.seed0 = (const uint32_t*)base;
+  v.episode = (int32_t*)(base + 4 * cap);
+  v.agent_steps = (uint32_t*)(base + 8 * cap);
+  v.bot_steps = (uint32_t*)(base + 12 * cap);
+  v.decks = base + 16 * cap;
+  v.factions = base + 40 * cap;
+  v.mark = base + 42 * cap;
+  v.pool = base + 43 * cap;
+  v.pool_n = cfg->pool_n;
+  v.opponent = cfg->opponent;
+  v.agent_side = cfg->agent_side;
+  v.max_steps = cfg->max_steps;
+  v.stride = cfg->seed_stride ? cfg->seed_stride : (uint32_t)n;
+  HIP_TRY(h, hipMemcpyAsync((void*)v.seed0, seed0, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  if (decks) HIP_TRY(h, hipMemcpyAsync(v.decks, decks, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
+  if (factions)
+    HIP_TRY(h, hipMemcpyAsync((void*)v.factions, factions, (size_t)n * 2, hipMemcpyHostToDevice, h->stream));
+  else
+    HIP_TRY(h, hipMemsetAsync((void*)v.factions, 0, (size_t)n * 2, h->stream));
+  if (cfg->pool_n) HIP_TRY(h, hipMemcpyAsync((void*)v.pool, cfg->pool, (size_t)cfg->pool_n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(v.episode, 0, (size_t)n * 4, h->stream));
+  HIP_TRY(h, hipMemsetAsync(v.agent_steps, 0, (size_t)n * 4, h->stream));
+  HIP_TRY(h, hipMemsetAsync(v.bot_steps, 0, (size_t)n * 4, h->stream));
+  HIP_TRY(h, hipMemsetAsync(v.mark, 1, (size_t)n, h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->b.meta, 0, (size_t)n * sizeof(GameMeta), h->stream));
+  hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, v, n);
+  hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, v, n, 1);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->n = n;
+  h->env_n = n;
+  h->env_on = true;
+  return MONSOON_OK;
+}
+
+// Enqueues the three env kernels on the handle's stream and returns: no allocation, copy or synchronisation (graph-capturable).
+int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_step_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  if (!actions_dev) {
+    h->err = "monsoon_env_step_dev: actions_dev is NULL";
+    return MONSOON_ERR_ARG;
+  }
+  HIP_TRY(h, bind_device(h));
+  const int n = h->env_n;
+  hipLaunchKernelGGL(k_env_step, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, actions_dev);
+  hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, h->env, n);
+  hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, 0);
+  HIP_TRY(h, hipGetLastError());
+  return MONSOON_OK;
+}
 
 }  // extern "C"

@@ -117,6 +117,8 @@ enum : int {
   FAULT_CAP_HAND = 24,      // hand entries
   FAULT_CAP_PATH = 25,      // path longer than PATH_CAP
   FAULT_CAP_INST = 26,      // card-instance strength outside 0..255
+  FAULT_BOT_BOUND = 27,     // vector env: the scripted bot still to play after 64 actions in one call (env.inc; the
+                            // reference's bot can repeat a USE that does nothing for ever)
 };
 
 // ---- static card table -----------------------------------------------------------------

@@ -183,6 +183,32 @@ class BatchEngine:
         self._ck(self.lib.monsoon_state_hash(self.h, _ptr(out)), "monsoon_state_hash")
         return out
 
+    # ---- vector env (monsoon_amd/vec_env.py drives these) ----------------------------------------
+    def env_reset(self, config, views, seed0, decks=None, factions=None):
+        """monsoon_env_reset: config = _lib.EnvConfig, views = _lib.EnvViews of device pointers; host seed0[n],
+        decks[n][2][12] (None with a pool), factions[n][2] or None.  Synchronises."""
+        seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
+        n = len(seed0)
+        if decks is not None:
+            decks = np.ascontiguousarray(decks, dtype=np.uint8)
+            if decks.shape == (2, 12):
+                decks = np.broadcast_to(decks, (n, 2, 12)).copy()
+            if decks.shape != (n, 2, 12):
+                raise ValueError(f"decks must be [n][2][12], got {decks.shape}")
+        if factions is not None:
+            factions = np.ascontiguousarray(factions, dtype=np.uint8).reshape(n, 2)
+        self._ck(self.lib.monsoon_env_reset(self.h, ctypes.byref(config), ctypes.byref(views), n, _ptr(seed0), _ptr(decks),
+                                            _ptr(factions)), "monsoon_env_reset")
+        self.n = n
+
+    def env_step_dev(self, actions_ptr):
+        """monsoon_env_step_dev on n bytes of device memory at actions_ptr (asynchronous on the handle's stream)."""
+        self._ck(self.lib.monsoon_env_step_dev(self.h, ctypes.c_void_p(actions_ptr)), "monsoon_env_step_dev")
+
+    def stream_ptr(self):
+        """The hipStream_t the handle launches on (monsoon_stream), as an integer."""
+        return self.lib.monsoon_stream(self.h) or 0
+
     # ---- Seam F ---------------------------------------------------------------------------
     def decide(self, weights, want_scores=False):
         weights = np.ascontiguousarray(weights, dtype=np.float64)

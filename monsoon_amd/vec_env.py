@@ -1,0 +1,124 @@
+"""VecEnv: the device-resident vector environment (monsoon_env_reset / monsoon_env_step_dev) as torch tensors.
+
+Seam G batched for a learner that lives on the GPU: n slots of games/abstract_game.py's interface (step, to_play,
+legal_actions, reset, expert_agent as the opponent), each an endless sequence of episodes that restart in place.  One
+`step` is three kernel launches on the handle's stream -- legality check, step, the scripted bot's turn, end of episode,
+re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.
+torch is used for device memory and stream ordering only; there is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+
+from ._lib import EnvConfig, EnvViews, MonsoonError
+from .engine import BatchEngine
+
+OPPONENTS = {"none": 0, "expert": 1}
+
+# name -> (trailing shape, torch dtype name); the order of monsoon_env_views
+_VIEWS = (("obs", (27, 5, 4), "int32"), ("legal", (156,), "bool"), ("obs_raises", (), "bool"), ("to_play", (), "uint8"),
+          ("reward", (), "int8"), ("done", (), "bool"), ("winner", (), "int8"), ("truncated", (), "bool"), ("fault", (), "uint8"),
+          ("illegal", (), "bool"), ("episode", (), "int32"), ("final_hash", (), "int64"))
+
+
+class VecEnv:
+    """n game slots on one GPU.  reset() loads episode 0 of every slot; step(actions) advances every slot by the agent's
+    action (and the bot's answer), restarts finished episodes and returns the view tensors.  See include/monsoon.h
+    (monsoon_env_*) for the contract and INTEGRATION.md for a trainer loop."""
+
+    def __init__(self, max_slots, device=0, extended=0, lanes_per_game=0):
+        """extended = 0 / 1 / 2 selects the record build (1: decks holding ua20 / b005).  Raises MonsoonError when no
+        gfx950 device is usable."""
+        self.engine = BatchEngine(max_slots, device=device, lanes_per_game=lanes_per_game, extended=extended)
+        self.device = device
+        self.extended = extended
+        self.n = 0
+        self.views = None
+
+    def close(self):
+        if self.engine is not None:
+            self.engine.close()
+            self.engine = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    @property
+    def stream(self):
+        """The handle's stream as a torch stream: order your own work against it, or capture env.step on it."""
+        import torch
+        return torch.cuda.ExternalStream(self.engine.stream_ptr(), device=torch.device("cuda", self.device))
+
+    def _alloc(self, n):
+        import torch
+        dev = torch.device("cuda", self.device)
+        views = {}
+        for name, shape, dt in _VIEWS:
+            views[name] = torch.zeros((n,) + shape, dtype=getattr(torch, dt), device=dev)
+        return views
+
+    def reset(self, seed0, decks=None, factions=None, opponent="none", agent_side=0, max_steps=0, pool=None, seed_stride=0):
+        """Episode 0 of every slot: slot i plays seed0[i] with decks[i] ([n][2][12] or one [2][12] pair for all) and
+        factions[i]; episode k then starts from seed0[i] + k * seed_stride (0 = n).  pool (12..128 card indices) draws
+        fresh decks for every episode instead (decks must be None).  opponent "expert" puts the reference's scripted bot on
+        the side that agent_side does not play.  max_steps > 0 truncates episodes.  Returns the view tensors (a dict)."""
+        import torch
+        if opponent not in OPPONENTS:
+            raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
+        seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
+        n = len(seed0)
+        if pool is None and decks is None:
+            raise ValueError("decks are required without a pool")
+        cfg = EnvConfig()
+        cfg.opponent = OPPONENTS[opponent]
+        cfg.agent_side = int(agent_side)
+        cfg.seed_stride = int(seed_stride) & 0xFFFFFFFF
+        cfg.max_steps = int(max_steps)
+        if pool is not None:
+            pool = np.ascontiguousarray(pool, dtype=np.uint8)
+            if not 12 <= len(pool) <= 128:
+                raise ValueError("a pool holds 12..128 cards")
+            cfg.pool_n = len(pool)
+            ctypes.memmove(cfg.pool, pool.ctypes.data, len(pool))
+        if self.views is None or self.n != n:
+            self.engine.sync()
+            self.views = self._alloc(n)
+        self.n = n
+        views = EnvViews(**{name: t.data_ptr() for name, t in self.views.items()})
+        # the views may still be read by work queued on torch's stream
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        try:
+            self.engine.env_reset(cfg, views, seed0, decks, factions)
+        finally:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return self.views
+
+    def step(self, actions):
+        """Advance every slot: actions is a uint8 CUDA tensor [n] (255 = leave the slot alone, 155 = PASS, any other
+        action must be legal, else views["illegal"][i] is set and the slot is left untouched).  Asynchronous: returns the
+        SAME view tensors reset() returned, overwritten in place on the env's stream (torch's current stream is made to
+        wait for it); copy what you want to keep before the next step."""
+        import torch
+        if self.views is None:
+            raise MonsoonError("VecEnv.step before reset")
+        if not isinstance(actions, torch.Tensor) or actions.dtype != torch.uint8 or not actions.is_cuda or actions.shape != (self.n,):
+            raise ValueError(f"actions must be a uint8 CUDA tensor of shape ({self.n},)")
+        actions = actions.contiguous()
+        cur = torch.cuda.current_stream(self.device)
+        env = self.stream
+        if cur.cuda_stream != env.cuda_stream:
+            env.wait_stream(cur)   # the actions were written on torch's stream
+        self.engine.env_step_dev(actions.data_ptr())
+        if cur.cuda_stream != env.cuda_stream:
+            cur.wait_stream(env)
+        return self.views
+
+    def state_hash(self):
+        """monsoon_state_hash of every slot's current state (synchronises)."""
+        return self.engine.state_hash()
+
+
+__all__ = ["VecEnv", "OPPONENTS", "MonsoonError"]
