@@ -202,7 +202,8 @@ int monsoon_ga_offspring(monsoon_t* h, monsoon_np_state* st, const double* paren
 int monsoon_ga_select(monsoon_t* h, const double* fitness, int32_t n, int32_t* out_order);
 
 /* Diagnostics: 192 raw counter words (words 0-4 back monsoon_get_stats; words 6 / 7 count the vector env's committed
- * agent / bot steps since monsoon_env_reset; a profiling build (-DMSB_PROF=1,
+ * agent / opponent steps since monsoon_env_reset, word 7 those of either opponent kind, scripted bot or heuristic agent;
+ * word 16 the heuristic opponent's look-ahead transitions since monsoon_env_reset; a profiling build (-DMSB_PROF=1,
  * scripts only) adds k_decide phase cycles at 8..15, per-function cycles / calls at 32..63 / 64..95, last-launch
  * occupancy at 96..101 and call entry / exit cycles at 128..159 / 160..191; the rest is zero).
  * No reference counterpart. */
@@ -244,10 +245,18 @@ void* monsoon_stream(monsoon_t* h);
  * most 64 actions per call: a bot still to play after that ends the episode with fault 27 (a guard of this library: the
  * reference's bot can pick a USE whose index does nothing and costs nothing -- action 64 + 21 * c + 20 -- over and over
  * and never end its turn; the tests require every fault 27 to be such a turn).  An episode can also end before the agent acts (the bot's opening turn,
- * or a first state whose observation raises): the slot then reports that end at the next step, whatever its action. */
+ * or a first state whose observation raises): the slot then reports that end at the next step, whatever its action.
+ *
+ * Opponent 2 is the reference's HeuristicAgent (evo/heuristic_agent.py) with the weights monsoon_env_set_opponents gives
+ * each slot.  It plays the side agent_side does not play, while that side is to play; each of its decisions is exactly
+ * monsoon_decide's (1-ply look-ahead over every legal action, score, first maximum, commit), and the episode ends by the
+ * rules above after each of its committed steps.  It plays at most 64 decisions per call: an opponent still to play
+ * after that ends the episode with fault 28 (FAULT_OPP_BOUND, the same guard as fault 27: a no-op USE that wins the
+ * argmax once wins it for ever from the identical state).  With agent_side 1 it plays the opening turn of every episode. */
 typedef struct {
-  int32_t opponent;      /* 0 = none (the caller acts for whichever side is to play), 1 = the reference's scripted bot */
-  int32_t agent_side;    /* with opponent 1: 0 = agent plays FIRST, 1 = SECOND (the bot plays the other side) */
+  int32_t opponent;      /* 0 = none (the caller acts for whichever side is to play), 1 = the reference's scripted bot,
+                            2 = the reference's HeuristicAgent (monsoon_env_set_opponents first) */
+  int32_t agent_side;    /* with opponent 1 or 2: 0 = agent plays FIRST, 1 = SECOND (the opponent plays the other side) */
   uint32_t seed_stride;  /* episode k of slot i starts from seed0[i] + k * seed_stride (mod 2^32); 0 = n */
   int32_t max_steps;     /* an episode reaching this many committed steps (agent + bot) ends truncated; 0 = no limit, <= 65535 */
   int32_t pool_n;        /* 0 = every episode of slot i uses the slot's reset decks; 12..128 = fresh decks per episode */
@@ -280,9 +289,18 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
 /* One step of every slot; actions_dev = n bytes of DEVICE memory: 255 leaves the slot untouched, 155 (PASS) is always
  * accepted, any other action must be legal, else illegal[i] = 1 and the slot is left untouched.  A slot whose episode
  * ended gets done / winner / truncated / fault / final_hash of that episode, episode[i] + 1, and the observation and legal
- * mask of its next episode's first state.  Asynchronous: enqueues three launches on the handle's stream (no allocation,
- * copy or synchronisation); MONSOON_ERR_STATE without a preceding monsoon_env_reset or after monsoon_reset. */
+ * mask of its next episode's first state.  Asynchronous: enqueues three launches on the handle's stream (seven with
+ * opponent 2; no allocation, copy or synchronisation); MONSOON_ERR_STATE without a preceding monsoon_env_reset or after
+ * monsoon_reset. */
 int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev);
+
+/* The heuristic opponents of opponent 2: weights[n_individuals][10] (host), and rows[n] (host), the weight row slot i's
+ * opponent plays (NULL = row 0 for every slot).  Required before monsoon_env_reset with opponent 2 (else it returns
+ * MONSOON_ERR_STATE), whose n must equal this n.  May be called again between steps: the new table and rows apply from the
+ * next decision (a league update).  The table is allocated for the n_individuals given before the reset and never
+ * reallocated while an opponent-2 env is loaded, so a captured step stays valid: a call with more rows then, a row outside
+ * [0, n_individuals) or an n different from the loaded env's returns MONSOON_ERR_ARG.  Synchronises. */
+int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_individuals, const int32_t* rows, int32_t n);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,7 @@ SIGNATURES = {
     "monsoon_env_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvViews), ctypes.c_int32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
 }
 
 

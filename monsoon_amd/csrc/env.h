@@ -1,0 +1,41 @@
+// env.h -- what the vector env's two translation units share: the device-side view of the env (EnvDev) and the launch
+// table of the heuristic opponent's kernel (k_env_opp, env_opp.hip).  monsoon_hip.hip holds the env's lane-per-slot
+// kernels (env.inc) and the host side.
+#pragma once
+#include "kernels.h"
+
+namespace msbk {
+
+constexpr int ENV_COUNT_STRIDE = 32;   // the two slot lists' counters, 128 bytes apart
+
+struct EnvDev {
+  monsoon_env_views v;      // the caller's views (any pointer but done may be null)
+  const uint32_t* seed0;    // [n]
+  uint8_t* decks;           // [n][24]: the decks of the slot's current episode
+  const uint8_t* factions;  // [n][2]: episode 0's factions (later episodes: 0, 0)
+  int32_t* episode;         // [n]: episodes completed
+  uint8_t* mark;            // [n]: 1 = the slot's episode ended, k_env_reseed / k_env_init start the next one
+  uint32_t* agent_steps;    // [n]: committed steps of the agent since monsoon_env_reset (monsoon_debug_counters word 6)
+  uint32_t* bot_steps;      // [n]: ... of the opponent, scripted bot or heuristic (word 7)
+  const uint8_t* pool;      // [128]
+  // opponent 2 (the heuristic agent) only, else null
+  const int32_t* opp_rows;  // [n]: the weight-table row of slot g's opponent
+  int32_t* opp_list;        // [2][cap]: slots whose opponent is to play -- list 0 after the agent's step, list 1 new episodes
+  int32_t* opp_count;       // [2 * ENV_COUNT_STRIDE]: the lists' lengths (list l at l * ENV_COUNT_STRIDE)
+  int* opp_pop;             // [2][POP_PARTS * POP_STRIDE]: k_env_opp's pop counters, set l for list l
+  uint32_t* opp_lookahead;  // [n]: the opponent's look-ahead transitions since monsoon_env_reset (monsoon_debug_counters word 16)
+  int pool_n, opponent, agent_side, max_steps;
+  uint32_t stride;
+  int cap;                  // max_games: the stride of opp_list
+};
+
+// k_env_opp<U, W> at the build's default variant (env_opp.hip): one wavefront per listed slot plays the opponent's turn.
+struct EnvOppOps {
+  int lanes, wpe;   // U, W
+  int lds_bytes;    // dynamic LDS of one workgroup
+  hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
+  void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list);
+};
+const EnvOppOps* monsoon_env_opp_ops();
+
+}  // namespace msbk

@@ -1,34 +1,27 @@
 // env.inc -- the device-resident vector environment (monsoon_env_reset / monsoon_env_step_dev, include/monsoon.h).
 // Included by monsoon_hip.hip inside its anonymous namespace, after the lane-per-game API kernels whose layout it uses
-// (ApiEngine, API_LANES, api_load / api_store, attach_rng / lane_commit_rng), so all three record builds get it.
+// (ApiEngine, API_LANES, api_load / api_store, attach_rng / lane_commit_rng), so all three record builds get it.  EnvDev
+// is in env.h, shared with env_opp.hip (k_env_opp, the heuristic opponent).
 //
 //   k_env_step    lane per slot: ONE record load for the legality check, the agent's step, the scripted bot's turn, the
 //                 end of the episode (winner / fault / truncation, final hash) and, for slots still live, the observation,
-//                 legal bytes and to_play; one store.  Marks the slots whose episode ended.
+//                 legal bytes and to_play (env_finish); one store.  Marks the slots whose episode ended.  With the
+//                 heuristic opponent, a slot whose opponent is now to play is put on slot list 0 instead of finished.
+//   k_env_opp     (opponent 2) wavefront per listed slot: the opponent's turn (env_opp.hip).
+//   k_env_after_opp  (opponent 2) lane per listed slot: env_finish (list 0) or the state views (list 1).
 //   k_env_reseed  wavefront per slot (grid n): marked slots only -- the next episode's stream (k_seed's code) and, with a
 //                 pool, its decks (k_draw_decks' code).
 //   k_env_init    lane per slot, marked slots only: init_game, the bot's opening turn when the agent is SECOND, then the
-//                 observation, legal bytes and to_play of the new episode's first state.
+//                 observation, legal bytes and to_play of the new episode's first state.  With the heuristic opponent, a
+//                 new episode that opens with the opponent is put on slot list 1, and k_env_opp / k_env_after_opp follow.
 //
 // A slot's episode is over when its GameMeta.result is no longer -2 (flags b1 = truncated); k_env_init starts every
-// episode with result -2.  Nothing here synchronises with the host: the three launches can be captured into a graph.
+// episode with result -2.  Nothing here synchronises with the host: the launches can be captured into a graph.  A
+// list's length is cleared by a launch between its last reader and its next writer: list 1's by k_env_step, list 0's by
+// k_env_init.
 
 constexpr int ENV_BOT_BOUND = 64;              // bot actions per call before FAULT_BOT_BOUND (a guard, include/monsoon.h)
 constexpr uint32_t ENV_POOL_XOR = 0x9E3779B9u;   // the decks' pre-stream (configuration C5, monsoon_draw_decks)
-
-struct EnvDev {
-  monsoon_env_views v;      // the caller's views (any pointer but done may be null)
-  const uint32_t* seed0;    // [n]
-  uint8_t* decks;           // [n][24]: the decks of the slot's current episode
-  const uint8_t* factions;  // [n][2]: episode 0's factions (later episodes: 0, 0)
-  int32_t* episode;         // [n]: episodes completed
-  uint8_t* mark;            // [n]: 1 = the slot's episode ended, k_env_reseed / k_env_init start the next one
-  uint32_t* agent_steps;    // [n]: committed steps of the agent since monsoon_env_reset (monsoon_debug_counters word 6)
-  uint32_t* bot_steps;      // [n]: ... of the scripted bot (word 7)
-  const uint8_t* pool;      // [128]
-  int pool_n, opponent, agent_side, max_steps;
-  uint32_t stride;
-};
 
 __device__ MSB_INL uint32_t env_seed(const EnvDev& v, int g) { return v.seed0[g] + (uint32_t)v.episode[g] * v.stride; }
 
@@ -85,6 +78,19 @@ __device__ inline int env_bot_turn(ApiEngine& e, const DevBuffers& b, int g, Gam
   return ENV_BOT_BOUND;
 }
 
+// Puts the calling lanes with on = true on slot list `list`: one atomic per wavefront (same-address atomics serialise at
+// ~25 ns each, kernels.h), the lanes' places by rank in the ballot.
+__device__ MSB_INL void env_append(const EnvDev& v, int list, int g, bool on) {
+  const unsigned long long bal = __ballot(on);
+  if (!bal) return;
+  const int lane = (int)threadIdx.x & 63;
+  const int leader = __builtin_ctzll(bal);
+  int base = 0;
+  if (lane == leader) base = atomicAdd(&v.opp_count[list * ENV_COUNT_STRIDE], __popcll(bal));
+  base = __builtin_amdgcn_readlane(base, leader);
+  if (on) v.opp_list[(size_t)list * v.cap + base + __popcll(bal & ((1ull << lane) - 1))] = g;
+}
+
 // The views that describe the state slot g is now in: to_play, legal bytes, observation (0 where it raises).
 __device__ MSB_INL void env_write_state(ApiEngine& e, const EnvDev& v, int g) {
   if (v.v.to_play) v.v.to_play[g] = (uint8_t)e.local();
@@ -112,36 +118,14 @@ __device__ MSB_INL void env_write_state(ApiEngine& e, const EnvDev& v, int g) {
   }
 }
 
-__global__ void __launch_bounds__(64) k_env_step(DevBuffers b, EnvDev v, int n, const uint8_t* actions) {
-  API_GAME_INDEX();
-  ApiEngine e;
-  api_load(b.state + (size_t)g * SW);
-  GameMeta m = b.meta[g];
-  const int a = actions[g];
-  int reward = 0, illegal = 0;
-  bool stepped = false;
-  if (m.result == -2 && a != 255) {   // an episode that ended before the agent could act is reported whatever the action
-    const msb_u64x4 mask = e.legal_mask_v();
-    const uint64_t word = a < 64 ? mask[0] : (a < 128 ? mask[1] : mask[2]);
-    // PASS (155) is always accepted, as k_step accepts it
-    if (a >= MONSOON_NUM_ACTIONS || (a != 155 && !((word >> (a & 63)) & 1))) {
-      illegal = 1;
-    } else {
-      attach_rng(e, b, g, m.rng);
-      reward = e.step(a) & 1;
-      stepped = true;
-      const int bot = (!env_after_step(e, b, g, m, a, v.max_steps) && v.opponent) ? env_bot_turn(e, b, g, m, v) : 0;
-      v.agent_steps[g] += 1;
-      v.bot_steps[g] += (uint32_t)bot;
-    }
-  }
+// The end of a step for slot g, whose record is in e and meta in m: the episode count, the end-of-episode views, the
+// mark for k_env_reseed / k_env_init, and for a slot still live the views of its state.
+__device__ MSB_INL void env_finish(ApiEngine& e, const DevBuffers& b, const EnvDev& v, int g, const GameMeta& m) {
   const bool ended = m.result != -2;
   const int ep = v.episode[g] + (ended ? 1 : 0);
   v.episode[g] = ep;
   v.mark[g] = ended ? 1 : 0;
   v.v.done[g] = ended ? 1 : 0;
-  if (v.v.reward) v.v.reward[g] = (int8_t)reward;
-  if (v.v.illegal) v.v.illegal[g] = (uint8_t)illegal;
   if (v.v.episode) v.v.episode[g] = ep;
   if (v.v.winner) v.v.winner[g] = ended ? m.result : (int8_t)-2;
   if (v.v.truncated) v.v.truncated[g] = (ended && (m.flags & 2)) ? 1 : 0;
@@ -154,11 +138,61 @@ __global__ void __launch_bounds__(64) k_env_step(DevBuffers b, EnvDev v, int n, 
     }
     v.v.final_hash[g] = hsh;
   }
+  if (!ended) env_write_state(e, v, g);
+}
+
+__global__ void __launch_bounds__(64) k_env_step(DevBuffers b, EnvDev v, int n, const uint8_t* actions) {
+  API_GAME_INDEX();
+  if (v.opponent == 2 && g == 0) v.opp_count[ENV_COUNT_STRIDE] = 0;   // list 1: its readers ran in the previous call
+  ApiEngine e;
+  api_load(b.state + (size_t)g * SW);
+  GameMeta m = b.meta[g];
+  const int a = actions[g];
+  int reward = 0, illegal = 0;
+  bool stepped = false, opp_turn = false;
+  if (m.result == -2 && a != 255) {   // an episode that ended before the agent could act is reported whatever the action
+    const msb_u64x4 mask = e.legal_mask_v();
+    const uint64_t word = a < 64 ? mask[0] : (a < 128 ? mask[1] : mask[2]);
+    // PASS (155) is always accepted, as k_step accepts it
+    if (a >= MONSOON_NUM_ACTIONS || (a != 155 && !((word >> (a & 63)) & 1))) {
+      illegal = 1;
+    } else {
+      attach_rng(e, b, g, m.rng);
+      reward = e.step(a) & 1;
+      stepped = true;
+      const bool ended = env_after_step(e, b, g, m, a, v.max_steps);
+      const int bot = (!ended && v.opponent == 1) ? env_bot_turn(e, b, g, m, v) : 0;
+      opp_turn = !ended && v.opponent == 2 && e.local() != v.agent_side;   // k_env_opp plays it, k_env_after_opp finishes
+      v.agent_steps[g] += 1;
+      v.bot_steps[g] += (uint32_t)bot;
+    }
+  }
+  if (v.v.reward) v.v.reward[g] = (int8_t)reward;
+  if (v.v.illegal) v.v.illegal[g] = (uint8_t)illegal;
   if (stepped) {
     b.meta[g] = m;
     api_store(b.state + (size_t)g * SW);
   }
-  if (!ended) env_write_state(e, v, g);
+  if (v.opponent == 2) env_append(v, 0, g, opp_turn);
+  if (!opp_turn) env_finish(e, b, v, g, m);
+}
+
+// After k_env_opp: the slots of list `list`, a lane each.  List 0 (the agent's step handed the turn over): env_finish.
+// List 1 (a new episode opened with the opponent): the views of the state the opponent left.
+__global__ void __launch_bounds__(64) k_env_after_opp(DevBuffers b, EnvDev v, int list) {
+  const int count = v.opp_count[list * ENV_COUNT_STRIDE];
+  if ((int)blockIdx.x * API_LANES >= count) return;   // uniform: the grid covers n slots, the list is usually short
+  lds_init_wtab(b.wk_ovf + (size_t)blockIdx.x * (API_LANES * OVF_WORDS));
+  if ((int)threadIdx.x >= API_LANES) return;
+  const int i = blockIdx.x * API_LANES + threadIdx.x;
+  if (i >= count) return;
+  const int g = v.opp_list[(size_t)list * v.cap + i];
+  ApiEngine e;
+  api_load(b.state + (size_t)g * SW);
+  const GameMeta m = b.meta[g];
+  attach_rng(e, b, g, m.rng);
+  if (list == 0) env_finish(e, b, v, g, m);
+  else env_write_state(e, v, g);
 }
 
 // k_env_step marked the slots whose episode ended: the next episode's stream and decks.  One wavefront per slot.
@@ -183,6 +217,7 @@ __global__ void __launch_bounds__(64) k_env_reseed(DevBuffers b, EnvDev v, int n
 // first = 1 (monsoon_env_reset): every slot is marked and the per-call views are cleared too.
 __global__ void __launch_bounds__(64) k_env_init(DevBuffers b, EnvDev v, int n, int first) {
   API_GAME_INDEX();
+  if (v.opponent == 2 && g == 0) v.opp_count[0] = 0;   // list 0: its readers (k_env_opp, k_env_after_opp) ran before
   if (!v.mark[g]) return;
   ApiEngine e;
   GameMeta m = GameMeta{};   // stream block 0, cursor 0: as k_env_reseed left it
@@ -200,8 +235,10 @@ __global__ void __launch_bounds__(64) k_env_init(DevBuffers b, EnvDev v, int n, 
   m.last_action = 255;
   int f = e.fault();
   if (!f && e.observation_raises()) f = FAULT_INT_CARD;   // the reference's reset() returns get_observation()
+  bool opp_turn = false;
   if (f) env_end(m, -1, f, false);
-  else if (v.opponent && e.local() != v.agent_side) v.bot_steps[g] += (uint32_t)env_bot_turn(e, b, g, m, v);
+  else if (v.opponent == 1 && e.local() != v.agent_side) v.bot_steps[g] += (uint32_t)env_bot_turn(e, b, g, m, v);
+  else if (v.opponent == 2) opp_turn = e.local() != v.agent_side;   // the opening turn: k_env_opp on list 1
   b.meta[g] = m;
   api_store(b.state + (size_t)g * SW);
   if (first) {
@@ -214,5 +251,6 @@ __global__ void __launch_bounds__(64) k_env_init(DevBuffers b, EnvDev v, int n, 
     if (v.v.fault) v.v.fault[g] = 0;
     if (v.v.final_hash) v.v.final_hash[g] = 0;
   }
-  env_write_state(e, v, g);
+  if (v.opponent == 2) env_append(v, 1, g, opp_turn);
+  if (!opp_turn) env_write_state(e, v, g);
 }

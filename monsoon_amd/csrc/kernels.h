@@ -233,17 +233,31 @@ struct PlayLds {
   static constexpr int TOTAL = SKB + U * SKW * 4;
 };
 
+// The vector env's heuristic opponent (opponent 2, env_opp.hip): what play_game<U, true> needs beyond DevBuffers.
+constexpr int ENV_OPP_BOUND = 64;   // opponent decisions per call before FAULT_OPP_BOUND (a guard, include/monsoon.h)
+struct EnvPolicy {
+  const int32_t* rows;   // [n]: the weight-table row slot g's opponent plays
+  uint32_t* steps;       // [n]: the opponent's committed steps (monsoon_debug_counters word 7)
+  uint32_t* lookahead;   // [n]: its look-ahead transitions (word 16)
+  int agent_side, max_steps;
+};
+
 // Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
 // to the last; HBM sees one read and one write of it per call.
-template <int U>
-__device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores) {
+// ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
+// play, plays the weights of row pol.rows[g], ends the episode by the env's rules after every commit (fault, winner,
+// max_steps: include/monsoon.h), stops after `rounds` decisions with FAULT_OPP_BOUND, and writes no scores / best.
+template <int U, bool ENV = false>
+__device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
+                                  const EnvPolicy& pol) {
   typedef PlayLds<U> L;
   typedef Engine<Col0Mem<U, L::PRIV>> ParEngine;
   typedef Engine<LaneMem<U, L::PRIV, L::SKB, SKW>> CandEngine;
   constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
   GameMeta meta = b.meta[g];
+  const uint32_t lookahead0 = meta.lookahead;
   if (meta.result != -2) {
-    if (lane == 0) {
+    if (!ENV && lane == 0) {
       b.meta[g].last_action = 255;
       if (b.best) b.best[g] = NAN;
     }
@@ -277,8 +291,9 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   PROF_MARK(0);   // stage
 
   for (int round = 0; round < rounds; round++) {   // (column 0 == v_par here)
-    // rollout contract: while not have_winner() and steps < max_turns
-    if (pe.have_winner() || meta.steps >= max_turns) {
+    if constexpr (ENV) {
+      if (pe.local() == pol.agent_side) break;   // the agent's turn (the env's end rules ran after the last commit)
+    } else if (pe.have_winner() || meta.steps >= max_turns) {   // rollout contract: while not have_winner() and steps < max_turns
       int b0 = pe.pl_base(0), b1 = pe.pl_base(1);
       int res = -1;
       if (pe.have_winner()) res = (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1;
@@ -306,7 +321,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     const bool before_raises = pe.observation_raises();
     // weights and "before" features are parked in LDS: 40 fewer live VGPRs across the recursive step calls
     {
-      const double* wt = b.weights + (size_t)(pe.local() == 0 ? meta.p1 : meta.p2) * 10;
+      const double* wt = b.weights + (size_t)(ENV ? pol.rows[g] : (pe.local() == 0 ? meta.p1 : meta.p2)) * 10;
       if (lane < 10) wf[lane] = wt[lane];
       // The "before" features of this decision are the "after" features the previous decision computed for the
       // successor it committed (same state, same mover); only the first decision of a call computes them.
@@ -384,7 +399,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           s = CandEngine::action_score_lds(wf, fa);
           my_feat = 1;
         }
-        if (write_scores) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;
+        if (!ENV && write_scores) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;
         my_fault = f ? f : (raises ? FAULT_INT_CARD : 0);
       }
       PROF_MARK(5);   // after-features + score
@@ -460,12 +475,38 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       meta.result = -1;
       break;
     }
+    if constexpr (ENV) {   // the env's end rules (env.inc env_after_step): the fault above, then a winner, then truncation
+      if (pe.have_winner()) {
+        const int b0 = pe.pl_base(0), b1 = pe.pl_base(1);
+        meta.result = (int8_t)((b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1);
+        meta.flags |= 1;
+        break;
+      }
+      if (pol.max_steps && meta.steps >= pol.max_steps) {
+        meta.result = -1;
+        meta.flags |= 2;   // truncated
+        break;
+      }
+    }
+  }
+  if constexpr (ENV) {
+    // still to play after `rounds` decisions: a USE that does nothing and costs nothing won the argmax and wins it for
+    // ever from the identical state (the reference's loop only ends such a turn through max_turns)
+    if (meta.result == -2 && pe.local() != pol.agent_side) {
+      meta.result = -1;
+      meta.fault = FAULT_OPP_BOUND;
+    }
   }
   MSB_EACH_GRANULE(grec[gr_] = v_par[j_])
 #undef MSB_EACH_GRANULE
   if (lane == 0) {
     b.meta[g] = meta;
-    if (b.best) b.best[g] = last_score;
+    if constexpr (ENV) {
+      pol.steps[g] += (uint32_t)played;
+      pol.lookahead[g] += meta.lookahead - lookahead0;
+    } else if (b.best) {
+      b.best[g] = last_score;
+    }
   }
   PROF_FLUSH();
 }
@@ -499,7 +540,7 @@ __global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_t
   while (t < hi) {
     int nxt = 0x7fffffff;
     if (persistent && lane == 0) nxt = lo + waves + atomicAdd(&mine[part * POP_STRIDE], 1);
-    play_game<U>(b, t, lane, max_turns, rounds, write_scores);
+    play_game<U, false>(b, t, lane, max_turns, rounds, write_scores, EnvPolicy{});
     __syncthreads();   // the LDS image is reused by the next game
     t = __builtin_amdgcn_readfirstlane(nxt);
   }

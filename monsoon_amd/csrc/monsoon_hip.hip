@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "env.h"
 #include "kernels.h"
 
 using namespace msb;
@@ -640,6 +641,13 @@ struct monsoon {
   EnvDev env;
   int env_n = 0;
   bool env_on = false;
+  // the env's heuristic opponent (monsoon_env_set_opponents): d_opp is sized by max_games and allocated once; the weight
+  // table is never moved while an opponent-2 env is loaded (a captured step points to it)
+  uint8_t* d_opp = nullptr;   // rows i32 [cap] | slot lists i32 [2][cap] | look-ahead transitions u32 [cap] | list counts i32 [2 * ENV_COUNT_STRIDE] | pop counters i32 [2][POP_PARTS * POP_STRIDE]
+  double* d_opp_w = nullptr;  // [opp_w_cap][10]
+  int opp_w_cap = 0;          // rows allocated
+  int opp_n = 0;              // slots the last monsoon_env_set_opponents gave rows for (0 = never called)
+  int opp_grid = 0;           // k_env_opp's grid: resident wavefronts, at most the slots (queried at reset)
 };
 
 static std::string g_create_error;
@@ -718,7 +726,7 @@ void monsoon_destroy(monsoon_t* h) {
   if (h->stream) hipStreamSynchronize(h->stream);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps, h->d_env};
+                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (auto& pr : h->ev_pool) {
@@ -1651,6 +1659,10 @@ int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
       out[6] += st[i];
       out[7] += st[h->env_n + i];
     }
+    if (h->env.opp_lookahead) {   // the heuristic opponent's look-ahead transitions
+      HIP_TRY(h, hipMemcpy(st.data(), h->env.opp_lookahead, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < h->env_n; i++) out[16] += st[i];
+    }
   }
 #if defined(MSB_PROF) && MSB_PROF
   {
@@ -1730,22 +1742,79 @@ int monsoon_kernel_time(monsoon_t* h, double* total_ms, int64_t* launches) {
 void* monsoon_stream(monsoon_t* h) { return h ? (void*)h->stream : nullptr; }
 
 // ---- vector env (env.inc) -----------------------------------------------------------------------
+}  // extern "C"
+
+// The heuristic opponent's turn for the slots of list `list`, then their views: two launches, no synchronisation.
+// k_env_opp reads the env's weight table through its own DevBuffers copy (monsoon_upload_weights' table is not touched).
+static int launch_env_opp(monsoon_t* h, int n, int list) {
+  const EnvOppOps* o = monsoon_env_opp_ops();
+  DevBuffers ob = h->b;
+  ob.weights = h->d_opp_w;
+  ob.scores = nullptr;
+  ob.best = nullptr;
+  o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list);
+  hipLaunchKernelGGL(k_env_after_opp, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, list);
+  HIP_TRY(h, hipGetLastError());
+  return MONSOON_OK;
+}
+
+static size_t env_opp_bytes(size_t cap) { return 16 * cap + 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE); }
+
+extern "C" {
+
+int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_individuals, const int32_t* rows, int32_t n) {
+  if (!h) return MONSOON_ERR_ARG;
+  const bool live = h->env_on && h->env.opponent == 2;   // a captured step may point to the table and the rows
+  const char* bad = nullptr;
+  if (!weights || n_individuals <= 0 || n <= 0 || n > h->cfg.max_games) bad = "bad argument (weights, n_individuals >= 1, 1 <= n <= max_games)";
+  else if (live && n != h->env_n) bad = "n differs from the loaded env's";
+  else if (live && n_individuals > h->opp_w_cap) bad = "more weight rows than when the env was reset (the table is not reallocated under a loaded env)";
+  for (int i = 0; !bad && rows && i < n; i++)
+    if (rows[i] < 0 || rows[i] >= n_individuals) bad = "a row outside [0, n_individuals)";
+  if (bad) {
+    h->err = std::string("monsoon_env_set_opponents: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  HIP_TRY(h, bind_device(h));
+  const size_t cap = (size_t)h->cfg.max_games;
+  if (!h->d_opp) HIP_TRY(h, hipMalloc(&h->d_opp, env_opp_bytes(cap)));
+  if (n_individuals > h->opp_w_cap) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (h->d_opp_w) HIP_TRY(h, hipFree(h->d_opp_w));
+    h->d_opp_w = nullptr;
+    h->opp_w_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_opp_w, (size_t)n_individuals * 80));
+    h->opp_w_cap = n_individuals;
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->d_opp_w, weights, (size_t)n_individuals * 80, hipMemcpyHostToDevice, h->stream));
+  if (rows) HIP_TRY(h, hipMemcpyAsync(h->d_opp, rows, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  else HIP_TRY(h, hipMemsetAsync(h->d_opp, 0, (size_t)n * 4, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->opp_n = n;
+  return MONSOON_OK;
+}
+
 int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon_env_views* views, int32_t n, const uint32_t* seed0,
                       const uint8_t* decks, const uint8_t* factions) {
   if (!h) return MONSOON_ERR_ARG;
   const char* bad = nullptr;
   if (!cfg || !views || !seed0 || n <= 0 || n > h->cfg.max_games) bad = "bad argument (1 <= n <= max_games)";
   else if (!views->done) bad = "views.done is required";
-  else if (cfg->opponent != 0 && cfg->opponent != 1) bad = "opponent must be 0 (none) or 1 (scripted bot)";
+  else if (cfg->opponent < 0 || cfg->opponent > 2) bad = "opponent must be 0 (none), 1 (scripted bot) or 2 (heuristic agent)";
   else if (cfg->agent_side != 0 && cfg->agent_side != 1) bad = "agent_side must be 0 or 1";
   else if (cfg->max_steps < 0 || cfg->max_steps > 65535) bad = "0 <= max_steps <= 65535";
   else if (cfg->pool_n != 0 && (cfg->pool_n < 12 || cfg->pool_n > 128)) bad = "pool_n must be 0 or 12..128";
   else if (!cfg->pool_n && !decks) bad = "decks are required without a pool";
   else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
   else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
+  else if (cfg->opponent == 2 && h->opp_n && h->opp_n != n) bad = "n differs from the n of monsoon_env_set_opponents";
   if (bad) {
     h->err = std::string("monsoon_env_reset: ") + bad;
     return MONSOON_ERR_ARG;
+  }
+  if (cfg->opponent == 2 && !h->opp_n) {
+    h->err = "monsoon_env_reset: opponent 2 needs monsoon_env_set_opponents first";
+    return MONSOON_ERR_STATE;
   }
   int rc = cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)") : check_decks(h, decks, (size_t)n * 24, "monsoon_env_reset");
   if (rc) return rc;
@@ -1771,6 +1840,35 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   v.agent_side = cfg->agent_side;
   v.max_steps = cfg->max_steps;
   v.stride = cfg->seed_stride ? cfg->seed_stride : (uint32_t)n;
+  v.cap = (int)cap;
+  v.opp_rows = nullptr;
+  v.opp_list = nullptr;
+  v.opp_count = nullptr;
+  v.opp_pop = nullptr;
+  v.opp_lookahead = nullptr;
+  if (cfg->opponent == 2) {
+    v.opp_rows = (const int32_t*)h->d_opp;
+    v.opp_list = (int32_t*)(h->d_opp + 4 * cap);
+    v.opp_lookahead = (uint32_t*)(h->d_opp + 12 * cap);
+    v.opp_count = (int32_t*)(h->d_opp + 16 * cap);
+    v.opp_pop = (int*)(h->d_opp + 16 * cap + 4 * 2 * ENV_COUNT_STRIDE);
+    const EnvOppOps* o = monsoon_env_opp_ops();
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
+    HIP_TRY(h, o->occupancy(&per_cu, o->lds_bytes));
+    // persistent: the resident wavefronts, but no more than the slots, and one at least for each of the POP_PARTS ranges
+    h->opp_grid = std::max(POP_PARTS, std::min(per_cu > 0 ? per_cu * prop.multiProcessorCount : 4096, n));
+    if ((size_t)h->opp_grid * o->lanes > h->ovf_lanes) {   // work-stack overflow blocks for every workgroup of k_env_opp
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      HIP_TRY(h, hipFree(h->b.wk_ovf));
+      h->b.wk_ovf = nullptr;
+      h->ovf_lanes = (size_t)h->opp_grid * o->lanes;
+      HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
+    }
+    HIP_TRY(h, hipMemsetAsync(v.opp_count, 0, 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE), h->stream));
+    HIP_TRY(h, hipMemsetAsync(v.opp_lookahead, 0, (size_t)n * 4, h->stream));
+  }
   HIP_TRY(h, hipMemcpyAsync((void*)v.seed0, seed0, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   if (decks) HIP_TRY(h, hipMemcpyAsync(v.decks, decks, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
   if (factions)
@@ -1786,6 +1884,10 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, v, n);
   hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, v, n, 1);
   HIP_TRY(h, hipGetLastError());
+  if (cfg->opponent == 2) {   // the opening turns of the episodes the opponent starts (list 1)
+    rc = launch_env_opp(h, n, 1);
+    if (rc) return rc;
+  }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->n = n;
   h->env_n = n;
@@ -1793,7 +1895,9 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   return MONSOON_OK;
 }
 
-// Enqueues the three env kernels on the handle's stream and returns: no allocation, copy or synchronisation (graph-capturable).
+// Enqueues the env kernels on the handle's stream and returns: no allocation, copy or synchronisation (graph-capturable).
+// Opponents 0 and 1: three launches.  Opponent 2: seven (env.inc), the opponent's kernel after the agent's step and
+// again after the re-initialisation.
 int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
   if (!h) return MONSOON_ERR_ARG;
   if (!h->env_on) {
@@ -1807,9 +1911,14 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
   HIP_TRY(h, bind_device(h));
   const int n = h->env_n;
   hipLaunchKernelGGL(k_env_step, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, actions_dev);
+  if (h->env.opponent == 2) {
+    int rc = launch_env_opp(h, n, 0);
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, h->env, n);
   hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, 0);
   HIP_TRY(h, hipGetLastError());
+  if (h->env.opponent == 2) return launch_env_opp(h, n, 1);
   return MONSOON_OK;
 }
 

@@ -119,6 +119,8 @@ enum : int {
   FAULT_CAP_INST = 26,      // card-instance strength outside 0..255
   FAULT_BOT_BOUND = 27,     // vector env: the scripted bot still to play after 64 actions in one call (env.inc; the
                             // reference's bot can repeat a USE that does nothing for ever)
+  FAULT_OPP_BOUND = 28,     // vector env: the heuristic opponent still to play after 64 decisions in one call (kernels.h
+                            // play_game<U, true>; a no-op USE that wins the argmax once wins it for ever)
 };
 
 // ---- static card table -----------------------------------------------------------------

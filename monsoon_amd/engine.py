@@ -201,6 +201,13 @@ class BatchEngine:
                                             _ptr(factions)), "monsoon_env_reset")
         self.n = n
 
+    def env_set_opponents(self, weights, rows, n):
+        """monsoon_env_set_opponents: host weights[k][10] float64, rows[n] int32 or None (row 0 for every slot).  Synchronises."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self._ck(self.lib.monsoon_env_set_opponents(self.h, _ptr(weights), len(weights), _ptr(rows), int(n)), "monsoon_env_set_opponents")
+
     def env_step_dev(self, actions_ptr):
         """monsoon_env_step_dev on n bytes of device memory at actions_ptr (asynchronous on the handle's stream)."""
         self._ck(self.lib.monsoon_env_step_dev(self.h, ctypes.c_void_p(actions_ptr)), "monsoon_env_step_dev")

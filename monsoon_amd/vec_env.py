@@ -3,7 +3,8 @@
 Seam G batched for a learner that lives on the GPU: n slots of games/abstract_game.py's interface (step, to_play,
 legal_actions, reset, expert_agent as the opponent), each an endless sequence of episodes that restart in place.  One
 `step` is three kernel launches on the handle's stream -- legality check, step, the scripted bot's turn, end of episode,
-re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.
+re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.  The
+opponent can also be the reference's HeuristicAgent with GA weights ("heuristic": seven launches per step).
 torch is used for device memory and stream ordering only; there is no CPU fallback.
 """
 import ctypes
@@ -13,7 +14,7 @@ import numpy as np
 from ._lib import EnvConfig, EnvViews, MonsoonError
 from .engine import BatchEngine
 
-OPPONENTS = {"none": 0, "expert": 1}
+OPPONENTS = {"none": 0, "expert": 1, "heuristic": 2}
 
 # name -> (trailing shape, torch dtype name); the order of monsoon_env_views
 _VIEWS = (("obs", (27, 5, 4), "int32"), ("legal", (156,), "bool"), ("obs_raises", (), "bool"), ("to_play", (), "uint8"),
@@ -34,6 +35,7 @@ class VecEnv:
         self.extended = extended
         self.n = 0
         self.views = None
+        self._heuristic = False   # an opponent-2 env is loaded
 
     def close(self):
         if self.engine is not None:
@@ -60,11 +62,14 @@ class VecEnv:
             views[name] = torch.zeros((n,) + shape, dtype=getattr(torch, dt), device=dev)
         return views
 
-    def reset(self, seed0, decks=None, factions=None, opponent="none", agent_side=0, max_steps=0, pool=None, seed_stride=0):
+    def reset(self, seed0, decks=None, factions=None, opponent="none", agent_side=0, max_steps=0, pool=None, seed_stride=0,
+              opponent_weights=None, opponent_rows=None):
         """Episode 0 of every slot: slot i plays seed0[i] with decks[i] ([n][2][12] or one [2][12] pair for all) and
         factions[i]; episode k then starts from seed0[i] + k * seed_stride (0 = n).  pool (12..128 card indices) draws
         fresh decks for every episode instead (decks must be None).  opponent "expert" puts the reference's scripted bot on
-        the side that agent_side does not play.  max_steps > 0 truncates episodes.  Returns the view tensors (a dict)."""
+        the side that agent_side does not play; "heuristic" puts the reference's HeuristicAgent there, slot i playing row
+        opponent_rows[i] (None = row 0) of opponent_weights ([10] or [k][10] float64, e.g. WeightVector.weights or a
+        Population's individuals).  max_steps > 0 truncates episodes.  Returns the view tensors (a dict)."""
         import torch
         if opponent not in OPPONENTS:
             raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
@@ -72,6 +77,15 @@ class VecEnv:
         n = len(seed0)
         if pool is None and decks is None:
             raise ValueError("decks are required without a pool")
+        opp = None
+        if opponent == "heuristic":
+            if opponent_weights is None:
+                raise ValueError('opponent="heuristic" needs opponent_weights ([10] or [k][10])')
+            opp = self._opponents(opponent_weights, opponent_rows, n)
+            if self._heuristic and self.n != n:
+                raise ValueError(f"a VecEnv with a heuristic opponent keeps its {self.n} slots: open another VecEnv for {n}")
+        elif opponent_weights is not None or opponent_rows is not None:
+            raise ValueError('opponent_weights / opponent_rows need opponent="heuristic"')
         cfg = EnvConfig()
         cfg.opponent = OPPONENTS[opponent]
         cfg.agent_side = int(agent_side)
@@ -91,10 +105,43 @@ class VecEnv:
         # the views may still be read by work queued on torch's stream
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         try:
+            if opp is not None:
+                self.engine.env_set_opponents(opp[0], opp[1], n)
+            self._heuristic = False
             self.engine.env_reset(cfg, views, seed0, decks, factions)
+            self._heuristic = opp is not None
         finally:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return self.views
+
+    @staticmethod
+    def _opponents(weights, rows, n):
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 1:
+            w = w[None]
+        if w.ndim != 2 or w.shape[1] != 10 or len(w) == 0:
+            raise ValueError(f"opponent weights must be [10] or [k][10], got {np.shape(weights)}")
+        if rows is not None:
+            rows = np.asarray(rows)
+            if rows.shape != (n,) or not np.issubdtype(rows.dtype, np.integer):
+                raise ValueError(f"opponent rows must be {n} integers, got {rows.shape} {rows.dtype}")
+            if n and (rows.min() < 0 or rows.max() >= len(w)):
+                raise ValueError(f"opponent rows must lie in [0, {len(w)})")
+            rows = rows.astype(np.int32)
+        return np.ascontiguousarray(w), rows
+
+    def set_opponents(self, weights, rows=None):
+        """A league update between steps: the heuristic opponents' weights ([10] or [k][10]; k at most the k given to
+        reset) and each slot's row (None = row 0).  They apply from the next step; a captured step graph stays valid."""
+        import torch
+        if not self._heuristic:
+            raise MonsoonError('VecEnv.set_opponents needs reset(opponent="heuristic", ...) first')
+        w, r = self._opponents(weights, rows, self.n)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        try:
+            self.engine.env_set_opponents(w, r, self.n)
+        finally:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
     def step(self, actions):
         """Advance every slot: actions is a uint8 CUDA tensor [n] (255 = leave the slot alone, 155 = PASS, any other

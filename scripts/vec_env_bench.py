@@ -2,9 +2,10 @@
 """Throughput of the device-resident vector env (monsoon_amd/vec_env.py) against the host-API loop on the same seeds.
 
 Workload: --slots games (default 65 536), N12M decks or a per-episode pool (every card of the standard record but
-up01/up02/up03), opponent none or the scripted bot, a random policy sampled on the device from the legal mask with
-torch ops.  Agent env-steps/s and bot steps/s are reported separately (the env's own counters, monsoon_debug_counters
-words 6 / 7).  The host loop is what the C ABI offered before the env: monsoon_legal_mask + monsoon_step +
+up01/up02/up03), opponent none, the scripted bot or the heuristic agent (8 weight vectors, slot i playing row i % 8), a
+random policy sampled on the device from the legal mask with torch ops.  Agent env-steps/s and opponent steps/s are
+reported separately (the env's own counters, monsoon_debug_counters words 6 / 7); for the heuristic opponent, whose steps
+are its decisions, also its look-ahead transitions/s (word 16).  The host loop is not run for the heuristic opponent.  The host loop is what the C ABI offered before the env: monsoon_legal_mask + monsoon_step +
 monsoon_observe_dev every step (the policy samples on the device from the uploaded mask), the bot's turn as
 monsoon_status + monsoon_expert_action + monsoon_step rounds, and the whole batch re-reset once every game is done.
 
@@ -29,10 +30,13 @@ from monsoon_amd.engine import BatchEngine  # noqa: E402
 from monsoon_amd.vec_env import VecEnv  # noqa: E402
 
 
+OPPONENTS = ("none", "expert", "heuristic")
+
+
 def counters(eng):
     c = np.zeros(192, dtype=np.uint64)
     eng._ck(eng.lib.monsoon_debug_counters(eng.h, c.ctypes.data_as(ctypes.c_void_p)), "monsoon_debug_counters")
-    return int(c[6]), int(c[7])
+    return int(c[6]), int(c[7]), int(c[16])
 
 
 def sample(torch, legal, gen):
@@ -42,13 +46,14 @@ def sample(torch, legal, gen):
 
 
 def windows(step_fn, count_fn, sync, args, chunk):
-    """Median over timed windows of (agent steps/s, bot steps/s, steps per window, window seconds)."""
+    """Median over timed windows of (agent steps/s, bot steps/s, steps per window, window seconds, look-ahead
+    transitions/s)."""
     for _ in range(args.warmup):
         step_fn()
     sync()
     res = []
     for _ in range(args.windows):
-        a0, b0 = count_fn()
+        a0, b0, l0 = count_fn()
         t0 = time.perf_counter()
         calls = 0
         while True:
@@ -59,16 +64,19 @@ def windows(step_fn, count_fn, sync, args, chunk):
                 if time.perf_counter() - t0 >= args.window_s:
                     break
         dt = time.perf_counter() - t0
-        a1, b1 = count_fn()
-        res.append(((a1 - a0) / dt, (b1 - b0) / dt, calls, dt))
+        a1, b1, l1 = count_fn()
+        res.append(((a1 - a0) / dt, (b1 - b0) / dt, calls, dt, (l1 - l0) / dt))
     res.sort(key=lambda r: r[0])
     return res[len(res) // 2], res
 
 
 def bench_env(torch, args, seed0, decks, pool, opponent):
     env = VecEnv(args.slots)
-    views = env.reset(seed0, None if pool is not None else decks, opponent=("none", "expert")[opponent], pool=pool,
-                      max_steps=args.max_steps)
+    kw = {}
+    if opponent == 2:
+        kw = dict(opponent_weights=np.random.RandomState(42).uniform(0, 1, (8, 10)), opponent_rows=np.arange(args.slots) % 8)
+    views = env.reset(seed0, None if pool is not None else decks, opponent=OPPONENTS[opponent], pool=pool,
+                      max_steps=args.max_steps, **kw)
     gen = torch.Generator(device="cuda")
     gen.manual_seed(7)
     state = {"v": views}
@@ -127,7 +135,7 @@ def bench_host(torch, args, seed0, decks, pool, opponent):
             bot_turn()
         eng._ck(eng.lib.monsoon_observe_dev(eng.h, ctypes.c_void_p(obs.data_ptr()), ctypes.c_void_p(raises.data_ptr())), "observe_dev")
 
-    med, all_ = windows(step, lambda: (st["agent"], st["bot"]), eng.sync, args, 1)
+    med, all_ = windows(step, lambda: (st["agent"], st["bot"], 0), eng.sync, args, 1)
     eng.close()
     return med, all_, st["episode"]
 
@@ -149,16 +157,19 @@ def main():
     decks = np.broadcast_to(deck, (n, 2, 12)).copy()
     pool = np.array(sorted(CARD_INDEX[c] for c in supported_pool()), dtype=np.uint8)
     for dname, p in (("N12M", None), ("pool", pool)):
-        for opponent in (0, 1):
-            name = f"{dname}/{('none', 'expert')[opponent]}"
+        for opponent in (0, 1, 2):
+            name = f"{dname}/{OPPONENTS[opponent]}"
             if args.only and name not in args.only.split(","):
                 continue
-            paths = [("env", bench_env)] + ([] if args.no_host else [("host_loop", bench_host)])
+            paths = [("env", bench_env)] + ([] if args.no_host or opponent == 2 else [("host_loop", bench_host)])
             for path, fn in paths:
                 med, all_, eps = fn(torch, args, seed0, decks, p, opponent)
-                print(json.dumps(dict(config=name, path=path, slots=n, agent_steps_per_s=round(med[0]), bot_steps_per_s=round(med[1]),
-                                      calls_per_window=med[2], window_s=round(med[3], 3),
-                                      windows_agent_steps_per_s=[round(r[0]) for r in all_], episodes=eps)), flush=True)
+                row = dict(config=name, path=path, slots=n, agent_steps_per_s=round(med[0]), bot_steps_per_s=round(med[1]),
+                           calls_per_window=med[2], window_s=round(med[3], 3),
+                           windows_agent_steps_per_s=[round(r[0]) for r in all_], episodes=eps)
+                if opponent == 2:
+                    row.update(opponent_decisions_per_s=round(med[1]), lookahead_transitions_per_s=round(med[4]))
+                print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
