@@ -7,6 +7,7 @@ actions; float64 features and scores compared by bit pattern)."""
 import numpy as np
 import pytest
 
+import kernel_variants
 import oracle_lib
 from monsoon_amd.cards import deck_indices
 
@@ -39,14 +40,30 @@ def test_initial_states_vs_reference(engines, gold):
         assert eng.export(j) == g["canon"][k][:g["length"][k]].tobytes(), k
 
 
+def _fnv1a64_rows(rows):
+    """oracle_lib.fnv1a64 of the bytes of every row of a 2-D uint8 array, vectorised over the rows."""
+    h = np.full(len(rows), 0xCBF29CE484222325, dtype=np.uint64)
+    prime = np.uint64(0x100000001B3)
+    for j in range(rows.shape[1]):
+        h = (h ^ rows[:, j]) * prime
+    return h
+
+
 @pytest.mark.parametrize("name", ["trace_random_N12V.npz", "trace_random_N12M.npz", "trace_random_IRONCLAD.npz",
-                                  "trace_random_S12.npz", "trace_pool.npz", "trace_pool_ext.npz", "trace_pool_up.npz"])
+                                  "trace_random_S12.npz", "trace_pool.npz", "trace_pool_ext.npz", "trace_pool_up.npz",
+                                  "trace_live_pool.npz", "trace_live_pool_ext.npz", "trace_live_b005.npz",
+                                  "trace_live_expert.npz"])
 def test_random_policy_traces_vs_reference(engines, gold, name):
     """Replays the reference's seeded random-policy games through monsoon_step in lockstep
-    (trace_pool_ext: all 109 observable cards on the extended-record build)."""
+    (trace_pool_ext, trace_live_pool_ext and trace_live_b005: all 109 observable cards on the extended-record build;
+    trace_live_expert: the reference's scripted bot on both sides, through monsoon_expert_action).  The device's
+    observation is compared with the reference's own (its fnv1a64 hash in the fixture) and with the oracle's, and its
+    features with the reference's rows where the fixture has them.  As in test_reference_live, a capacity limit of the
+    extended record (fault 16 / 22 / 23) may end a game early, and a recorded expert action 255 ends it."""
     g = gold(name)
     n = len(g["seeds"])
-    ext = name.endswith("_ext.npz")
+    ext = name.endswith("_ext.npz") or "b005" in name
+    expert = "expert" in name
     eng = engines(256, 0, ext)
     eng.reset(g["seeds"], np.stack([g["deck0"], g["deck1"]], axis=1))
     assert np.array_equal(eng.state_hash(), g["init_hash"])
@@ -57,29 +74,52 @@ def test_random_policy_traces_vs_reference(engines, gold, name):
     lens = (off[1:] - off[:-1]).copy()
     # feature rows exist for the steps the reference completed: a game whose last step raised has one row less
     foff = np.concatenate([[0], np.cumsum(lens - g["fault"].astype(np.int64))]) if "feat" in g.files else None
+    ended = np.zeros(n, dtype=bool)
+    n_obs = n_feat = 0
     for t in range(int(lens.max())):
-        live = np.nonzero(lens > t)[0]
+        live = np.nonzero((lens > t) & ~ended)[0]
         masks = eng.legal_mask()
+        bot = eng.expert_action()[0] if expert else None   # advances every game's stream, as the reference's bot does
         acts = np.full(n, 255, dtype=np.uint8)
         for k in live:
             assert np.array_equal(masks[k], g["legal"][off[k] + t]), (k, t)
             acts[k] = g["action"][off[k] + t]
+            if expert:
+                ob, fe = orc.expert_action(k)
+                if acts[k] == 255:   # the reference's bot raised: the game ends here
+                    assert fe != 0, (k, t)
+                    ended[k] = True
+                    continue
+                assert fe == 0 and ob == acts[k] == bot[k], (k, t)
         reward, done, fault = eng.step(acts)
         hashes = eng.state_hash()
         obs, raises = eng.observe()
+        obs_hash = _fnv1a64_rows(obs.reshape(n, -1).view(np.uint8))
         feat = eng.features() if "feat" in g.files else None
         for k in live:
+            if ended[k]:
+                continue
             i = off[k] + t
             fo, _, _ = orc.step(k, int(acts[k]))
             if g["fault"][k] and t == lens[k] - 1:   # the reference raised on this step
                 assert fault[k] != 0 or raises[k], (k, t)
                 continue
+            if ext and name.startswith("trace_live_") and fault[k] in (16, 22, 23):   # a capacity limit of the record, both sides
+                assert fo == fault[k], (k, t)
+                ended[k] = True
+                continue
             assert fault[k] == 0 and fo == 0, (k, t, fault[k])
             assert hashes[k] == g["hash"][i], (k, t)
             assert (reward[k], done[k]) == (g["reward"][i], g["done"][i]), (k, t)
+            assert not raises[k] and obs_hash[k] == g["obs"][i], (k, t)   # the reference's observation itself
             assert np.array_equal(obs[k], orc.observe(k)), (k, t)
+            n_obs += 1
             if feat is not None:   # the reference's StateFeatures at EVERY step (the fixture holds no rows for faulted steps)
                 assert np.array_equal(feat[k].view(np.uint64), g["feat"][foff[k] + t].view(np.uint64)), (k, t)
+                n_feat += 1
+    print(f"{name}: {n_obs} observations and {n_feat} feature rows equal the reference's")
+    if "feat" in g.files:
+        assert n_feat >= len(g["feat"]) - 20   # a few rows may be lost to a tolerated capacity limit
 
 
 def test_expert_bot_vs_reference(engines, gold):
@@ -110,22 +150,31 @@ def test_expert_bot_vs_reference(engines, gold):
             assert sf[k] == 0 and hashes[k] == g["hash"][i], (k, t)
 
 
-@pytest.mark.parametrize("fixture", ["trace_heuristic_N12M.npz", "trace_heuristic_S12.npz", "trace_heuristic_IRONCLAD.npz",
-                                     "trace_heuristic_pool.npz", "trace_heuristic_pool_ext.npz", "trace_heuristic_c5_big.npz"])
+HEURISTIC_FIXTURES = ["trace_heuristic_N12M.npz", "trace_heuristic_S12.npz", "trace_heuristic_IRONCLAD.npz",
+                      "trace_heuristic_pool.npz", "trace_heuristic_pool_ext.npz", "trace_heuristic_c5_big.npz"]
+
+
+def _fixture_build(fixture):
+    # "_big": games of the C5 family whose nested b005 memories outgrow the extended record, on the large record
+    return 2 if fixture.endswith("_big.npz") else fixture.endswith("_ext.npz")
+
+
+@pytest.mark.parametrize("fixture", HEURISTIC_FIXTURES)
 def test_heuristic_selfplay_vs_reference(engines, gold, fixture):
     """monsoon_decide against the reference's HeuristicAgent self-play (corrected loop): action,
     complete score vector, best score and committed state at every decision of the fixture's games (N12M mirror,
     the Swarm deck, the reference's default Ironclad-vs-Swarm pair, per-game random decks); a game that the reference
     ends with an exception (hash 0) faults here at the same decision."""
-    g = gold(fixture)
+    _heuristic_selfplay(engines(32, extended=_fixture_build(fixture)), gold(fixture), fixture)
+
+
+def _heuristic_selfplay(eng, g, fixture):
     n = len(g["seeds"])
     if "decks" in g.files:
         decks = g["decks"]                       # a pair of 12-card decks per game
     else:
         decks = np.stack([g["deck"], g["deck1"] if "deck1" in g.files else g["deck"]])
-    # "_big": games of the C5 family whose nested b005 memories outgrow the extended record, on the large record
-    ext = 2 if fixture.endswith("_big.npz") else fixture.endswith("_ext.npz")
-    eng = engines(32, extended=ext)
+    eng.reset_stats()
     eng.reset(g["seeds"], decks)
     off = g["offsets"]
     for t in range(int(g["max_turns"])):
@@ -153,9 +202,11 @@ def test_heuristic_selfplay_vs_reference(engines, gold, fixture):
 def test_heuristic_two_weight_vectors_vs_reference(engines, gold):
     """Per-side weight vectors [n][2][10]: the kernel uses the mover's vector as the reference's
     agents[adapter.get_current_player()] does -- action, score vector, best score, committed state of every decision."""
-    g = gold("trace_heuristic_N12M_2w.npz")
+    _heuristic_two_weight_vectors(engines(16), gold("trace_heuristic_N12M_2w.npz"))
+
+
+def _heuristic_two_weight_vectors(eng, g):
     n = len(g["seeds"])
-    eng = engines(16)
     eng.reset(g["seeds"], np.stack([g["deck"], g["deck1"]]))
     w = np.broadcast_to(np.stack([g["w0"], g["w1"]]), (n, 2, 10)).copy()
     off = g["offsets"]
@@ -170,6 +221,33 @@ def test_heuristic_two_weight_vectors_vs_reference(engines, gold):
             legal = ~np.isnan(scores[k])
             assert oracle_lib.fnv1a64(scores[k][legal].tobytes()) == int(g["shash"][i]), (k, t)
             assert best[k] == g["best"][i] and hashes[k] == g["hash"][i], (k, t)
+
+
+VARIANTS, VARIANT_IDS = kernel_variants.matrix()
+
+
+@pytest.mark.parametrize("ext,u,w", VARIANTS, ids=VARIANT_IDS)
+def test_heuristic_fixtures_on_every_kernel_variant(gold, monkeypatch, ext, u, w):
+    """The two tests above on every hot-kernel instantiation of variants.def (each a translation unit of its own, with its
+    own register allocation and, for U = 4 / 16 on the extended and large records, its own PlayLds layout), selected with
+    MONSOON_LANES / MONSOON_WPE: every reference heuristic fixture of the variant's build."""
+    from monsoon_amd.engine import BatchEngine
+    kernel_variants.select(monkeypatch, u, w)
+    eng = BatchEngine(32, extended=ext)
+    try:
+        assert eng.variant() == (u, w)
+        ran = []
+        for fixture in HEURISTIC_FIXTURES:
+            if _fixture_build(fixture) == ext:
+                _heuristic_selfplay(eng, gold(fixture), fixture)
+                ran.append(fixture)
+        if ext is False:
+            _heuristic_two_weight_vectors(eng, gold("trace_heuristic_N12M_2w.npz"))
+            ran.append("trace_heuristic_N12M_2w.npz")
+        assert len(ran) == {False: 5, True: 1, 2: 1}[ext]
+        print(f"variant {kernel_variants.BUILD_NAMES[ext]} ({u}, {w}): {', '.join(ran)}")
+    finally:
+        eng.close()
 
 
 @pytest.mark.parametrize("lanes", [4, 8, 16, 32, 64])
