@@ -31,6 +31,7 @@
 #include "../../include/monsoon.h"
 #include "rules.h"
 #include "canon.h"
+#include "coop_features.h"
 
 namespace msbk {
 using namespace msb;
@@ -253,7 +254,12 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   typedef PlayLds<U> L;
   typedef Engine<Col0Mem<U, L::PRIV>> ParEngine;
   typedef Engine<LaneMem<U, L::PRIV, L::SKB, SKW>> CandEngine;
+  typedef Engine<SubColMem<U, L::PRIV>> SubEngine;   // candidate (lane % U)'s record, read only: the wave-cooperative features
   constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
+  // Features by the whole wave (coop_features.h) where a candidate has sub-lanes to spare, on the standard record.  The
+  // extended records keep the serial form: with 2 x 12 VGPRs of record per lane next to the phase's temporaries the
+  // register allocator spilled them (k_play<8,2>: 0 -> 312 spilled VGPRs, scratch 3 168 -> 3 408 B), see DESIGN.md section 4.
+  constexpr bool COOP = U < 64 && GPL == 1;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
   if (meta.result != -2) {
@@ -325,8 +331,14 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if (lane < 10) wf[lane] = wt[lane];
       // The "before" features of this decision are the "after" features the previous decision computed for the
       // successor it committed (same state, same mover); only the first decision of a call computes them.
-      if (!before_raises && !have_before) {
-        if (lane == 0) pe.features(wf + 10);
+      if (!before_raises && !have_before) {   // (uniform)
+        if constexpr (!COOP) {
+          if (lane == 0) pe.features(wf + 10);
+        } else {
+          int sl = lane;   // (opaque: what derives from it is computed here, not hoisted out of the game loop and spilled)
+          asm volatile("" : "+v"(sl));
+          coop_features<U>(pe, sl, true, wf + 10);   // every lane reads column 0: all U columns compute the same ten values
+        }
       }
     }
     __syncthreads();
@@ -382,8 +394,11 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         raises = f == 0 && ce.observation_raises();
       }
       PROF_MARK(4);   // step
-      if (active) {
-        if (f == 0 && !before_raises && !raises) {
+      // The candidates that get features and a score; all of them run the same code now, so the whole wave works on it:
+      // lane l is sub-lane l / U of candidate l % U (coop_features.h).  !COOP: the serial form.
+      const bool scored = active && f == 0 && !before_raises && !raises;
+      if constexpr (!COOP) {
+        if (scored) {
           // the ten values go to LDS for the winner's sake (argmax below) and feed the score from registers
           double fa[10];
 #if defined(MSB_STUDY_FEATURES)
@@ -399,6 +414,32 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           s = CandEngine::action_score_lds(wf, fa);
           my_feat = 1;
         }
+      } else {
+        const unsigned long long part = __ballot(scored);   // (candidates sit on lanes 0 .. U-1)
+        if (part) {
+          int sl = lane;   // (opaque: what derives from it is computed here, not hoisted out of the game loop and spilled)
+          asm volatile("" : "+v"(sl));
+          const int col = sl % U;
+          const bool on = (part >> col) & 1;
+          SubEngine se;
+          se.m.c16 = col * 16;
+          MSB_AS_LDS double* cfc = (MSB_AS_LDS double*)(uintptr_t)(L::CF + col * 80);   // the features of this lane's candidate
+          // the ten values go to LDS (cf), for the score and for the winner's sake (argmax below)
+#if defined(MSB_STUDY_FEATURES)
+          {   // study build: the candidates' features and their scores computed once more
+            coop_features<U>(se, sl, on, cfc);
+            double s2 = coop_score(wf, cfc);
+            asm volatile("" : : "v"(s2) : "memory");
+          }
+#endif
+          coop_features<U>(se, sl, on, cfc);
+          if (scored) {
+            s = coop_score(wf, cfc);
+            my_feat = 1;
+          }
+        }
+      }
+      if (active) {
         if (!ENV && write_scores) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;
         my_fault = f ? f : (raises ? FAULT_INT_CARD : 0);
       }

@@ -428,6 +428,29 @@ struct Col0Mem {
   MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }
   MSB_HD MSB_INL static void ovf_st(int, uint32_t) {}
 };
+// One column of a lane-interleaved image, chosen per lane by the caller (c16 = column * 16), READ ONLY: how the sub-lanes of a
+// candidate (lanes c, c + LANES, c + 2*LANES, ... of the wave) all see candidate c's record in the wave-cooperative features
+// (coop_features.h).  It has loads only: an Engine over it can inspect a record and nothing else.  Unlike its stateless
+// neighbours it carries the column offset: a value the caller derives where it is used, so that the address arithmetic is not
+// hoisted out of the kernel's game loop and kept (spilled) for its whole life.
+template <int LANES, int BASE>
+struct SubColMem {
+  int c16;
+  MSB_HD MSB_INL MSB_AS_LDS const uint8_t* b(int o) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)(BASE + (o >> 4) * (LANES * 16) + (o & 15) + c16); }
+  MSB_HD MSB_INL MSB_AS_LDS const uint8_t* gb(int g, int k) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)(BASE + g * (LANES * 16) + k + c16); }
+  MSB_HD MSB_INL int ld8(int o) const { return *b(o); }
+  MSB_HD MSB_INL int ld16(int o) const { return *(MSB_AS_LDS const int16_t*)b(o); }
+  MSB_HD MSB_INL uint32_t ld32(int o) const { return *(MSB_AS_LDS const uint32_t*)b(o); }
+  MSB_HD MSB_INL double ldf(int o) const { return *(MSB_AS_LDS const double*)b(o); }
+  MSB_HD MSB_INL uint64_t ld64(int o) const { return *(MSB_AS_LDS const uint64_t*)b(o); }
+  MSB_HD MSB_INL msb_u32x4 ld128(int o) const { return *(MSB_AS_LDS const msb_u32x4*)b(o); }
+  MSB_HD MSB_INL int ld8g(int g, int k) const { return *gb(g, k); }
+  MSB_HD MSB_INL int ld16g(int g, int k) const { return *(MSB_AS_LDS const int16_t*)gb(g, k); }
+  MSB_HD MSB_INL msb_u32x4 ld128g(int g) const { return *(MSB_AS_LDS const msb_u32x4*)gb(g, 0); }
+  MSB_HD MSB_INL uint32_t ld32g(int g, int k) const { return *(MSB_AS_LDS const uint32_t*)gb(g, k); }
+  MSB_HD MSB_INL double ldfg(int g, int k) const { return *(MSB_AS_LDS const double*)gb(g, k); }
+  MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
+};
 #endif
 
 template <class A, class B>
