@@ -167,6 +167,42 @@ int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, 
  * libmonsoon_hip_big.so, as monsoon_amd/fitness.py does -- and their rows of the result replaced. */
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches);
 
+/* The evolved agent against the reference's scripted bot (play_vs_expert.py: HeuristicAgent.select_action on one side,
+ * Stormbound.expert_action on the other; evo/EVOLUTIONARY_PLAN.md's yardstick).  monsoon_rollout's arguments and rollout
+ * contract, with one more kind of player: p1, p2 or both of a match may be MONSOON_PLAYER_EXPERT.
+ *
+ *   steps = 0
+ *   while not have_winner() and steps < max_turns:
+ *       side = to_play()
+ *       if side is the bot:  a = expert_action()        -- draws from the game's own stream, like the reference
+ *       else:                a = HeuristicAgent(weights[row]).select_action()   -- exactly monsoon_decide's decision
+ *       state = step(a); steps += 1
+ *
+ *  - The result follows the one rule of monsoon_rollout (FIRST wins iff SECOND's base < 0 <= FIRST's base, ...), not
+ *    play_vs_expert.py's "<= 0" test: have_winner is strict.
+ *  - An expert_action that raises (random.choice([]) inside the bot) ends the game as a draw with that fault code and
+ *    without a step, as in the vector env.  The reference's fallback there -- Python's unseeded random.choice over the
+ *    legal list -- is not reproducible and is not restated.
+ *  - A committed step that faults, or whose observation raises (the reference's step returns get_observation()), ends
+ *    the game as a draw with that code, the bot's step or the agent's.
+ *  - There is no guard like FAULT_BOT_BOUND / FAULT_OPP_BOUND: every committed step counts towards max_turns, so a bot
+ *    that repeats a USE which does nothing runs the game into max_turns, as it does in the reference's loop.
+ *  - out_steps counts all committed steps; monsoon_stats.decisions only the heuristic agent's decisions and
+ *    lookahead_steps only its look-aheads (a bot step is one committed transition and no look-ahead).
+ *  - out_counts[n_individuals][3] is accumulated into the row of the match's INDIVIDUAL: p1 if it is one (a win = FIRST
+ *    won), else p2 (a win = SECOND won); a match of the bot against itself touches no row.  out_results stays
+ *    FIRST / SECOND (-1 draw, 0 FIRST, 1 SECOND).
+ * A match without a bot is played exactly as monsoon_rollout plays it, so a schedule may mix both kinds.  The kernel is
+ * the build's default variant, whatever lanes_per_game the handle was created with.  monsoon_rollout_faults,
+ * monsoon_get_stats, monsoon_state_hash (final records of the last batch) and the replay of record-limited games on a
+ * larger build work as after monsoon_rollout.  The games stay loaded with the bot's row in place: monsoon_decide_round_dev
+ * / monsoon_play_rounds_dev refuse them (MONSOON_ERR_STATE) until players are assigned again; monsoon_rollout itself and
+ * monsoon_assign_players keep refusing negative rows, and monsoon_state_load never loads one. */
+#define MONSOON_PLAYER_EXPERT (-1)
+int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                              int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
+                              int32_t* out_counts, int8_t* out_results, int32_t* out_steps);
+
 /* Per-game decks of configuration C5 on the device: for every seed, numpy.random.RandomState(seed).choice(pool, 12,
  * replace=False) twice -> out_pairs[n][2][12] (card indices taken from pool[pool_n], 12 <= pool_n <= 128).  The caller
  * passes the pre-stream seeds (game seed ^ 0x9E3779B9).  Host buffers in and out; needs no loaded games.

@@ -46,6 +46,8 @@ class EvolutionaryConfig:
     lanes_per_game: int = 0          # hot-kernel variant: candidate lanes per game (0 = build default)
     concurrent_tiers: bool = True    # a schedule with games on both records: the two sub-schedules from two host threads (two handles, two streams)
     ga_on_device: bool = False       # offspring + selection order through monsoon_ga_* (same numpy stream; results within a few ulp of the host's)
+    expert_eval_interval: int = 0    # every that many generations the parents play the reference's scripted bot (0 = never): the absolute yardstick
+    expert_eval_games: int = 32      # games per individual of such an evaluation (sides alternate)
 
     # nested-JSON sections of the reference's configs/config.json -> flat fields
     _SECTIONS = {
@@ -76,6 +78,8 @@ class EvolutionaryConfig:
             raise ValueError("mode must be 'rollout' or 'as_written'")
         if self.schedule not in ("round_robin", "ring"):
             raise ValueError("schedule must be 'round_robin' or 'ring'")
+        if self.expert_eval_interval < 0 or self.expert_eval_games <= 0:
+            raise ValueError("expert_eval_interval must not be negative and expert_eval_games must be positive")
 
     @classmethod
     def from_json(cls, json_path):

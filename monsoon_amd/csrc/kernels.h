@@ -248,7 +248,40 @@ struct EnvPolicy {
 // ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
 // play, plays the weights of row pol.rows[g], ends the episode by the env's rules after every commit (fault, winner,
 // max_steps: include/monsoon.h), stops after `rounds` decisions with FAULT_OPP_BOUND, and writes no scores / best.
-template <int U, bool ENV = false>
+// VS = true (k_play_vs, vs_expert.hip; with ENV = false): a side whose weight row is MONSOON_PLAYER_EXPERT is the
+// reference's scripted bot.  Its round runs no legal mask, clone, features or arg-max: candidate lane 0 runs
+// expert_action() and, unless that raised, step() on column 0 -- the current record's image with the stream window
+// attached -- and column 0 is then "the best successor" that the commit takes over.
+//
+// MSB_COMMIT_BEST is that commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
+// the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
+// whole wave (the used-up block becomes the new "next" block; the twist buffer is the column area, hence the second copy
+// of v_best); the committed successor's features (feat_ok: wf[20..29] holds them) become the "before" side of the next
+// decision.  It is a macro because the bot's round expands it a second time: the instantiations without a bot then see the
+// statements they always had, in place, and compile to the same instructions as before.
+#define MSB_COMMIT_BEST()                                                                           \
+  __syncthreads();                                                                                  \
+  MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])                                                      \
+  __syncthreads();                                                                                  \
+  {                                                                                                 \
+    uint32_t new_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe.rng_pos());                 \
+    int cur = (meta.rng >> 16) & 1;                                                                 \
+    if (new_pos >= (uint32_t)MT_N) {                                                                \
+      new_pos -= MT_N;                                                                              \
+      wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);                                     \
+      MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])                                                  \
+      __syncthreads();                                                                              \
+      cur ^= 1;                                                                                     \
+      if (lane == 0) pe.rng_block_advance();                                                        \
+    }                                                                                               \
+    meta.rng = new_pos | ((uint32_t)cur << 16);                                                     \
+    if (lane == 0) attach_rng(pe, b, g, meta.rng);                                                  \
+    have_before = feat_ok != 0;                                                                     \
+    if (have_before && lane < 10) wf[10 + lane] = wf[20 + lane];                                    \
+    __syncthreads();                                                                                \
+    MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])                                                     \
+  }
+template <int U, bool ENV = false, bool VS = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol) {
   typedef PlayLds<U> L;
@@ -310,6 +343,38 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         last_score = NAN;
       }
       break;
+    }
+    if constexpr (VS) {
+      if ((pe.local() == 0 ? meta.p1 : meta.p2) < 0) {   // (uniform) the scripted bot is to play
+        int a = 155, f = 0, fs = 0;
+        if (lane == 0) {   // (the other lanes wait at the barrier)
+          a = ce.expert_action();
+          f = ce.fault();   // random.choice([]) inside the bot: nothing is stepped, the game ends
+          if (!f) {
+            ce.step(a);
+            fs = ce.fault();
+            if (!fs && ce.observation_raises()) fs = FAULT_INT_CARD;
+          }
+        }
+        __syncthreads();
+        a = __builtin_amdgcn_readfirstlane(a);
+        f = __builtin_amdgcn_readfirstlane(f);
+        fs = __builtin_amdgcn_readfirstlane(fs);
+        MSB_EACH_GRANULE(v_best[j_] = priv[gr_ * U])   // the successor (if the bot raised: the record with its cursor moved on)
+        constexpr int feat_ok = 0;   // the bot's successor has no features: the next decision computes its "before" side
+        MSB_COMMIT_BEST()
+        if (!f) {   // one committed transition, no decision, no look-ahead
+          meta.steps++;
+          meta.last_action = (uint8_t)a;
+        }
+        played++;
+        if (f | fs) {   // a draw with that code, as after a decision's commit below
+          meta.fault = (uint8_t)(f ? f : fs);
+          meta.result = -1;
+          break;
+        }
+        continue;
+      }
     }
 #if defined(MSB_STUDY_LEGAL)
     {   // study build (scripts/step_cost.sh): the legal mask computed once more
@@ -479,29 +544,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       }
       PROF_MARK(6);   // argmax + new best into registers
     }
-    // commit: adapter = adapter.apply_action(best).  The successor carries its own stream cursor (H_RNGPOS).
-    __syncthreads();
-    MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])
-    __syncthreads();
-    {
-      uint32_t new_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe.rng_pos());
-      int cur = (meta.rng >> 16) & 1;
-      if (new_pos >= (uint32_t)MT_N) {
-        new_pos -= MT_N;
-        wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);   // the used-up block becomes the new "next" block
-        MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])               // (the twist buffer is the column area)
-        __syncthreads();
-        cur ^= 1;
-        if (lane == 0) pe.rng_block_advance();
-      }
-      meta.rng = new_pos | ((uint32_t)cur << 16);
-      if (lane == 0) attach_rng(pe, b, g, meta.rng);
-      // the committed successor's features become the "before" side of the next decision
-      have_before = feat_ok != 0;
-      if (have_before && lane < 10) wf[10 + lane] = wf[20 + lane];
-      __syncthreads();
-      MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])
-    }
+    MSB_COMMIT_BEST()
     meta.steps++;
     meta.last_action = (uint8_t)run_a;
     meta.lookahead += (uint32_t)n_legal;   // every legal action is stepped exactly once; the commit re-executes nothing
@@ -540,6 +583,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   }
   MSB_EACH_GRANULE(grec[gr_] = v_par[j_])
 #undef MSB_EACH_GRANULE
+#undef MSB_COMMIT_BEST
   if (lane == 0) {
     b.meta[g] = meta;
     if constexpr (ENV) {
@@ -595,5 +639,8 @@ struct VariantOps {
   void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,
                int parity);
 };
+
+// k_play_vs<U, W> at the build's default variant (vs_expert.hip): the rollout kernel that knows the scripted bot.
+const VariantOps* monsoon_vs_expert_ops();
 
 }  // namespace msbk

@@ -302,6 +302,36 @@ __global__ void k_collect(DevBuffers b, int n, int32_t* counts, int8_t* results,
   if (faults) faults[m.match] = (uint8_t)reported_fault(m);
 }
 
+// monsoon_rollout_vs_expert's form of k_collect: a match counts for its INDIVIDUAL -- p1 if that is one (a win = FIRST won),
+// else p2 (a win = SECOND won); a match of the bot against itself touches no row.  Same grouping, by that row.
+__global__ void k_collect_vs(DevBuffers b, int n, int32_t* counts, int8_t* results, int32_t* steps, uint8_t* faults) {
+  int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool on = g < n;
+  GameMeta m = b.meta[on ? g : 0];
+  int r = m.result == -2 ? -1 : m.result;
+  const int row = m.p1 >= 0 ? m.p1 : m.p2;
+  const bool won = r == (m.p1 >= 0 ? 0 : 1);
+  const bool counted = on && row >= 0;
+  const int lane = threadIdx.x & 63;
+  for (unsigned long long todo = __ballot(counted); todo;) {
+    const int leader = __builtin_ctzll(todo);
+    const int key = __builtin_amdgcn_readlane(row, leader);
+    const bool mine = counted && row == key;
+    const unsigned long long grp = __ballot(mine);
+    const int wins = __popcll(__ballot(mine && won)), draws = __popcll(__ballot(mine && r == -1));
+    if (lane == leader) {
+      if (wins) atomicAdd(&counts[3 * key + 0], wins);
+      if (draws) atomicAdd(&counts[3 * key + 1], draws);
+      atomicAdd(&counts[3 * key + 2], __popcll(grp));
+    }
+    todo &= ~grp;
+  }
+  if (!on) return;
+  if (results) results[m.match] = (int8_t)r;
+  if (steps) steps[m.match] = m.steps;
+  if (faults) faults[m.match] = (uint8_t)reported_fault(m);
+}
+
 // monsoon_debug_build / monsoon_debug_op (diagnostics; scenario tests): ONE lane runs scenario.inc on game g.  The
 // engine of this kernel logs the order in which abilities run (TraceLaneMem) -- the product kernels' engines do not.
 constexpr int DBG_TRACE_CAP = 256;
@@ -608,6 +638,8 @@ struct monsoon {
   size_t ovf_lanes = 0;   // stepping lanes b.wk_ovf has room for (OVF_WORDS words each)
   unsigned long long st_acc[ST_N], st_base[ST_N];   // statistics: totals of earlier batches, baseline of the loaded one
   int grid_waves = 0; // persistent grid size of k_decide (resident wavefronts), 0 = not yet queried
+  int vs_grid_waves = 0;   // ... of k_play_vs (monsoon_rollout_vs_expert), 0 = not yet queried
+  bool bot_rows = false;   // the loaded games' p1 / p2 may be MONSOON_PLAYER_EXPERT: only k_play_vs may play them
   int n = 0;          // games loaded by the last reset
   int n_individuals = 0;   // rows of the uploaded weight table
   int weights_cap = 0;     // rows allocated
@@ -702,11 +734,11 @@ extern "C" {
 
 int monsoon_version(void) {
 #if defined(MSB_EXT) && MSB_EXT == 2
-  return 0x30002;   // bits 16 + 17: the large extended record (254 entity slots)
+  return 0x30003;   // bits 16 + 17: the large extended record (254 entity slots)
 #elif defined(MSB_EXT) && MSB_EXT
-  return 0x10002;   // bit 16: extended record
+  return 0x10003;   // bit 16: extended record
 #else
-  return 2;
+  return 3;
 #endif
 }
 
@@ -1345,13 +1377,18 @@ int monsoon_upload_weights(monsoon_t* h, const double* weights, int32_t n_indivi
   return MONSOON_OK;
 }
 
-static int assign_players(monsoon_t* h, const int32_t* p1, const int32_t* p2, int match_base) {
+// min_row = MONSOON_PLAYER_EXPERT: monsoon_rollout_vs_expert's schedules, in which a side may be the scripted bot
+static int assign_players(monsoon_t* h, const int32_t* p1, const int32_t* p2, int match_base, int min_row = 0) {
   int n = h->n;
-  for (int i = 0; i < n; i++)
-    if (p1[i] < 0 || p2[i] < 0 || p1[i] >= h->n_individuals || p2[i] >= h->n_individuals) {
+  bool bot_rows = false;
+  for (int i = 0; i < n; i++) {
+    if (p1[i] < min_row || p2[i] < min_row || p1[i] >= h->n_individuals || p2[i] >= h->n_individuals) {
       h->err = "monsoon_assign_players: index outside the uploaded weight table";
       return MONSOON_ERR_ARG;
     }
+    bot_rows |= p1[i] < 0 || p2[i] < 0;
+  }
+  h->bot_rows = bot_rows;
   HIP_TRY(h, hipMemcpyAsync(h->d_p1, p1, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_p2, p2, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_assign, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_p1, h->d_p2, match_base);
@@ -1403,23 +1440,29 @@ static const int g_lds_pad = getenv("MONSOON_LDS_PAD") ? atoi(getenv("MONSOON_LD
 
 // `rounds` decisions of every loaded game in ONE launch (1 = a decision round; max_turns + 1 = whole games: the extra
 // round turns "still running at the cap" into a result).
-static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed) {
+// vs = true: k_play_vs, the kernel that knows the scripted bot (the build's default variant, whatever the handle's is).
+static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false) {
+  if (h->bot_rows && !vs) {   // (a weight row of -1 must never reach k_play)
+    h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
+    return MONSOON_ERR_STATE;
+  }
   size_t slot = 0;
   if (timed) {
     int rc = timing_begin(h, &slot);
     if (rc) return rc;
   }
-  const VariantOps* v = h->var;
+  const VariantOps* v = vs ? monsoon_vs_expert_ops() : h->var;
   const int lds = v->lds_bytes + g_lds_pad;
-  if (!h->grid_waves) {   // resident wavefronts of the handle's kernel variant (queried once)
+  int& grid_waves = vs ? h->vs_grid_waves : h->grid_waves;
+  if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
     int per_cu = 0;
     hipDeviceProp_t prop;
     HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
     HIP_TRY(h, v->occupancy(&per_cu, lds));
-    h->grid_waves = per_cu > 0 ? per_cu * prop.multiProcessorCount : 4096;
+    grid_waves = per_cu > 0 ? per_cu * prop.multiProcessorCount : 4096;
   }
   // one decision per game and launch: two waves per slot measured best; many decisions per game: exactly the resident waves
-  int grid = rounds > 1 ? h->grid_waves : 2 * h->grid_waves;
+  int grid = rounds > 1 ? grid_waves : 2 * grid_waves;
   if (const char* e = getenv("MONSOON_GRID")) grid = atoi(e);
   // the persistent form needs a wavefront for every one of its POP_PARTS ranges
   const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
@@ -1502,25 +1545,26 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
   return MONSOON_OK;
 }
 
-int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
-                    int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
-                    int32_t* out_counts, int8_t* out_results, int32_t* out_steps) {
+// monsoon_rollout (min_row = 0) and monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot)
+static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                        int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
+                        int8_t* out_results, int32_t* out_steps) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
       max_turns > 30000) {
-    h->err = "monsoon_rollout: bad argument";
+    h->err = std::string(who) + ": bad argument";
     return MONSOON_ERR_ARG;
   }
   // The whole schedule and every deck are checked before anything is loaded or launched.
   for (int i = 0; i < n_matches; i++) {
     const monsoon_match& mm = matches[i];
-    if (mm.p1 < 0 || mm.p1 >= n_individuals || mm.p2 < 0 || mm.p2 >= n_individuals || mm.deck >= (uint32_t)n_decks) {
-      h->err = "monsoon_rollout: schedule entry " + std::to_string(i) + " out of range";
+    if (mm.p1 < min_row || mm.p1 >= n_individuals || mm.p2 < min_row || mm.p2 >= n_individuals || mm.deck >= (uint32_t)n_decks) {
+      h->err = std::string(who) + ": schedule entry " + std::to_string(i) + " out of range";
       return MONSOON_ERR_ARG;
     }
   }
-  int rc = check_decks(h, deck_pairs, (size_t)n_decks * 24, "monsoon_rollout");
+  int rc = check_decks(h, deck_pairs, (size_t)n_decks * 24, who);
   if (rc) return rc;
   rc = monsoon_upload_weights(h, weights, n_individuals);
   if (rc) return rc;
@@ -1563,12 +1607,14 @@ int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, 
       p2[i] = mm.p2;
     }
     rc = monsoon_reset(h, n, seeds.data(), decks.data(), nullptr);
-    if (!rc) rc = assign_players(h, p1.data(), p2.data(), base);
+    if (!rc) rc = assign_players(h, p1.data(), p2.data(), base, min_row);
     if (rc) return rc;
-    // one launch plays the whole batch to the end
-    rc = launch_play(h, n, max_turns, max_turns + 1, 0, true);
+    // one launch plays the whole batch to the end; a batch without a bot is k_play's, counted by k_collect, as ever
+    const bool vs = h->bot_rows;
+    rc = launch_play(h, n, max_turns, max_turns + 1, 0, true, vs);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results, h->d_steps, d_faults);
+    hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
+                       h->d_steps, d_faults);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     rc = drain_timing(h);
@@ -1581,6 +1627,20 @@ int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, 
   if (out_steps) HIP_TRY(h, hipMemcpy(out_steps, h->d_steps, (size_t)n_matches * 4, hipMemcpyDeviceToHost));
   h->rollout_matches = (size_t)n_matches;
   return MONSOON_OK;
+}
+
+int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                    const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                    int32_t* out_steps) {
+  return rollout_impl(h, "monsoon_rollout", 0, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns, out_counts,
+                      out_results, out_steps);
+}
+
+int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                              const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                              int32_t* out_steps) {
+  return rollout_impl(h, "monsoon_rollout_vs_expert", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
+                      max_turns, out_counts, out_results, out_steps);
 }
 
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches) {

@@ -230,6 +230,15 @@ class BatchEngine:
         return (action, best, scores) if want_scores else (action, best)
 
     def rollout(self, weights, matches, deck_pairs, max_turns, want_results=False):
+        return self._rollout("monsoon_rollout", weights, matches, deck_pairs, max_turns, want_results)
+
+    def rollout_vs_expert(self, weights, matches, deck_pairs, max_turns, want_results=False):
+        """monsoon_rollout_vs_expert: a rollout in which p1, p2 or both of a match may be monsoon_amd.EXPERT (-1), the
+        reference's scripted bot.  counts[n][3] go to the row of the match's individual -- p1 if it is one (a win = FIRST
+        won), else p2 (a win = SECOND won); results stay FIRST / SECOND, steps count both sides' committed steps."""
+        return self._rollout("monsoon_rollout_vs_expert", weights, matches, deck_pairs, max_turns, want_results)
+
+    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results):
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         n_ind = weights.shape[0]
         deck_pairs = np.ascontiguousarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12)
@@ -242,8 +251,8 @@ class BatchEngine:
         counts = np.zeros((n_ind, 3), dtype=np.int32)
         results = np.zeros(len(m), dtype=np.int8) if want_results else None
         steps = np.zeros(len(m), dtype=np.int32) if want_results else None
-        self._ck(self.lib.monsoon_rollout(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
-                                          max_turns, _ptr(counts), _ptr(results), _ptr(steps)), "monsoon_rollout")
+        self._ck(getattr(self.lib, entry)(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
+                                          max_turns, _ptr(counts), _ptr(results), _ptr(steps)), entry)
         # the handle now holds the last batch of the schedule
         self.n = len(m) - ((len(m) - 1) // self.max_games) * self.max_games
         return (counts, results, steps) if want_results else counts

@@ -2,7 +2,9 @@
 
 initialize(); run(): while not population.should_terminate(): parents (+ offspring after
 generation 0) -> FitnessEvaluator.evaluate_population -> assign / (mu+lambda) selection ->
-training_log.csv row -> periodic checkpoint; then results_summary.txt.
+training_log.csv row -> periodic checkpoint; then results_summary.txt.  With config.expert_eval_interval
+the parents also play the reference's scripted bot every that many generations (evaluate_vs_expert):
+co-evolutionary fitness is relative, the bot is the yardstick that stays put.
 """
 import os
 import time
@@ -25,6 +27,7 @@ class EvolutionEngine:
         self.start_time = None
         self.results_dir = config.results_dir
         self._rollout_fn = rollout_fn
+        self.vs_expert_log = []   # (generation, mean, best) of every evaluation against the scripted bot
         os.makedirs(self.results_dir, exist_ok=True)
 
     def initialize(self):
@@ -51,26 +54,35 @@ class EvolutionEngine:
                 pop.generation += 1
             else:
                 pop.select_from_combined(everyone, scores, order=ga.ga_select(scores) if ga is not None else None)
-            self._log_generation(time.time() - t0)
+            vs_expert = None
+            every = self.config.expert_eval_interval
+            if every and pop.generation % every == 0:
+                vs = self.fitness_evaluator.evaluate_vs_expert(pop.get_parents(), pop.generation)
+                vs_expert = (sum(vs) / len(vs), max(vs))
+                self.vs_expert_log.append((pop.generation,) + vs_expert)
+            self._log_generation(time.time() - t0, vs_expert)
             if pop.generation % self.config.checkpoint_interval == 0:
                 self._save_checkpoint()
         return self._finalize_training(time.time() - self.start_time)
 
-    def _log_generation(self, generation_time):
+    def _log_generation(self, generation_time, vs_expert=None):
         stats = self.population.get_population_stats()
         ev = self.fitness_evaluator.get_stats()
         print(f"gen {stats['generation']}: best {stats['best_fitness']:.4f} mean {stats['mean_fitness']:.4f} "
-              f"std {stats['std_fitness']:.4f} games/s {ev['games_per_second']:.1f} env-steps/s {ev['env_steps_per_second']:.3g}")
+              f"std {stats['std_fitness']:.4f} games/s {ev['games_per_second']:.1f} env-steps/s {ev['env_steps_per_second']:.3g}"
+              + (f" vs_expert mean {vs_expert[0]:.4f} best {vs_expert[1]:.4f}" if vs_expert else ""))
         if not self.config.save_logs:
             return
         path = os.path.join(self.results_dir, "training_log.csv")
         if not os.path.exists(path):
             with open(path, "w") as f:   # the reference's columns + env_steps_per_sec
-                f.write("generation,time,best_fitness,mean_fitness,std_fitness,diversity,avg_sigma,games_per_sec,env_steps_per_sec\n")
+                f.write("generation,time,best_fitness,mean_fitness,std_fitness,diversity,avg_sigma,games_per_sec,env_steps_per_sec"
+                        + (",vs_expert_mean,vs_expert_best" if self.config.expert_eval_interval else "") + "\n")
         with open(path, "a") as f:
             f.write(f"{stats['generation']},{generation_time:.2f},{stats['best_fitness']:.6f},{stats['mean_fitness']:.6f},"
                     f"{stats['std_fitness']:.6f},{stats['diversity']:.6f},{stats['avg_mutation_strength']:.6f},"
-                    f"{ev['games_per_second']:.1f},{ev['env_steps_per_second']:.1f}\n")
+                    f"{ev['games_per_second']:.1f},{ev['env_steps_per_second']:.1f}"
+                    + ((f",{vs_expert[0]:.6f},{vs_expert[1]:.6f}" if vs_expert else ",,") if self.config.expert_eval_interval else "") + "\n")
 
     def _save_checkpoint(self):
         stamp = datetime.now().strftime("%Y%m%d_%H%M%S")

@@ -66,11 +66,50 @@ def ring_schedule(n_individuals, games_per_individual, generation):
     return out
 
 
+EXPERT = -1   # MONSOON_PLAYER_EXPERT (include/monsoon.h): the reference's scripted bot as p1 / p2 of a match
+
+
+def expert_schedule(n_individuals, games_per_individual, generation, sides="both"):
+    """The absolute yardstick (play_vs_expert.py's tournament): individual i plays games_per_individual games against
+    the scripted bot.  sides="both": game k has the individual FIRST for even k, SECOND for odd k; "first" / "second"
+    fix it.  Seed hash32(generation, i, k, 0xE): a fourth word, so the games differ from the ring / round-robin ones."""
+    if sides not in ("both", "first", "second"):
+        raise ValueError("sides must be 'both', 'first' or 'second'")
+    i, k = np.meshgrid(np.arange(n_individuals), np.arange(games_per_individual), indexing="ij")
+    i, k = i.ravel(), k.ravel()
+    first = (k % 2 == 0) if sides == "both" else np.full(len(k), sides == "first")
+    out = np.zeros(len(i), dtype=MATCH_DTYPE)
+    out["p1"], out["p2"] = np.where(first, i, EXPERT), np.where(first, EXPERT, i)
+    out["seed"] = hash32_array(generation, i, k, 0xE)
+    return out
+
+
+def match_rows(matches):
+    """Row of a match = the individual its counts belong to: p1 if it is one, else p2 (p1 is the scripted bot); -1 for a
+    match of the bot against itself, which belongs to nobody.  Every piece of count bookkeeping goes through here."""
+    return np.where(matches["p1"] >= 0, matches["p1"], matches["p2"])
+
+
+def match_wins(matches, results):
+    """bool[n]: the match's individual won -- FIRST won where it is p1, SECOND won where p1 is the bot."""
+    return np.asarray(results) == np.where(matches["p1"] >= 0, 0, 1)
+
+
+def _uncount(counts, matches, results):
+    """Take the given matches, with the results they had, out of counts[n][3]."""
+    rows = match_rows(matches)
+    on = rows >= 0
+    np.subtract.at(counts[:, 0], rows[on], match_wins(matches, results)[on])
+    np.subtract.at(counts[:, 1], rows[on], (np.asarray(results) == -1)[on])
+    np.subtract.at(counts[:, 2], rows[on], 1)
+
+
 def shard_by_individual(matches, n_individuals, rank, world):
     """Contiguous blocks of row individuals per rank."""
     lo = (n_individuals * rank) // world
     hi = (n_individuals * (rank + 1)) // world
-    return matches[(matches["p1"] >= lo) & (matches["p1"] < hi)]
+    rows = match_rows(matches)
+    return matches[(rows >= lo) & (rows < hi)]
 
 
 def fitness_from_counts(counts, games_per_individual):
@@ -101,10 +140,7 @@ def replace_capacity_faulted(counts, results, steps, faults, matches, replay):
     if len(bad) == 0:
         return 0
     c2, r2, s2, f2 = replay(matches[bad])
-    p1 = matches["p1"][bad]
-    np.subtract.at(counts[:, 0], p1, results[bad] == 0)
-    np.subtract.at(counts[:, 1], p1, results[bad] == -1)
-    np.subtract.at(counts[:, 2], p1, 1)
+    _uncount(counts, matches[bad], results[bad])
     counts += np.asarray(c2, dtype=counts.dtype)
     results[bad], steps[bad], faults[bad] = r2, s2, f2
     return len(bad)
@@ -157,10 +193,7 @@ def tiered_rollout(play, n_rows, matches, deck_pairs, concurrent=False):
             continue
         replays += len(bad)
         c2, r2, s2, f2 = run(t, matches[bad])
-        p1 = matches["p1"][bad]
-        np.subtract.at(counts[:, 0], p1, results[bad] == 0)
-        np.subtract.at(counts[:, 1], p1, results[bad] == -1)
-        np.subtract.at(counts[:, 2], p1, 1)
+        _uncount(counts, matches[bad], results[bad])
         counts += np.asarray(c2, dtype=np.int64)
         results[bad], steps[bad], faults[bad] = r2, s2, f2
         tier[bad] = t
@@ -220,11 +253,12 @@ class FitnessEvaluator:
     def _hip_rollout(self, weights, matches, deck_pairs, max_turns):
         import threading
         lock = threading.Lock()
+        vs_expert = bool(((matches["p1"] < 0) | (matches["p2"] < 0)).any())   # the scripted bot plays: monsoon_rollout_vs_expert
 
         def play(tier, sub, sub_pairs):
             eng = self._engine(tier)
             before = eng.stats()["lookahead_steps"]
-            counts, results, steps = eng.rollout(weights, sub, sub_pairs, max_turns, want_results=True)
+            counts, results, steps = (eng.rollout_vs_expert if vs_expert else eng.rollout)(weights, sub, sub_pairs, max_turns, want_results=True)
             with lock:
                 self.total_env_steps += eng.stats()["lookahead_steps"] - before
                 self.total_decisions += int(steps.sum())
@@ -335,6 +369,48 @@ class FitnessEvaluator:
         fitness = fitness_from_counts(counts[:n], per_individual)
         self._update_hall_of_fame(population, fitness)
         return fitness
+
+    def evaluate_vs_expert(self, population, generation=0, games_per_individual=None, sides="both"):
+        """The population against the reference's scripted bot (play_vs_expert.py; the success criterion of
+        evo/EVOLUTIONARY_PLAN.md): individual i plays `games_per_individual` games (config.expert_eval_games by default)
+        of expert_schedule; returns its score (wins + 0.5 * draws) / games.  self.last_vs_expert keeps the raw
+        counts[n][3] = {wins, draws, games}.  Decks, tiers, sharding and the all-reduce are evaluate_population's; the hall
+        of fame, the total_* statistics and a DeckEvolutionConfig's sequential stream are left alone, so the fitness
+        evaluate_population returns does not depend on whether this was called."""
+        from .cards import RANDOM_DECK
+        cfg = self.config
+        n = len(population)
+        games = int(cfg.expert_eval_games if games_per_individual is None else games_per_individual)
+        if games <= 0:
+            raise ValueError("games_per_individual must be positive")
+        matches = expert_schedule(n, games, generation, sides)
+        weights = np.stack([np.asarray(o.weights, dtype=np.float64) for o in population])
+        dist = self._dist()
+        mine = matches
+        if dist is not None:
+            mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size()).copy()
+        per_game = self.deck_config is not None and not self.deck_config.is_static(generation)
+        if per_game:
+            # The random phase of a DeckEvolutionConfig draws every game's decks from ONE sequential stream: drawing from it
+            # here would change the decks of the next evaluate_population.  These games take their decks as configuration C5
+            # does instead, each from its own seed's pre-stream.
+            deck_config, deck, self.deck_config = self.deck_config, cfg.deck, None
+            cfg.deck = RANDOM_DECK
+        try:
+            deck_pairs = self._decks_for(mine, generation) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
+        finally:
+            if per_game:
+                self.deck_config, cfg.deck = deck_config, deck
+        fn = self._rollout_fn or self._hip_rollout
+        counts = np.zeros((n, 3), dtype=np.int64)
+        if len(mine):
+            keep = self.total_env_steps, self.total_decisions
+            counts += np.asarray(fn(weights, mine, deck_pairs, cfg.max_turns), dtype=np.int64)
+            self.total_env_steps, self.total_decisions = keep
+        if dist is not None:
+            counts = self._all_reduce_counts(dist, counts)
+        self.last_vs_expert = counts
+        return fitness_from_counts(counts, games)
 
     @staticmethod
     def _all_reduce_counts(dist, counts):
