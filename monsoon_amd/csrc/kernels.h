@@ -32,6 +32,7 @@
 #include "rules.h"
 #include "canon.h"
 #include "coop_features.h"
+#include "coop_draw.h"
 
 namespace msbk {
 using namespace msb;
@@ -293,6 +294,12 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   // extended records keep the serial form: with 2 x 12 VGPRs of record per lane next to the phase's temporaries the
   // register allocator spilled them (k_play<8,2>: 0 -> 312 spilled VGPRs, scratch 3 168 -> 3 408 B), see DESIGN.md section 4.
   constexpr bool COOP = U < 64 && GPL == 1;
+  // The weighted draw of the REPLACE candidates resolved once per decision by the whole wave (coop_draw.h): standard record.
+#if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
+  constexpr bool COOP_DRAW = GPL == 1;
+#else
+  constexpr bool COOP_DRAW = false;
+#endif
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
   if (meta.result != -2) {
@@ -348,6 +355,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if ((pe.local() == 0 ? meta.p1 : meta.p2) < 0) {   // (uniform) the scripted bot is to play
         int a = 155, f = 0, fs = 0;
         if (lane == 0) {   // (the other lanes wait at the barrier)
+          if constexpr (COOP_DRAW) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;   // the bot's own REPLACE draws serially
           a = ce.expert_action();
           f = ce.fault();   // random.choice([]) inside the bot: nothing is stepped, the game ends
           if (!f) {
@@ -389,6 +397,19 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     uint64_t rem[3] = {mask[0], mask[1], mask[2]};
     const int n_legal = __popcll(mask[0]) + __popcll(mask[1]) + __popcll(mask[2]);
     PROF_MARK(1);   // legal mask
+    if constexpr (COOP_DRAW) {
+      // what the first draw of this decision's REPLACE steps (actions 148..151) will find; the candidates read it after
+      // the barrier below, wherever in the passes they sit
+      uint32_t hint = 0u;
+      if ((mask[2] >> (148 - 128)) & 0xfull) {   // (uniform)
+        const bool u_ok = (meta.rng & 0xffffu) + 1u < (uint32_t)(2 * MT_N);
+        const uint32_t ra = u_ok ? peek_u32(b, g, meta.rng) : 0u, rb = u_ok ? peek_u32(b, g, meta.rng + 1u) : 0u;
+        int sl = lane;   // (opaque, as for the features below)
+        asm volatile("" : "+v"(sl));
+        hint = coop_draw(pe, sl, ra, rb, u_ok);
+      }
+      if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = hint;
+    }
     const bool before_raises = pe.observation_raises();
     // weights and "before" features are parked in LDS: 40 fewer live VGPRs across the recursive step calls
     {

@@ -2067,7 +2067,29 @@ struct Engine {
   }
 
   // Player.draw, player.py:46-52: numpy choice(deck, size=1, p=w/sum(w))
-  MSB_HD MSB_A_DRAW void draw(int o, int amount) {
+  //
+  // The search asks whether fl(acc / last) <= u for the running sum acc, and mostly gets the answer without dividing.
+  // Write e = 2^-53.  A correctly rounded quotient is q = (acc / last)(1 + d), |d| <= e, and t = fl(u * last) =
+  // u * last * (1 + d'), |d'| <= e (u is a multiple of e below 1 and last is about 1: nothing underflows).  With
+  // diff = fl(acc - t) = (acc - t)(1 + d''), |d''| <= e, and band = t * 2^-50 = 8e * t (an exact scaling):
+  //   diff > band   =>  acc - t > 8e t / (1 + e) > 7e t  =>  acc > u last (1 - e)(1 + 7e) > u last (1 + 5e)
+  //                 =>  q > u (1 + 5e)(1 - e) > u: the search stops here;
+  //   diff < -band  =>  acc < t (1 - 7e) <= u last (1 + e)(1 - 7e) < u last (1 - 5e)
+  //                 =>  q < u (1 - 5e)(1 + e) < u: the search goes on.
+  // (u == 0: t = band = 0 and acc > 0, the first case.)  Only inside the band -- a few ulps around a cdf boundary -- is
+  // the quotient formed.  With last == 1.0 the quotient is acc itself.
+  //
+  // hint (the hot kernel's decision loop, coop_draw.h): index + 1 that the search of the FIRST draw finds, resolved by the
+  // whole wave before the candidates step; 0 = none.  The sample is still taken (cursor, block switch and overrun as ever).
+  MSB_HD MSB_INL bool draw_stops(double acc, double last, double u) const {   // !(acc / last <= u)
+    if (last == 1.0) return !(acc <= u);
+    const double t = u * last;
+    const double diff = acc - t, band = t * 0x1p-50;
+    if (diff > band) return true;
+    if (diff < -band) return false;
+    return !(acc / last <= u);
+  }
+  MSB_HD MSB_A_DRAW void draw(int o, int amount, int hint = 0) {
     MSB_SCOPE(PS_DRAW);
     for (int k = 0; k < amount; k++) {
       int n = pl_deck_n(o);
@@ -2075,22 +2097,46 @@ struct Engine {
         set_fault(FAULT_PY_EXCEPTION);  // choice over an empty deck raises
         return;
       }
-      double sum = 0.0;  // Python sum(): 0 + w0 + w1 ... left to right
-      for (int i = 0; i < n; i++) sum = sum + deck_w(o, i);
-      // cdf = cumsum(w/sum); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right').  The running sum is
-      // recomputed in the second pass (same operations, same order) instead of being kept in an array.
-      double last = 0.0;
-      for (int i = 0; i < n; i++) {
-        double p = deck_w(o, i) / sum;
-        last = (i == 0) ? p : last + p;   // ndarray.cumsum: sequential
-      }
-      double u = rng_random_sample();
       int idx = 0;
-      double acc = 0.0;
-      for (; idx < n; idx++) {
-        double p = deck_w(o, idx) / sum;
-        acc = (idx == 0) ? p : acc + p;
-        if (!(acc / last <= u)) break;
+      if (k == 0 && hint > 0) {
+        (void)rng_random_sample();
+        idx = hint - 1;
+      } else {
+        double sum = 0.0;  // Python sum(): 0 + w0 + w1 ... left to right
+        for (int i = 0; i < n; i++) sum = sum + deck_w(o, i);
+        // cdf = cumsum(w/sum); cdf /= cdf[-1]; idx = searchsorted(cdf, u, 'right').  The running sum is
+        // recomputed in the second pass (same operations, same order) instead of being kept in an array.
+        double last = 0.0;
+        for (int i = 0; i < n; i++) {
+          double p = deck_w(o, i) / sum;
+          last = (i == 0) ? p : last + p;   // ndarray.cumsum: sequential
+        }
+        double u = rng_random_sample();
+        double acc = 0.0;
+        for (; idx < n; idx++) {
+          double p = deck_w(o, idx) / sum;
+          acc = (idx == 0) ? p : acc + p;
+          if (draw_stops(acc, last, u)) break;
+        }
+#if defined(MSB_STUDY_DRAW)
+        {   // study build (scripts/step_cost.sh): the arithmetic of the draw once more; no state change, no sample taken
+          double sum2 = 0.0, last2 = 0.0, acc2 = 0.0;
+          for (int i = 0; i < n; i++) sum2 = sum2 + deck_w(o, i);
+          asm volatile("" : "+v"(sum2));
+          for (int i = 0; i < n; i++) {
+            double p = deck_w(o, i) / sum2;
+            last2 = (i == 0) ? p : last2 + p;
+          }
+          asm volatile("" : "+v"(last2));
+          int idx2 = 0;
+          for (; idx2 < n; idx2++) {
+            double p = deck_w(o, idx2) / sum2;
+            acc2 = (idx2 == 0) ? p : acc2 + p;
+            if (draw_stops(acc2, last2, u)) break;
+          }
+          asm volatile("" : : "v"(idx2), "v"(acc2) : "memory");
+        }
+#endif
       }
       if (idx >= n) {
         set_fault(FAULT_PY_EXCEPTION);
@@ -2182,9 +2228,18 @@ struct Engine {
   }
   // Player.cycle, player.py:79-81
   MSB_HD MSB_INL void cycle(int o, int hand_index) {
+#if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
+    // what the wave resolved for this decision's REPLACE candidates (0 where it did not, and in every other kernel):
+    // byte 0 for a replaced card that goes back to the deck, byte 1 for a single-use card, which does not
+    const int appended = !(hand_flags(o, hand_index) & CF_SINGLE_USE);
+    discard(o, hand_index);
+    if (fault()) return;
+    draw(o, 1, (int)((M::draw_hint() >> (appended ? 0 : 8)) & 0xff));
+#else
     discard(o, hand_index);
     if (fault()) return;
     draw(o, 1);
+#endif
   }
 
   // ------------------------------------------------------------------------------------------

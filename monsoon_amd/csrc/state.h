@@ -169,6 +169,14 @@ constexpr int WT_LDS = 928;      // behind the function-scope counters of the pr
 constexpr int WT_LDS = 16;       // LDS address 0 is avoided (the null LDS pointer)
 #endif
 constexpr int WK_OVF_LDS = WT_LDS + 8 * WT_LDS_N;    // u64: global address of this workgroup's work-stack overflow block
+// u32 behind it: what the hot kernel's wave resolved about the weighted draw of the current decision's REPLACE candidates
+// (coop_draw.h, rules.h cycle()): byte 0 / byte 1 = drawn index + 1 where the replaced card returns to the deck / does not;
+// 0 = nothing resolved, the draw runs its serial form.  Zero in every kernel but that one (lds_init_wtab).
+constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
+// The wave-uniform draw resolution of the hot kernel: standard record only.  0 builds the serial form everywhere.
+#ifndef MSB_COOP_DRAW
+#define MSB_COOP_DRAW 1
+#endif
 constexpr int LDS_RECORDS = WK_OVF_LDS + 16;         // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
@@ -263,6 +271,7 @@ struct FlatMem {
   MSB_HD MSB_INL double ldfg(int g, int k) const { return ldf(g * 16 + k); }
   MSB_HD MSB_INL void stfg(int g, int k, double v) { stf(g * 16 + k, v); }
   MSB_HD MSB_INL static double wtab(int age) { return g_wtab.v[age & AGE_MAX]; }
+  MSB_HD MSB_INL static uint32_t draw_hint() { return 0u; }
   // work stack: a per-thread array on the host, large enough never to evict; the device never steps a game through
   // this accessor
 #if defined(MSB_HOST_SKW)   // study / test build: the host evicts like the device does (oracle/Makefile libproduct_host_evict.so)
@@ -317,7 +326,10 @@ MSB_HD MSB_INL double lds_wtab(int age) {
 MSB_HD MSB_INL void lds_init_wtab(uint32_t* wk_ovf = nullptr) {
   for (int i = (int)__builtin_amdgcn_workitem_id_x(); i < WT_LDS_N; i += (int)__builtin_amdgcn_workgroup_size_x())
     *(MSB_AS_LDS double*)(uintptr_t)(WT_LDS + 8 * i) = g_wtab.v[i];
-  if (__builtin_amdgcn_workitem_id_x() == 0) *(MSB_AS_LDS uint64_t*)(uintptr_t)WK_OVF_LDS = (uint64_t)(uintptr_t)wk_ovf;
+  if (__builtin_amdgcn_workitem_id_x() == 0) {
+    *(MSB_AS_LDS uint64_t*)(uintptr_t)WK_OVF_LDS = (uint64_t)(uintptr_t)wk_ovf;
+    *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;
+  }
   __syncthreads();
 }
 // LDS image of one record, interleaved across the lanes of a wave in 16-BYTE granules: granule c of
@@ -375,6 +387,7 @@ struct LaneMem {   // this lane's private record among LANES interleaved ones
   MSB_HD MSB_INL static double ldfg(int g, int k) { return *(MSB_AS_LDS const double*)gb(g, k); }
   MSB_HD MSB_INL static void stfg(int g, int k, double v) { *(MSB_AS_LDS double*)gb(g, k) = v; }
   MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
+  MSB_HD MSB_INL static uint32_t draw_hint() { return *(MSB_AS_LDS const uint32_t*)(uintptr_t)DRAW_HINT_LDS; }
   MSB_HD MSB_INL static void trace_ability(int, int) {}
 };
 // The same with the ability log of the scenario tests switched on: {card, position} pairs appended to an LDS array
@@ -421,6 +434,7 @@ struct Col0Mem {
   MSB_HD MSB_INL static double ldfg(int g, int k) { return *(MSB_AS_LDS const double*)gb(g, k); }
   MSB_HD MSB_INL static void stfg(int g, int k, double v) { *(MSB_AS_LDS double*)gb(g, k) = v; }
   MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
+  MSB_HD MSB_INL static uint32_t draw_hint() { return 0u; }
   MSB_HD MSB_INL static void trace_ability(int, int) {}
   static constexpr int SKW = SK_CAP;   // (nothing is stepped through it)
   MSB_HD MSB_INL static uint32_t sk_ld(int) { return 0; }

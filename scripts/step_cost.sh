@@ -3,7 +3,8 @@
 # builds that execute every look-ahead step (or a prefix of it: -DMSB_STUDY_CUT_AT) one more time, scripts/ab_build.sh
 # <name> "-DMSB_STUDY_REPEAT=1 ..."; differences per launch are printed by scripts/step_cost.py.
 #   bash scripts/step_cost.sh base=monsoon_amd/libmonsoon_hip.so rep=monsoon_amd/libmonsoon_hip_rep.so ...
-# Study builds: -DMSB_STUDY_REPEAT=1 [-DMSB_STUDY_CUT_AT=n] (look-ahead step), -DMSB_STUDY_FEATURES=1, -DMSB_STUDY_LEGAL=1.
+# Study builds: -DMSB_STUDY_REPEAT=1 [-DMSB_STUDY_CUT_AT=n] (look-ahead step), -DMSB_STUDY_FEATURES=1, -DMSB_STUDY_LEGAL=1,
+# -DMSB_STUDY_DRAW=1 (with -DMSB_COOP_DRAW=0: the arithmetic of the serial weighted draw).
 # tag=library[@tree]: `tree` = another source tree with its own bench.py and the same study block in its kernels.h (round 3
 # compared itself with round 2's recursive core this way: `git archive 18c1ffb bench.py monsoon_amd include | tar -x -C study_r2`).
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
