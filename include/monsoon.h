@@ -338,6 +338,43 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev);
  * [0, n_individuals) or an n different from the loaded env's returns MONSOON_ERR_ARG.  Synchronises. */
 int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_individuals, const int32_t* rows, int32_t n);
 
+/* Afterstates: the successor of every legal action of every slot's current state, for a learner that evaluates them
+ * itself (afterstate TD, a value network over the successor's observation).  It is the reference's 1-ply look-ahead
+ * (evo/heuristic_agent.py: copy.deepcopy of the game, stream included, then apply_action) without the score: the successor
+ * of action a is exactly the state monsoon_env_step_dev would commit for a, before any opponent answers, and it is read
+ * the way monsoon_step, monsoon_observe and monsoon_features read a plain handle.  The env's episode rules are NOT applied
+ * to afterstates: no max_steps, no auto-reset, no bot turn.  The call works for whichever side is to play, with every
+ * opponent kind (with opponent 1 or 2 that side is always the agent's).
+ *
+ * K = max_after entries per slot.  Entry k < min(n_legal, K) is the k-th legal action in ascending order; n_legal is the
+ * full count, also where it exceeds K.  Entries k >= min(n_legal, K) get action = 255 and are otherwise not written.  An
+ * entry whose status is not 0 gets action, status, reward and winner, but no features and no observation; where the step
+ * itself raised (any status but FAULT_INT_CARD) the reference defines neither a reward nor a winner, and 0 and -2 are
+ * written.  A slot whose episode already ended before the agent acts (the pending end monsoon_env_step_dev reports at the
+ * next step) has n_legal = 0.
+ *
+ * The call changes nothing of the handle: no record, meta row, stream cursor, stream block, statistic or counter.  It is
+ * asynchronous on the handle's stream: one launch, no allocation, host copy or synchronisation, so it captures into a
+ * graph next to monsoon_env_step_dev.  MONSOON_ERR_STATE without a loaded env (before monsoon_env_reset, after
+ * monsoon_reset / monsoon_rollout); MONSOON_ERR_ARG for max_after outside 1..156, a NULL out, n_legal or action, an n_legal
+ * or obs that is not 4-byte aligned, or features / before_features that are not 8-byte aligned. */
+typedef struct {            /* caller-owned DEVICE buffers; K = max_after; any may be NULL except n_legal and action;
+                               n_legal and obs 4-byte aligned, features and before_features 8-byte aligned */
+  int32_t* n_legal;         /* [n]       legal actions of the slot's current state (may exceed K); 0 for a slot whose episode
+                                         already ended before the agent acts */
+  uint8_t* action;          /* [n][K]    entry k = the k-th legal action in ascending order; 255 for k >= min(n_legal, K) */
+  uint8_t* status;          /* [n][K]    0, or the fault code of the look-ahead step (msb_base.h), FAULT_INT_CARD (2) where the
+                                         successor's observation would raise */
+  int8_t*  reward;          /* [n][K]    the reference's reward of that step, as monsoon_step's */
+  int8_t*  winner;          /* [n][K]    -2 = no winner after the step; else 0 / 1 / -1 by the rollout contract */
+  double*  features;        /* [n][K][10] monsoon_features of the successor (status 0 only) */
+  int32_t* obs;             /* [n][K][540] monsoon_observe of the successor (status 0 only); 4-byte aligned */
+  double*  before_features; /* [n][10]   monsoon_features of the current state (not written where its observation raises,
+                                         nor for a slot with n_legal = 0 by a pending end) */
+} monsoon_env_after;
+
+int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int32_t max_after);   /* 1..156 */
+
 #ifdef __cplusplus
 }
 #endif

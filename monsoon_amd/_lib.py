@@ -55,6 +55,11 @@ class EnvViews(ctypes.Structure):    # monsoon_env_views: caller-owned device bu
                                                       "truncated", "fault", "illegal", "episode", "final_hash")]
 
 
+class EnvAfter(ctypes.Structure):    # monsoon_env_after: caller-owned device buffers (NULL = not wanted, except n_legal and action)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("n_legal", "action", "status", "reward", "winner", "features", "obs",
+                                                      "before_features")]
+
+
 SIGNATURES = {
     "monsoon_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "monsoon_destroy": (None, [ctypes.c_void_p]),
@@ -110,6 +115,7 @@ SIGNATURES = {
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
+    "monsoon_env_afterstates_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvAfter), ctypes.c_int32]),
 }
 
 

@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "env.h"
+#include "env_after.h"
 #include "kernels.h"
 
 using namespace msb;
@@ -680,6 +680,9 @@ struct monsoon {
   int opp_w_cap = 0;          // rows allocated
   int opp_n = 0;              // slots the last monsoon_env_set_opponents gave rows for (0 = never called)
   int opp_grid = 0;           // k_env_opp's grid: resident wavefronts, at most the slots (queried at reset)
+  int after_grid = 0;         // k_env_after's grid (monsoon_env_afterstates_dev), likewise
+  int after_waves = 0;        // resident wavefronts of k_env_after (queried once per handle)
+  int cu_count = 0;           // compute units of the device (queried once per handle)
 };
 
 static std::string g_create_error;
@@ -1804,6 +1807,28 @@ void* monsoon_stream(monsoon_t* h) { return h ? (void*)h->stream : nullptr; }
 // ---- vector env (env.inc) -----------------------------------------------------------------------
 }  // extern "C"
 
+// Compute units of the handle's device.
+static int device_cus(monsoon_t* h, int* out) {
+  if (!h->cu_count) {
+    hipDeviceProp_t prop;
+    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
+    h->cu_count = prop.multiProcessorCount;
+  }
+  *out = h->cu_count;
+  return MONSOON_OK;
+}
+
+// Work-stack overflow blocks for `lanes` stepping lanes (grid x candidate lanes of a kernel): grown, never shrunk.
+static int grow_ovf(monsoon_t* h, size_t lanes) {
+  if (lanes <= h->ovf_lanes) return MONSOON_OK;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipFree(h->b.wk_ovf));
+  h->b.wk_ovf = nullptr;
+  h->ovf_lanes = lanes;
+  HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
+  return MONSOON_OK;
+}
+
 // The heuristic opponent's turn for the slots of list `list`, then their views: two launches, no synchronisation.
 // k_env_opp reads the env's weight table through its own DevBuffers copy (monsoon_upload_weights' table is not touched).
 static int launch_env_opp(monsoon_t* h, int n, int list) {
@@ -1913,21 +1938,29 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     v.opp_count = (int32_t*)(h->d_opp + 16 * cap);
     v.opp_pop = (int*)(h->d_opp + 16 * cap + 4 * 2 * ENV_COUNT_STRIDE);
     const EnvOppOps* o = monsoon_env_opp_ops();
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
+    int per_cu = 0, cus = 0;
+    rc = device_cus(h, &cus);
+    if (rc) return rc;
     HIP_TRY(h, o->occupancy(&per_cu, o->lds_bytes));
     // persistent: the resident wavefronts, but no more than the slots, and one at least for each of the POP_PARTS ranges
-    h->opp_grid = std::max(POP_PARTS, std::min(per_cu > 0 ? per_cu * prop.multiProcessorCount : 4096, n));
-    if ((size_t)h->opp_grid * o->lanes > h->ovf_lanes) {   // work-stack overflow blocks for every workgroup of k_env_opp
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-      HIP_TRY(h, hipFree(h->b.wk_ovf));
-      h->b.wk_ovf = nullptr;
-      h->ovf_lanes = (size_t)h->opp_grid * o->lanes;
-      HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
-    }
+    h->opp_grid = std::max(POP_PARTS, std::min(per_cu > 0 ? per_cu * cus : 4096, n));
+    rc = grow_ovf(h, (size_t)h->opp_grid * o->lanes);   // work-stack overflow blocks for every workgroup of k_env_opp
+    if (rc) return rc;
     HIP_TRY(h, hipMemsetAsync(v.opp_count, 0, 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE), h->stream));
     HIP_TRY(h, hipMemsetAsync(v.opp_lookahead, 0, (size_t)n * 4, h->stream));
+  }
+  {   // monsoon_env_afterstates_dev allocates nothing: its grid and the overflow blocks of its workgroups are settled here
+    const EnvAfterOps* o = monsoon_env_after_ops();
+    if (!h->after_waves) {
+      int per_cu = 0, cus = 0;
+      rc = device_cus(h, &cus);
+      if (rc) return rc;
+      HIP_TRY(h, o->occupancy(&per_cu, o->lds_bytes));
+      h->after_waves = per_cu > 0 ? per_cu * cus : 4096;
+    }
+    h->after_grid = std::min(h->after_waves, n);
+    rc = grow_ovf(h, (size_t)h->after_grid * o->lanes);
+    if (rc) return rc;
   }
   HIP_TRY(h, hipMemcpyAsync((void*)v.seed0, seed0, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   if (decks) HIP_TRY(h, hipMemcpyAsync(v.decks, decks, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
@@ -1979,6 +2012,30 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
   hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, 0);
   HIP_TRY(h, hipGetLastError());
   if (h->env.opponent == 2) return launch_env_opp(h, n, 1);
+  return MONSOON_OK;
+}
+
+// One launch on the handle's stream: no allocation, copy or synchronisation (graph-capturable); nothing of the handle is
+// written (env_after.h).
+int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int32_t max_after) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_afterstates_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  const char* bad = nullptr;
+  if (!out || !out->n_legal || !out->action) bad = "out, out->n_legal and out->action are required";
+  else if (max_after < 1 || max_after > MONSOON_NUM_ACTIONS) bad = "1 <= max_after <= 156";
+  else if (((uintptr_t)out->obs | (uintptr_t)out->n_legal) & 3) bad = "n_legal and obs must be 4-byte aligned";
+  else if (((uintptr_t)out->features | (uintptr_t)out->before_features) & 7) bad = "features and before_features must be 8-byte aligned";
+  if (bad) {
+    h->err = std::string("monsoon_env_afterstates_dev: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  HIP_TRY(h, bind_device(h));
+  const EnvAfterOps* o = monsoon_env_after_ops();
+  o->launch(h->after_grid, o->lds_bytes, h->stream, h->b, *out, h->env_n, max_after);
+  HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
 }
 

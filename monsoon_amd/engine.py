@@ -212,6 +212,11 @@ class BatchEngine:
         """monsoon_env_step_dev on n bytes of device memory at actions_ptr (asynchronous on the handle's stream)."""
         self._ck(self.lib.monsoon_env_step_dev(self.h, ctypes.c_void_p(actions_ptr)), "monsoon_env_step_dev")
 
+    def env_afterstates_dev(self, after, max_after):
+        """monsoon_env_afterstates_dev: after = _lib.EnvAfter of device pointers with max_after entries per slot
+        (asynchronous on the handle's stream; nothing of the handle changes)."""
+        self._ck(self.lib.monsoon_env_afterstates_dev(self.h, ctypes.byref(after), int(max_after)), "monsoon_env_afterstates_dev")
+
     def stream_ptr(self):
         """The hipStream_t the handle launches on (monsoon_stream), as an integer."""
         return self.lib.monsoon_stream(self.h) or 0

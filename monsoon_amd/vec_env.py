@@ -11,7 +11,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import EnvConfig, EnvViews, MonsoonError
+from ._lib import EnvAfter, EnvConfig, EnvViews, MonsoonError
 from .engine import BatchEngine
 
 OPPONENTS = {"none": 0, "expert": 1, "heuristic": 2}
@@ -20,6 +20,34 @@ OPPONENTS = {"none": 0, "expert": 1, "heuristic": 2}
 _VIEWS = (("obs", (27, 5, 4), "int32"), ("legal", (156,), "bool"), ("obs_raises", (), "bool"), ("to_play", (), "uint8"),
           ("reward", (), "int8"), ("done", (), "bool"), ("winner", (), "int8"), ("truncated", (), "bool"), ("fault", (), "uint8"),
           ("illegal", (), "bool"), ("episode", (), "int32"), ("final_hash", (), "int64"))
+
+# name -> (shape behind [n], with K = max_after; torch dtype name); the order of monsoon_env_after
+_AFTER = (("n_legal", (), "int32"), ("action", ("K",), "uint8"), ("status", ("K",), "uint8"), ("reward", ("K",), "int8"),
+          ("winner", ("K",), "int8"), ("features", ("K", 10), "float64"), ("obs", ("K", 27, 5, 4), "int32"),
+          ("before_features", (10,), "float64"))
+
+
+def select_actions(after, values):
+    """The actions for VecEnv.step from a value per afterstate: values [n][K] (any real dtype) over the dict that
+    VecEnv.afterstates returned -> uint8 [n].  Per slot the first maximum over the entries that exist (k < min(n_legal, K))
+    and whose look-ahead raised nothing (status == 0); 155 (PASS, always accepted) where no entry is left; 255 (the slot is
+    left alone, its pending end is reported by the step) where n_legal == 0.  A NaN value counts as -inf: its entry is taken
+    only where no entry of the slot has a number.  Pure torch: works on CPU tensors too."""
+    import torch
+    action, status, n_legal = after["action"], after["status"], after["n_legal"]
+    n, k = action.shape
+    if values.shape != (n, k):
+        raise ValueError(f"values must be [{n}][{k}], got {tuple(values.shape)}")
+    ok = (torch.arange(k, device=action.device)[None, :] < n_legal[:, None]) & (status == 0)
+    # first maximum: among the entries equal to the row's maximum, the lowest k (argmax's tie rule is not specified)
+    v = values.to(torch.float64)
+    v = torch.where(ok & ~torch.isnan(v), v, torch.full_like(v, float("-inf")))   # a NaN value ranks below every number
+    best = ok & (v == v.max(dim=1, keepdim=True).values)
+    idx = torch.arange(k, device=action.device)[None, :].expand(n, k)
+    first = torch.where(best, idx, torch.full_like(idx, k)).min(dim=1).values.clamp(max=k - 1)
+    out = action.gather(1, first[:, None])[:, 0]
+    out = torch.where(best.any(dim=1), out, torch.full_like(out, 155))
+    return torch.where(n_legal == 0, torch.full_like(out, 255), out)
 
 
 class VecEnv:
@@ -36,6 +64,7 @@ class VecEnv:
         self.n = 0
         self.views = None
         self._heuristic = False   # an opponent-2 env is loaded
+        self._after = {}          # obs -> ((n, K), tensors, _lib.EnvAfter): the latest shape per obs flag, reused until it changes
 
     def close(self):
         if self.engine is not None:
@@ -163,9 +192,47 @@ class VecEnv:
             cur.wait_stream(env)
         return self.views
 
+    def afterstates(self, max_after=64, obs=True):
+        """The successor of every legal action of every slot's current state (monsoon_env_afterstates_dev): one launch on
+        the env's stream that changes nothing of the env.  Returns a dict of CUDA tensors with K = max_after entries per
+        slot: n_legal [n] int32 (the full count, also beyond K), action / status [n][K] uint8, reward / winner [n][K] int8,
+        features [n][K][10] float64, obs [n][K][27][5][4] int32 (obs=True only: 2 160 bytes per entry), before_features
+        [n][10] float64.  Entry k is the k-th legal action in ascending order; entries k >= min(n_legal, K) hold action 255
+        and are otherwise stale, entries with status != 0 have no features / obs (include/monsoon.h).  The tensors are
+        allocated on the first call per (n, max_after, obs) and overwritten in place by every later one (a later call
+        allocates nothing and can be captured).  One set is kept per obs flag: a call with another max_after, or after a
+        reset to another n, replaces it, and the dict returned before must no longer be used.  Stream ordering as in step."""
+        import torch
+        if self.views is None:
+            raise MonsoonError("VecEnv.afterstates before reset")
+        if not isinstance(max_after, int) or not 1 <= max_after <= 156:
+            raise ValueError("max_after must be an integer in 1..156")
+        obs = bool(obs)
+        if obs not in self._after or self._after[obs][0] != (self.n, max_after):
+            # one set per obs flag: a call with another n or max_after replaces it (9.1 GB at 65 536 slots, K = 64 with obs)
+            self._after.pop(obs, None)
+            dev = torch.device("cuda", self.device)
+            t = {}
+            for name, shape, dt in _AFTER:
+                if name == "obs" and not obs:
+                    continue
+                shape = tuple(max_after if d == "K" else d for d in shape)
+                t[name] = torch.zeros((self.n,) + shape, dtype=getattr(torch, dt), device=dev)
+            t["action"].fill_(255)
+            self._after[obs] = ((self.n, max_after), t, EnvAfter(**{name: x.data_ptr() for name, x in t.items()}))
+        _, tensors, struct = self._after[obs]
+        cur = torch.cuda.current_stream(self.device)
+        env = self.stream
+        if cur.cuda_stream != env.cuda_stream:
+            env.wait_stream(cur)   # the tensors may still be read by work queued on torch's stream
+        self.engine.env_afterstates_dev(struct, max_after)
+        if cur.cuda_stream != env.cuda_stream:
+            cur.wait_stream(env)
+        return tensors
+
     def state_hash(self):
         """monsoon_state_hash of every slot's current state (synchronises)."""
         return self.engine.state_hash()
 
 
-__all__ = ["VecEnv", "OPPONENTS", "MonsoonError"]
+__all__ = ["VecEnv", "OPPONENTS", "MonsoonError", "select_actions"]
