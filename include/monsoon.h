@@ -63,6 +63,8 @@ typedef struct {
 int monsoon_create(const monsoon_config* cfg, monsoon_t** out);
 void monsoon_destroy(monsoon_t* h);
 const char* monsoon_last_error(monsoon_t* h);   /* h may be NULL: last create() error */
+/* bits 0-15: the ABI generation (3); bits 16 / 17: the record build (extended / large extended); bits 24-31: the
+ * generation's revision, raised when calls are added (1: monsoon_env_save_dev / monsoon_env_load_dev) */
 int monsoon_version(void);
 /* the hot-kernel variant the handle runs (any pointer may be NULL) */
 int monsoon_variant(monsoon_t* h, int32_t* lanes_per_game, int32_t* waves_per_simd);
@@ -374,6 +376,56 @@ typedef struct {            /* caller-owned DEVICE buffers; K = max_after; any m
 } monsoon_env_after;
 
 int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int32_t max_after);   /* 1..156 */
+
+/* Saving and restoring slots on the device (snapshot / fork): what a search deeper than one ply needs -- keep a state, put
+ * it back into a slot, or into many slots at once -- without a host round trip.  (monsoon_state_save / monsoon_state_load
+ * move one game per call through host memory, synchronise, and know nothing of the env's own per-slot state.)
+ *
+ * An ENTRY is monsoon_env_entry_bytes() of caller-owned DEVICE memory (a multiple of 16; 8 320 on the standard record)
+ * and holds everything that makes the slot's future a function of the actions it is given: a 16-byte header (a magic
+ * value, monsoon_version(), the record's size in words, the slot's episode count), the slot's bookkeeping row, the 24 deck
+ * bytes of its current episode, its record, and its stream (the raw state and both resident blocks).  entries_dev is an
+ * array of entries, 16-byte aligned.
+ *
+ * An entry does NOT hold the slot's configuration: the loading env's seed0[dst], seed_stride, opponent kind, agent_side,
+ * max_steps, pool and -- with opponent 2 -- weight table and row of slot dst apply.  Of the bookkeeping row only the
+ * episode's own fields are loaded (result, fault, last action, flags, committed steps, stream cursor); the weight rows p1 /
+ * p2 and the schedule index belong to the handle (the env's opponent 2 never reads them: it plays the row
+ * monsoon_env_set_opponents gave slot dst), and the row's look-ahead statistics stay the destination's.  The statistics
+ * counters (monsoon_get_stats, monsoon_debug_counters words 6 / 7 / 16) are neither saved nor restored.
+ *
+ * What follows:
+ *  - Loading an entry into the slot it came from is a rewind: every later step reproduces the first run bit for bit, for
+ *    ever (the same actions given).
+ *  - Loading it into another slot reproduces the source until that episode ends; the next episode then follows the
+ *    destination's seed schedule with the carried episode count k: seed0[dst] + k * seed_stride.
+ *  - A slot saved with an end pending (an episode that ended before the agent could act) is restored with it pending: the
+ *    next step reports it.
+ *  - Entries are plain device bytes: they can be copied, kept and loaded into any handle of the same record build and
+ *    library version.  Nothing else is promised: an entry of another build or version, or a zero-filled one, never loads.
+ *
+ * monsoon_env_save_dev: entry j receives slot slots_dev[j] (DEVICE int32[m]; NULL = slot j, and then m <= n).  A slot
+ * index outside [0, n) writes an entry whose header is zero.  Nothing of the handle changes.  One launch.
+ *
+ * monsoon_env_load_dev: for j < m, slot dst_dev[j] (NULL = j, and then m <= n) becomes entry src_dev[j] (NULL = j) of the
+ * n_entries at entries_dev; m <= max_games.  A pair is skipped -- the slot and its views stay untouched -- when src is
+ * outside [0, n_entries), dst is outside [0, n), or the entry's header does not match this library (magic, version, record
+ * size) or its stream cursor is out of range.  loaded_dev[j] (DEVICE bytes, may be NULL) is set to 1 when pair j was
+ * loaded and to 0 when it was skipped.  The same src may appear many times: that is the fork.  The same dst appearing
+ * twice is the caller's error: which of the entries the slot ends up with, or which mixture of them, is unspecified.
+ * After the call the views of every loaded slot read as after a step that ended nothing: obs, legal, obs_raises and
+ * to_play of the restored state; done 0, reward 0, winner -2, truncated 0, fault 0, illegal 0, final_hash 0; episode = the
+ * entry's count.  For a slot with a pending end they are what monsoon_env_reset / the step that started that episode left:
+ * the views of the state the episode ended in.  Two launches.
+ *
+ * Both are asynchronous on the handle's stream: no allocation, host copy or synchronisation, so they capture into a graph
+ * next to monsoon_env_step_dev.  MONSOON_ERR_STATE without a loaded env (all three calls); MONSOON_ERR_ARG for a NULL
+ * entries_dev, one that is not 16-byte aligned, m < 0, n_entries < 0, m > n with NULL slots_dev / dst_dev, or a load with
+ * m > max_games. */
+int monsoon_env_entry_bytes(monsoon_t* h, int32_t* out);
+int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_dev, int32_t m);
+int monsoon_env_load_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev,
+                         int32_t m, uint8_t* loaded_dev);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,10 @@ SIGNATURES = {
     "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_env_afterstates_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvAfter), ctypes.c_int32]),
+    "monsoon_env_entry_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
+    "monsoon_env_save_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "monsoon_env_load_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                            ctypes.c_void_p]),
 }
 
 

@@ -14,6 +14,8 @@
 //   k_env_init    lane per slot, marked slots only: init_game, the bot's opening turn when the agent is SECOND, then the
 //                 observation, legal bytes and to_play of the new episode's first state.  With the heuristic opponent, a
 //                 new episode that opens with the opponent is put on slot list 1, and k_env_opp / k_env_after_opp follow.
+//   k_env_view    lane per (entry, slot) pair of monsoon_env_load_dev, after the copy (k_env_load, env_snap.hip): the views
+//                 of every slot that was loaded.
 //
 // A slot's episode is over when its GameMeta.result is no longer -2 (flags b1 = truncated); k_env_init starts every
 // episode with result -2.  Nothing here synchronises with the host: the launches can be captured into a graph.  A
@@ -253,4 +255,28 @@ __global__ void __launch_bounds__(64) k_env_init(DevBuffers b, EnvDev v, int n, 
   }
   if (v.opponent == 2) env_append(v, 1, g, opp_turn);
   if (!opp_turn) env_write_state(e, v, g);
+}
+
+// After k_env_load (env_snap.hip): the views of the slots it loaded, a lane per pair j; dst null = slot j.  They read as
+// after a step that ended nothing; for a slot restored with its end pending they are what k_env_init left for it (the
+// views of the state the episode ended in: the next step reports the end).  A pair that was skipped writes nothing.
+__global__ void __launch_bounds__(64) k_env_view(DevBuffers b, EnvDev v, int m, const int32_t* dst, const uint8_t* loaded) {
+  lds_init_wtab(b.wk_ovf + (size_t)blockIdx.x * (API_LANES * OVF_WORDS));
+  if ((int)threadIdx.x >= API_LANES) return;
+  const int j = blockIdx.x * API_LANES + threadIdx.x;
+  if (j >= m || !loaded[j]) return;
+  const int g = dst ? dst[j] : j;
+  ApiEngine e;
+  api_load(b.state + (size_t)g * SW);
+  attach_rng(e, b, g, b.meta[g].rng);
+  v.mark[g] = 0;
+  v.v.done[g] = 0;
+  if (v.v.reward) v.v.reward[g] = 0;
+  if (v.v.illegal) v.v.illegal[g] = 0;
+  if (v.v.episode) v.v.episode[g] = v.episode[g];
+  if (v.v.winner) v.v.winner[g] = -2;
+  if (v.v.truncated) v.v.truncated[g] = 0;
+  if (v.v.fault) v.v.fault[g] = 0;
+  if (v.v.final_hash) v.v.final_hash[g] = 0;
+  env_write_state(e, v, g);
 }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "env_after.h"
+#include "env_snap.h"
 #include "kernels.h"
 
 using namespace msb;
@@ -669,7 +670,7 @@ struct monsoon {
   double kernel_ms = 0;
   long long kernel_launches = 0;
   // vector env (monsoon_env_reset): workspace of max_games slots, allocated once; env_on until monsoon_reset / rollout
-  uint8_t* d_env = nullptr;   // seed0 u32 | episode i32 | agent steps u32 | bot steps u32 | decks [24] | factions [2] | mark | pool [128]
+  uint8_t* d_env = nullptr;   // seed0 u32 | episode i32 | agent steps u32 | bot steps u32 | decks [24] | factions [2] | mark | pool [128] | loaded flags [cap]
   EnvDev env;
   int env_n = 0;
   bool env_on = false;
@@ -682,6 +683,8 @@ struct monsoon {
   int opp_grid = 0;           // k_env_opp's grid: resident wavefronts, at most the slots (queried at reset)
   int after_grid = 0;         // k_env_after's grid (monsoon_env_afterstates_dev), likewise
   int after_waves = 0;        // resident wavefronts of k_env_after (queried once per handle)
+  int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
+  uint8_t* d_snap_flag = nullptr;   // [cap], inside d_env: the loaded flags of monsoon_env_load_dev when the caller keeps none
   int cu_count = 0;           // compute units of the device (queried once per handle)
 };
 
@@ -737,11 +740,11 @@ extern "C" {
 
 int monsoon_version(void) {
 #if defined(MSB_EXT) && MSB_EXT == 2
-  return 0x30003;   // bits 16 + 17: the large extended record (254 entity slots)
+  return 0x1030003;   // bits 16 + 17: the large extended record (254 entity slots)
 #elif defined(MSB_EXT) && MSB_EXT
-  return 0x10003;   // bit 16: extended record
+  return 0x1010003;   // bit 16: extended record
 #else
-  return 3;
+  return 0x1000003;   // bits 0-15: the ABI generation; bits 24-31: its revision (1 = monsoon_env_save_dev / monsoon_env_load_dev)
 #endif
 }
 
@@ -1908,7 +1911,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   if (rc) return rc;
   h->env_on = false;
   const size_t cap = (size_t)h->cfg.max_games;
-  if (!h->d_env) HIP_TRY(h, hipMalloc(&h->d_env, 44 * cap + 128));
+  if (!h->d_env) HIP_TRY(h, hipMalloc(&h->d_env, 45 * cap + 128));
   EnvDev& v = h->env;
   uint8_t* base = h->d_env;
   v.v = *views;
@@ -1920,6 +1923,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   v.factions = base + 40 * cap;
   v.mark = base + 42 * cap;
   v.pool = base + 43 * cap;
+  h->d_snap_flag = base + 43 * cap + 128;
   v.pool_n = cfg->pool_n;
   v.opponent = cfg->opponent;
   v.agent_side = cfg->agent_side;
@@ -1961,6 +1965,13 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     h->after_grid = std::min(h->after_waves, n);
     rc = grow_ovf(h, (size_t)h->after_grid * o->lanes);
     if (rc) return rc;
+  }
+  if (!h->snap_blocks) {   // monsoon_env_save_dev / monsoon_env_load_dev query nothing
+    int per_cu = 0, cus = 0;
+    rc = device_cus(h, &cus);
+    if (rc) return rc;
+    HIP_TRY(h, monsoon_env_snap_ops()->occupancy(&per_cu));
+    h->snap_blocks = per_cu > 0 ? per_cu * cus : 1024;
   }
   HIP_TRY(h, hipMemcpyAsync((void*)v.seed0, seed0, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   if (decks) HIP_TRY(h, hipMemcpyAsync(v.decks, decks, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
@@ -2035,6 +2046,73 @@ int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int3
   HIP_TRY(h, bind_device(h));
   const EnvAfterOps* o = monsoon_env_after_ops();
   o->launch(h->after_grid, o->lds_bytes, h->stream, h->b, *out, h->env_n, max_after);
+  HIP_TRY(h, hipGetLastError());
+  return MONSOON_OK;
+}
+
+int monsoon_env_entry_bytes(monsoon_t* h, int32_t* out) {
+  if (!h || !out) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_entry_bytes: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  *out = monsoon_env_snap_ops()->entry_bytes;
+  return MONSOON_OK;
+}
+
+// The copy kernels' grid: a workgroup of SNAP_WAVES wavefronts takes SNAP_WAVES entries at a time; no more workgroups
+// than the GPU holds at once.
+static int snap_grid(const monsoon_t* h, int m) { return std::min((m + SNAP_WAVES - 1) / SNAP_WAVES, h->snap_blocks); }
+
+// One launch on the handle's stream: no allocation, copy or synchronisation (graph-capturable); nothing of the handle is
+// written.
+int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_dev, int32_t m) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_save_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  const char* bad = nullptr;
+  if (!entries_dev) bad = "entries_dev is NULL";
+  else if ((uintptr_t)entries_dev & 15) bad = "entries_dev must be 16-byte aligned";
+  else if (m < 0) bad = "m < 0";
+  else if (!slots_dev && m > h->env_n) bad = "m > n without slots_dev";
+  if (bad) {
+    h->err = std::string("monsoon_env_save_dev: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  if (m == 0) return MONSOON_OK;
+  HIP_TRY(h, bind_device(h));
+  monsoon_env_snap_ops()->save(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, slots_dev, m, (uint32_t)monsoon_version());
+  HIP_TRY(h, hipGetLastError());
+  return MONSOON_OK;
+}
+
+// Two launches on the handle's stream, the copy (k_env_load) and the views of the loaded slots (k_env_view): no
+// allocation, copy or synchronisation (graph-capturable).
+int monsoon_env_load_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev, int32_t m,
+                         uint8_t* loaded_dev) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_load_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  const char* bad = nullptr;
+  if (!entries_dev) bad = "entries_dev is NULL";
+  else if ((uintptr_t)entries_dev & 15) bad = "entries_dev must be 16-byte aligned";
+  else if (m < 0 || n_entries < 0) bad = "m < 0 or n_entries < 0";
+  else if (!dst_dev && m > h->env_n) bad = "m > n without dst_dev";
+  else if (m > h->cfg.max_games) bad = "m > max_games";
+  if (bad) {
+    h->err = std::string("monsoon_env_load_dev: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  if (m == 0) return MONSOON_OK;
+  HIP_TRY(h, bind_device(h));
+  uint8_t* flags = loaded_dev ? loaded_dev : h->d_snap_flag;
+  monsoon_env_snap_ops()->load(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, n_entries, src_dev, dst_dev, m, flags,
+                               (uint32_t)monsoon_version());
+  hipLaunchKernelGGL(k_env_view, dim3((m + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, m, dst_dev, flags);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
 }

@@ -217,6 +217,25 @@ class BatchEngine:
         (asynchronous on the handle's stream; nothing of the handle changes)."""
         self._ck(self.lib.monsoon_env_afterstates_dev(self.h, ctypes.byref(after), int(max_after)), "monsoon_env_afterstates_dev")
 
+    def env_entry_bytes(self):
+        """monsoon_env_entry_bytes: the size of one saved slot of this record build (needs a loaded env)."""
+        out = ctypes.c_int32()
+        self._ck(self.lib.monsoon_env_entry_bytes(self.h, ctypes.byref(out)), "monsoon_env_entry_bytes")
+        return int(out.value)
+
+    def env_save_dev(self, entries_ptr, slots_ptr, m):
+        """monsoon_env_save_dev: entry j at entries_ptr (device, 16-byte aligned) receives slot slots[j] (device int32[m] at
+        slots_ptr, 0 = slot j).  Asynchronous on the handle's stream."""
+        self._ck(self.lib.monsoon_env_save_dev(self.h, ctypes.c_void_p(entries_ptr), ctypes.c_void_p(slots_ptr or None), int(m)),
+                 "monsoon_env_save_dev")
+
+    def env_load_dev(self, entries_ptr, n_entries, src_ptr, dst_ptr, m, loaded_ptr):
+        """monsoon_env_load_dev: slot dst[j] becomes entry src[j] for j < m (device int32[m] each, 0 = j); loaded_ptr =
+        m device bytes or 0.  Asynchronous on the handle's stream."""
+        self._ck(self.lib.monsoon_env_load_dev(self.h, ctypes.c_void_p(entries_ptr), int(n_entries), ctypes.c_void_p(src_ptr or None),
+                                               ctypes.c_void_p(dst_ptr or None), int(m), ctypes.c_void_p(loaded_ptr or None)),
+                 "monsoon_env_load_dev")
+
     def stream_ptr(self):
         """The hipStream_t the handle launches on (monsoon_stream), as an integer."""
         return self.lib.monsoon_stream(self.h) or 0

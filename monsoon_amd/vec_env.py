@@ -5,6 +5,7 @@ legal_actions, reset, expert_agent as the opponent), each an endless sequence of
 `step` is three kernel launches on the handle's stream -- legality check, step, the scripted bot's turn, end of episode,
 re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.  The
 opponent can also be the reference's HeuristicAgent with GA weights ("heuristic": seven launches per step).
+`snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device.
 torch is used for device memory and stream ordering only; there is no CPU fallback.
 """
 import ctypes
@@ -50,10 +51,31 @@ def select_actions(after, values):
     return torch.where(n_legal == 0, torch.full_like(out, 255), out)
 
 
+class EnvSnapshot:
+    """Saved slots of a VecEnv (VecEnv.snapshot): data is a uint8 CUDA tensor [cap][entry_bytes], count the entries in
+    use (the first `count` rows), extended the record build that wrote them, entry_bytes that build's entry size.  The
+    entries are plain device bytes (include/monsoon.h, monsoon_env_save_dev): they load into any VecEnv of the same record
+    build and library version."""
+
+    def __init__(self, data, count, extended, entry_bytes):
+        self.data = data
+        self.count = int(count)
+        self.extended = int(extended)
+        self.entry_bytes = int(entry_bytes)
+
+    @property
+    def capacity(self):
+        return int(self.data.shape[0])
+
+    def __len__(self):
+        return self.count
+
+
 class VecEnv:
     """n game slots on one GPU.  reset() loads episode 0 of every slot; step(actions) advances every slot by the agent's
-    action (and the bot's answer), restarts finished episodes and returns the view tensors.  See include/monsoon.h
-    (monsoon_env_*) for the contract and INTEGRATION.md for a trainer loop."""
+    action (and the bot's answer), restarts finished episodes and returns the view tensors.  snapshot() / restore() save
+    slots and load them back, also one entry into many slots.  See include/monsoon.h (monsoon_env_*) for the contract and
+    INTEGRATION.md for a trainer loop."""
 
     def __init__(self, max_slots, device=0, extended=0, lanes_per_game=0):
         """extended = 0 / 1 / 2 selects the record build (1: decks holding ua20 / b005).  Raises MonsoonError when no
@@ -230,9 +252,108 @@ class VecEnv:
             cur.wait_stream(env)
         return tensors
 
+    @property
+    def entry_bytes(self):
+        """The size of one saved slot (monsoon_env_entry_bytes); needs reset() first."""
+        if self.views is None:
+            raise MonsoonError("VecEnv.entry_bytes before reset")
+        return self.engine.env_entry_bytes()
+
+    def _index(self, t, name, m=None):
+        """An int32 CUDA tensor [m] on this env's device (m None: any length) -> (contiguous tensor, length)."""
+        import torch
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.device or t.dim() != 1
+                or (m is not None and t.shape[0] != m)):
+            raise ValueError(f"{name} must be an int32 CUDA tensor of shape ({'m' if m is None else m},) on device {self.device}")
+        return t.contiguous(), int(t.shape[0])
+
+    def _on_env_stream(self, call):
+        import torch
+        cur = torch.cuda.current_stream(self.device)
+        env = self.stream
+        if cur.cuda_stream != env.cuda_stream:
+            env.wait_stream(cur)   # the index tensors were written, the entries may still be read, on torch's stream
+        call()
+        if cur.cuda_stream != env.cuda_stream:
+            cur.wait_stream(env)
+
+    def snapshot(self, slots=None, out=None):
+        """Save slots (monsoon_env_save_dev): entry j = slot slots[j] (an int32 CUDA tensor [m]; None = every slot, in
+        order).  Returns an EnvSnapshot of m entries.  out = an earlier snapshot of this env's build with room for m
+        entries: it is overwritten and returned, nothing is allocated and the call can be captured.  A slot index outside
+        [0, n) leaves an entry that never loads.  One launch on the env's stream that changes nothing of the env; stream
+        ordering as in step."""
+        import torch
+        if self.views is None:
+            raise MonsoonError("VecEnv.snapshot before reset")
+        size = self.entry_bytes
+        m = self.n
+        if slots is not None:
+            slots, m = self._index(slots, "slots")
+        if out is None:
+            data = torch.zeros((m, size), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            out = EnvSnapshot(data, m, int(self.extended), size)
+        else:
+            self._check_snapshot(out)
+            if out.capacity < m:
+                raise ValueError(f"out holds {out.capacity} entries, {m} are to be saved")
+            out.count = m
+        if m:
+            self._on_env_stream(lambda: self.engine.env_save_dev(out.data.data_ptr(), 0 if slots is None else slots.data_ptr(), m))
+        return out
+
+    def _check_snapshot(self, snap):
+        import torch
+        if not isinstance(snap, EnvSnapshot):
+            raise ValueError("not an EnvSnapshot")
+        if snap.extended != int(self.extended) or snap.entry_bytes != self.entry_bytes:
+            raise ValueError(f"the snapshot is of record build {snap.extended} with {snap.entry_bytes}-byte entries, this env of build "
+                             f"{int(self.extended)} with {self.entry_bytes}")
+        d = snap.data
+        if (not isinstance(d, torch.Tensor) or d.dtype != torch.uint8 or not d.is_cuda or d.device.index != self.device or d.dim() != 2
+                or d.shape[1] != snap.entry_bytes or not d.is_contiguous() or d.data_ptr() % 16 or not 0 <= snap.count <= d.shape[0]):
+            raise ValueError(f"snapshot data must be a contiguous uint8 CUDA tensor [cap][{snap.entry_bytes}] on device {self.device}")
+
+    def restore(self, snap, src=None, dst=None, loaded=None):
+        """Load saved slots (monsoon_env_load_dev): for every j, slot dst[j] becomes entry src[j] of snap (int32 CUDA
+        tensors of one length m; None = j: without dst m <= n, without both m = len(snap)).  The same src may appear many
+        times -- the fork; the same dst twice is an error of the caller with an unspecified result.  A pair whose src is
+        outside [0, len(snap)) or whose dst is outside [0, n), or whose entry was never written, is skipped: the slot and
+        its views stay untouched.  loaded (a uint8 or bool CUDA tensor [m]) receives 1 per loaded pair, 0 per skipped one.
+        A slot loaded from its own entry replays its future bit for bit; loaded elsewhere it follows the source until
+        the episode ends and the destination's seed schedule after it, and plays the destination's opponent row.  Returns
+        the view tensors: those of the loaded slots read as after a step that ended nothing (done 0, reward 0, winner -2,
+        episode = the entry's count) in the restored state.  Two launches on the env's stream, no allocation: the call can be
+        captured.  Stream ordering as in step.  ValueError for a snapshot of another build or entry size and for tensors
+        of wrong dtype, device or shape; MonsoonError before reset."""
+        import torch
+        if self.views is None:
+            raise MonsoonError("VecEnv.restore before reset")
+        self._check_snapshot(snap)
+        m = None
+        if src is not None:
+            src, m = self._index(src, "src")
+        if dst is not None:
+            dst, m = self._index(dst, "dst", m)
+        if m is None:
+            m = snap.count
+        if dst is None and m > self.n:
+            raise ValueError(f"{m} entries into {self.n} slots: give dst")
+        if m > self.engine.max_games:
+            raise ValueError(f"at most max_slots = {self.engine.max_games} pairs per call")
+        if loaded is not None:
+            if (not isinstance(loaded, torch.Tensor) or loaded.dtype not in (torch.uint8, torch.bool) or not loaded.is_cuda
+                    or loaded.device.index != self.device or loaded.shape != (m,) or not loaded.is_contiguous()):
+                raise ValueError(f"loaded must be a contiguous uint8 or bool CUDA tensor of shape ({m},) on device {self.device}")
+        if m:
+            self._on_env_stream(lambda: self.engine.env_load_dev(snap.data.data_ptr(), snap.count, 0 if src is None else src.data_ptr(),
+                                                                 0 if dst is None else dst.data_ptr(), m,
+                                                                 0 if loaded is None else loaded.data_ptr()))
+        return self.views
+
     def state_hash(self):
         """monsoon_state_hash of every slot's current state (synchronises)."""
         return self.engine.state_hash()
 
 
-__all__ = ["VecEnv", "OPPONENTS", "MonsoonError", "select_actions"]
+__all__ = ["VecEnv", "EnvSnapshot", "OPPONENTS", "MonsoonError", "select_actions"]
