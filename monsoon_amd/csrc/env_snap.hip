@@ -3,7 +3,8 @@
 // granules, lane l taking granules l, l + 64, ... so that every load and every store of the wave covers 1 024
 // consecutive bytes on the slot side and on the entry side (at the seams between record, rng_mt and rng_out one
 // instruction covers the end of one row and the start of the next).  A pass loads up to SNAP_PASS granules per lane
-// before it stores the first, so a wave has a whole standard entry in flight.  The kernels touch no rules code: one
+// before it stores the first, so a wave has a whole standard or extended entry in flight; the large entry's body (989
+// granules) takes a second pass of 349, whose sixth load is live on 29 lanes.  The kernels touch no rules code: one
 // instantiation per record build because SW and with it the layout differ.
 #include "env_snap.h"
 
@@ -12,7 +13,7 @@ using namespace msbk;
 namespace {
 
 static_assert(SW * 4 == STATE_BYTES, "the record's stride is the record");
-constexpr int SNAP_PASS = 10;   // granules per lane and pass: 9 cover the standard record's body (515), 10 the extended one's
+constexpr int SNAP_PASS = 10;   // granules per lane and pass: 9 cover the standard body (515), 10 the extended one (618); large: 2 passes
 
 // Body granule i of slot g: the record, then rng_mt, then rng_out.
 __device__ MSB_INL u32x4* slot_granule(const DevBuffers& b, const int g, const int i) {

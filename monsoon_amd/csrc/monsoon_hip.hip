@@ -637,6 +637,7 @@ struct monsoon {
   const VariantOps* var = nullptr;   // hot-kernel variant: candidate lanes per game, waves per SIMD
   int parity = 0;     // which of b.pop the next k_decide launch uses
   size_t ovf_lanes = 0;   // stepping lanes b.wk_ovf has room for (OVF_WORDS words each)
+  std::vector<uint32_t*> ovf_retired;   // earlier, smaller b.wk_ovf blocks: a captured launch may still point to one (grow_ovf)
   unsigned long long st_acc[ST_N], st_base[ST_N];   // statistics: totals of earlier batches, baseline of the loaded one
   int grid_waves = 0; // persistent grid size of k_decide (resident wavefronts), 0 = not yet queried
   int vs_grid_waves = 0;   // ... of k_play_vs (monsoon_rollout_vs_expert), 0 = not yet queried
@@ -767,6 +768,7 @@ void monsoon_destroy(monsoon_t* h) {
                   h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w};
   for (void* p : ptrs)
     if (p) hipFree(p);
+  for (uint32_t* p : h->ovf_retired) hipFree(p);
   for (auto& pr : h->ev_pool) {
     hipEventDestroy(pr.first);
     hipEventDestroy(pr.second);
@@ -1441,6 +1443,23 @@ static int drain_timing(monsoon_t* h) {
   return MONSOON_OK;
 }
 
+// Work-stack overflow blocks for `lanes` stepping lanes (grid x candidate lanes of a kernel): grown, never shrunk.  The
+// block it replaces is kept until monsoon_destroy, not freed: DevBuffers travels by value, so an env step captured into a
+// graph holds the wk_ovf of its capture, and that block still has room for the grid that was captured.  (The handle
+// cannot know whether a capture exists, and sizing for the largest grid any later rollout may choose would cost every
+// env hundreds of MB it may never use.)  Growth at least doubles the buffer, so the kept blocks together stay smaller than
+// the live one however the requests creep upward.  No synchronisation: nothing is freed under work in flight.
+static int grow_ovf(monsoon_t* h, size_t lanes) {
+  if (lanes <= h->ovf_lanes) return MONSOON_OK;
+  lanes = std::max(lanes, 2 * h->ovf_lanes);
+  uint32_t* grown = nullptr;
+  HIP_TRY(h, hipMalloc(&grown, lanes * OVF_WORDS * 4));
+  if (h->b.wk_ovf) h->ovf_retired.push_back(h->b.wk_ovf);
+  h->b.wk_ovf = grown;
+  h->ovf_lanes = lanes;
+  return MONSOON_OK;
+}
+
 static const int g_persistent = getenv("MONSOON_PERSIST") ? atoi(getenv("MONSOON_PERSIST")) : 1;
 static const int g_lds_pad = getenv("MONSOON_LDS_PAD") ? atoi(getenv("MONSOON_LDS_PAD")) : 0;   // occupancy experiments only
 
@@ -1473,12 +1492,9 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   // the persistent form needs a wavefront for every one of its POP_PARTS ranges
   const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
   if (!pers) grid = n;   // a wavefront per game
-  if ((size_t)grid * v->lanes > h->ovf_lanes) {   // work-stack overflow blocks for every workgroup of this grid
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipFree(h->b.wk_ovf));
-    h->b.wk_ovf = nullptr;
-    h->ovf_lanes = (size_t)grid * v->lanes;
-    HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
+  {   // work-stack overflow blocks for every workgroup of this grid
+    int rc = grow_ovf(h, (size_t)grid * v->lanes);
+    if (rc) return rc;
   }
   v->play(grid, lds, h->stream, h->b, n, max_turns, rounds, write_scores, pers, h->parity);
   // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
@@ -1818,17 +1834,6 @@ static int device_cus(monsoon_t* h, int* out) {
     h->cu_count = prop.multiProcessorCount;
   }
   *out = h->cu_count;
-  return MONSOON_OK;
-}
-
-// Work-stack overflow blocks for `lanes` stepping lanes (grid x candidate lanes of a kernel): grown, never shrunk.
-static int grow_ovf(monsoon_t* h, size_t lanes) {
-  if (lanes <= h->ovf_lanes) return MONSOON_OK;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipFree(h->b.wk_ovf));
-  h->b.wk_ovf = nullptr;
-  h->ovf_lanes = lanes;
-  HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
   return MONSOON_OK;
 }
 

@@ -53,7 +53,8 @@ class AfterstatesModel:
         f0, f1 = (int(m.factions[j, 0]), int(m.factions[j, 1])) if k == 0 else (0, 0)
         orc.reset(0, m.seed(j), m.decks[j, 0], m.decks[j, 1], f0, f1)
         for a in self.history.of(j, k):
-            if m.opponent and orc.to_play(0) != m.agent_side:   # the bot's step: its expert_action drew from the stream
+            # the scripted bot's step: its expert_action drew from the stream (the heuristic opponent, 2, decides on copies)
+            if m.opponent == 1 and orc.to_play(0) != m.agent_side:
                 ea, _ = orc.expert_action(0)
                 assert ea == a, (j, ea, a)
             orc.step(0, a)

@@ -16,11 +16,55 @@ bookkeeping is a LINEAGE per tracked slot: the events that lead to its state,
 and a snapshot is a list of lineages.  A restore replays the entry's lineage on a fresh one-slot model and appends the
 move.  A spec is the keyword dictionary of VecEnvModel (seed0, decks, factions, opponent, agent_side, seed_stride,
 max_steps, pool, extended), plus opponent_weights / opponent_rows for the heuristic opponent.
+
+The bytes of an entry (monsoon_amd/csrc/env_snap.h) are modelled too, for all three record builds: entry_layout gives the
+sizes from the build's record size, build_entry puts an entry together from what the handle exports by another path
+(monsoon_state_save: the meta row, the record and the stream of one slot).
 """
 import numpy as np
 
 from vec_env_heuristic_model import HeuristicVecEnvModel
 from vec_env_model import VecEnvModel
+
+
+SNAP_MAGIC = 0x50414E53                     # "SNAP"
+HEAD_BYTES, META_BYTES, DECK_BYTES = 16, 32, 24
+BODY_AT = 80                                # header, meta row, 24 deck bytes and 8 bytes of zero
+MT_BYTES, OUT_BYTES = 624 * 4, 2 * 624 * 4  # the raw stream state, the two tempered blocks
+PASS_GRANULES = 64 * 10                     # the copy kernels move 64 lanes x SNAP_PASS granules per pass
+BLOB_HEAD = 8                               # monsoon_state_save: {u32 magic, u32 record bytes}, meta row, record, stream
+
+
+def record_bytes(extended):
+    """The record size of a build, from the size of its state blob (a host function of the library: no GPU needed)."""
+    from monsoon_amd import _lib
+    return int(_lib.load(int(extended)).monsoon_state_blob_bytes()) - BLOB_HEAD - META_BYTES - MT_BYTES - OUT_BYTES
+
+
+def entry_layout(extended):
+    """Sizes of one saved slot of record build 0 / 1 / 2: entry bytes, body granules (record + rng_mt + rng_out), the byte
+    offsets of the two seams inside the entry, the passes of the copy loop and the granules of its last pass."""
+    rec = record_bytes(extended)
+    assert rec % 16 == 0
+    body = (rec + MT_BYTES + OUT_BYTES) // 16
+    passes = -(-body // PASS_GRANULES)
+    return dict(record_bytes=rec, entry_bytes=BODY_AT + 16 * body, body_granules=body, mt_at=BODY_AT + rec,
+                out_at=BODY_AT + rec + MT_BYTES, passes=passes, tail_granules=body - (passes - 1) * PASS_GRANULES)
+
+
+def build_entry(extended, version, episode, decks, blob):
+    """The entry monsoon_env_save_dev writes for a slot whose monsoon_state_save blob is `blob`, whose episode count is
+    `episode` and whose current decks are `decks` ([2][12] uint8): header {magic, monsoon_version(), record words, episode},
+    the meta row, the decks and 8 zero bytes, then record, rng_mt and rng_out as they sit in the blob."""
+    lay = entry_layout(extended)
+    blob = np.frombuffer(bytes(blob), dtype=np.uint8)
+    assert len(blob) == BLOB_HEAD + META_BYTES + lay["record_bytes"] + MT_BYTES + OUT_BYTES
+    assert int(blob[4:8].view("<u4")[0]) == lay["record_bytes"]
+    head = np.array([SNAP_MAGIC, int(version) & 0xFFFFFFFF, lay["record_bytes"] // 4, int(episode) & 0xFFFFFFFF], dtype="<u4")
+    out = np.concatenate([head.view(np.uint8), blob[BLOB_HEAD:BLOB_HEAD + META_BYTES], np.asarray(decks, dtype=np.uint8).reshape(24),
+                          np.zeros(8, dtype=np.uint8), blob[BLOB_HEAD + META_BYTES:]])
+    assert len(out) == lay["entry_bytes"]
+    return out
 
 
 def _fresh(spec, slot):

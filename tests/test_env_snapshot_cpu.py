@@ -7,7 +7,7 @@ import inspect
 import numpy as np
 import pytest
 
-from env_snapshot_model import EnvSnapshotModel, replay
+from env_snapshot_model import EnvSnapshotModel, build_entry, entry_layout, replay
 from monsoon_amd.cards import deck_indices
 from test_abi import header_functions
 from vec_env_model import VecEnvModel
@@ -108,3 +108,36 @@ def test_helper_fork_follows_the_source_then_the_destinations_schedule():
     assert m1.seed(0) == int(spec["seed0"][1]) + n and m4.seed(0) == int(spec["seed0"][4]) + n
     assert np.array_equal(m4.decks[0], spec["decks"][1]) and not np.array_equal(spec["decks"][4], spec["decks"][1])
     assert helper.hashes()[4] != helper.hashes()[1]
+
+
+# build -> (body granules = record + rng_mt + rng_out, passes of the copy loop, granules of its last pass): the table of
+# monsoon_amd/csrc/env_snap.hip's SNAP_PASS (64 x 10 granules per pass)
+ENTRY_TABLE = {0: (47 + 156 + 312, 1, 515), 1: (150 + 156 + 312, 1, 618), 2: (521 + 156 + 312, 2, 349)}
+
+
+@pytest.mark.parametrize("ext", [0, 1, 2])
+def test_entry_layout_of_every_build(ext):
+    """The entry model derives its sizes from the build's record size; they are the documented ones, and only the large
+    entry takes a second pass of the copy loop, whose sixth load of 64 granules is live on 29 lanes."""
+    from monsoon_amd import _lib
+    lay = entry_layout(ext)
+    body, passes, tail = ENTRY_TABLE[ext]
+    assert (lay["body_granules"], lay["passes"], lay["tail_granules"]) == (body, passes, tail)
+    assert lay["entry_bytes"] == 80 + 16 * body and lay["entry_bytes"] % 16 == 0
+    assert lay["record_bytes"] // 16 == body - 156 - 312
+    assert lay["mt_at"] == 80 + lay["record_bytes"] and lay["out_at"] == lay["mt_at"] + 2496 and lay["out_at"] + 4992 == lay["entry_bytes"]
+    if ext == 0:
+        assert lay["entry_bytes"] == 8320
+    if ext == 2:
+        assert lay["record_bytes"] == 8336 and tail - 5 * 64 == 29
+    # build_entry puts the parts where the layout says
+    blob_bytes = int(_lib.load(ext).monsoon_state_blob_bytes())
+    blob = (np.arange(blob_bytes) % 251).astype(np.uint8)
+    blob[4:8] = np.array([lay["record_bytes"]], dtype="<u4").view(np.uint8)
+    decks = np.arange(24, dtype=np.uint8).reshape(2, 12) + 100
+    e = build_entry(ext, 0x01030003, 7, decks, blob)
+    assert len(e) == lay["entry_bytes"]
+    assert e[:16].view("<u4").tolist() == [0x50414E53, 0x01030003, lay["record_bytes"] // 4, 7]
+    assert np.array_equal(e[16:48], blob[8:40]) and np.array_equal(e[48:72], decks.reshape(24)) and not e[72:80].any()
+    assert np.array_equal(e[80:lay["mt_at"]], blob[40:40 + lay["record_bytes"]])
+    assert np.array_equal(e[lay["mt_at"]:], blob[40 + lay["record_bytes"]:])

@@ -12,11 +12,12 @@ OPP_BOUND = 64
 class HeuristicVecEnvModel(VecEnvModel):
     """opponent_weights: [k][10]; opponent_rows: [n] over the WHOLE env (None = row 0), taken for the model's slots."""
 
-    def __init__(self, seed0, opponent_weights, opponent_rows=None, slots=None, **kw):
+    def __init__(self, seed0, opponent_weights, opponent_rows=None, slots=None, on_decide=None, **kw):
         n_all = len(np.asarray(seed0))
         sl = np.arange(n_all) if slots is None else np.asarray(slots, dtype=np.int64)
         self.set_opponents(opponent_weights, opponent_rows, sl)
         self.opp_bound_turns = []   # the opponent's decisions in every turn the guard ended
+        self.on_decide = on_decide  # on_decide(j, action, legal mask words) after every decision of the opponent
         super().__init__(seed0, opponent=2, slots=slots, **kw)
 
     def set_opponents(self, weights, rows=None, slots=None):
@@ -32,7 +33,9 @@ class HeuristicVecEnvModel(VecEnvModel):
         for _ in range(OPP_BOUND):
             if self.orc.to_play(j) == self.agent_side:
                 return
-            a, _, _ = self.orc.decide(j, w)
+            a, _, mask = self.orc.decide(j, w)
+            if self.on_decide is not None:
+                self.on_decide(j, int(a), mask)
             turn.append(int(a))
             fs, _, _ = self.orc.step(j, a)
             if self._after_step(j, a, fs):
