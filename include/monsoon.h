@@ -253,7 +253,13 @@ int monsoon_upload_weights(monsoon_t* h, const double* weights, int32_t n_indivi
 int monsoon_assign_players(monsoon_t* h, const int32_t* p1, const int32_t* p2);   /* [n] indices */
 int monsoon_decide_round_dev(monsoon_t* h);   /* asynchronous on the handle's stream */
 /* `rounds` decisions of every loaded game in one launch (evo/fitness.py:193-211, a slice of the _play_game loop): a
- * game's record stays on chip from its first to its last decision of the call.  Asynchronous like the call above. */
+ * game's record stays on chip from its first to its last decision of the call.  Asynchronous like the call above.
+ *
+ * Both calls may play the second half of a large batch on a second stream of the handle, so that the next call's first
+ * half fills the GPU while this call's second half runs out of games (MONSOON_SPLIT=0 in the environment, read per
+ * call: always one launch on the handle's stream).  Every other entry point, monsoon_sync and monsoon_stream included,
+ * first makes the handle's stream wait for that half: a caller that orders work of its own behind these two calls
+ * fetches monsoon_stream after them, or calls monsoon_sync. */
 int monsoon_play_rounds_dev(monsoon_t* h, int32_t rounds);
 int monsoon_sync(monsoon_t* h);
 

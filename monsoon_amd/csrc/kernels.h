@@ -70,7 +70,7 @@ struct DevBuffers {
   unsigned long long* stats;  // [8]: lookahead, decisions, finished, faults, capacity_faults, look-ahead capacity faults
   double* scores;      // [cap][156] or null
   double* best;        // [cap]
-  int* pop;            // [2][POP_PARTS * POP_STRIDE] game-index counters of the persistent k_decide, alternating between launches
+  int* pop;            // [SPLIT_MAX][2][POP_PARTS * POP_STRIDE] game-index counters of the persistent k_decide: per sub-batch of a split call (k_play) a pair alternating between launches
   unsigned long long* prof;   // [cap][..] phase cycles, scope cycles, scope calls (profiling build), profiling build only (else null)
   uint32_t* wk_ovf;    // overflow blocks of the rules core's work stack: [workgroup][SK_CAP - SKW][lanes stepping games in it]
 };
@@ -628,21 +628,25 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // other one is cleared for the next launch.  persistent = 0: one workgroup per game.  The host launches the
 // persistent form only with at least POP_PARTS workgroups (a range without a wavefront would never be played).
 // rounds = 1 is one decision round over the batch; rounds > max_turns plays every game to its end (rollouts).
-constexpr int POP_PARTS = 8, POP_STRIDE = 32;
+// The launch plays games [g0, g0 + n).  A call split into sub-batches (monsoon_hip.hip launch_play) is SPLIT_MAX or
+// fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
+// overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
+constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
 template <int U, int WPE>
-__global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent, int parity) {
+__global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent, int parity,
+                                                  int g0, int half) {
   const int lane = threadIdx.x;
-  lds_init_wtab(b.wk_ovf + (size_t)blockIdx.x * (U * OVF_WORDS));
+  lds_init_wtab(b.wk_ovf + ((size_t)half * gridDim.x + blockIdx.x) * (U * OVF_WORDS));
   // one body for both forms (play_game is the whole rules core, inlined once): the non-persistent form is a "range" of
   // one game that is never refilled
-  int* mine = b.pop + parity * POP_PARTS * POP_STRIDE;
-  int* other = b.pop + (parity ^ 1) * POP_PARTS * POP_STRIDE;
+  int* mine = b.pop + (2 * half + parity) * POP_PARTS * POP_STRIDE;
+  int* other = b.pop + (2 * half + (parity ^ 1)) * POP_PARTS * POP_STRIDE;
   if (persistent && blockIdx.x == 0 && lane < POP_PARTS) other[lane * POP_STRIDE] = 0;
   const int part = blockIdx.x % POP_PARTS, rank = blockIdx.x / POP_PARTS;
   const int waves = ((int)gridDim.x - part + POP_PARTS - 1) / POP_PARTS;   // wavefronts working on this range
-  const int lo = persistent ? (int)((long long)n * part / POP_PARTS) : 0;
-  const int hi = persistent ? (int)((long long)n * (part + 1) / POP_PARTS) : n;
-  int t = persistent ? lo + rank : (int)blockIdx.x;
+  const int lo = g0 + (persistent ? (int)((long long)n * part / POP_PARTS) : 0);
+  const int hi = g0 + (persistent ? (int)((long long)n * (part + 1) / POP_PARTS) : n);
+  int t = persistent ? lo + rank : g0 + (int)blockIdx.x;
   while (t < hi) {
     int nxt = 0x7fffffff;
     if (persistent && lane == 0) nxt = lo + waves + atomicAdd(&mine[part * POP_STRIDE], 1);
@@ -658,7 +662,7 @@ struct VariantOps {
   int lds_bytes;            // dynamic LDS of one workgroup
   hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
   void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,
-               int parity);
+               int parity, int g0, int half);   // games [g0, g0 + n) as sub-batch `half` (k_play_vs: 0, 0 only)
 };
 
 // k_play_vs<U, W> at the build's default variant (vs_expert.hip): the rollout kernel that knows the scripted bot.

@@ -635,7 +635,13 @@ struct monsoon {
   hipStream_t stream = nullptr;
   DevBuffers b;
   const VariantOps* var = nullptr;   // hot-kernel variant: candidate lanes per game, waves per SIMD
-  int parity = 0;     // which of b.pop the next k_decide launch uses
+  int parity[SPLIT_MAX] = {};   // which of its two sets of b.pop the next persistent launch of sub-batch s uses (s = 0: every unsplit launch)
+  // split calls (launch_play): sub-batch s > 0 runs on split_stream[s], created on first use; [0] stays unused
+  hipStream_t split_stream[SPLIT_MAX] = {};
+  hipEvent_t split_done[SPLIT_MAX] = {};   // recorded behind sub-batch s of the last split call
+  hipEvent_t split_fork = nullptr;         // recorded on `stream` before the first split call after other work
+  int split_live = 0;   // sub-batches of split calls that `stream` has not waited for yet (bind_device joins them), 0 = none
+  int split_grid = 0;   // ... and their grid
   size_t ovf_lanes = 0;   // stepping lanes b.wk_ovf has room for (OVF_WORDS words each)
   std::vector<uint32_t*> ovf_retired;   // earlier, smaller b.wk_ovf blocks: a captured launch may still point to one (grow_ovf)
   unsigned long long st_acc[ST_N], st_base[ST_N];   // statistics: totals of earlier batches, baseline of the loaded one
@@ -667,6 +673,7 @@ struct monsoon {
   size_t matches_cap = 0;
   // kernel timing: event pairs are created once and reused
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+  std::vector<char> ev_split;   // pair i times a split call: its end event lies on the last sub-batch's stream (drain_timing)
   size_t ev_used = 0;
   double kernel_ms = 0;
   long long kernel_launches = 0;
@@ -763,6 +770,14 @@ void monsoon_destroy(monsoon_t* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
+  for (int s = 1; s < SPLIT_MAX; s++) {   // (a split call may still be in flight on these: not joined, the handle goes away)
+    if (h->split_stream[s]) {
+      hipStreamSynchronize(h->split_stream[s]);
+      hipStreamDestroy(h->split_stream[s]);
+    }
+    if (h->split_done[s]) hipEventDestroy(h->split_done[s]);
+  }
+  if (h->split_fork) hipEventDestroy(h->split_fork);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
                   h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w};
@@ -777,7 +792,7 @@ void monsoon_destroy(monsoon_t* h) {
   delete h;
 }
 
-static hipError_t bind_device(monsoon_t* h);
+static hipError_t bind_device(monsoon_t* h, bool join = true);
 static int create_impl(monsoon* h) {
   const monsoon_config& cfg = h->cfg;
   size_t cap = (size_t)cfg.max_games;
@@ -807,8 +822,8 @@ static int create_impl(monsoon* h) {
   // up to whole workgroups); launch_play grows the buffer once it knows its grid
   h->ovf_lanes = ((cap + API_LANES - 1) / API_LANES) * (size_t)API_LANES;
   HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
-  HIP_TRY(h, hipMalloc(&h->b.pop, 2 * 8 * 32 * sizeof(int)));
-  HIP_TRY(h, hipMemset(h->b.pop, 0, 2 * 8 * 32 * sizeof(int)));
+  HIP_TRY(h, hipMalloc(&h->b.pop, SPLIT_MAX * 2 * POP_PARTS * POP_STRIDE * sizeof(int)));
+  HIP_TRY(h, hipMemset(h->b.pop, 0, SPLIT_MAX * 2 * POP_PARTS * POP_STRIDE * sizeof(int)));
 #if defined(MSB_PROF) && MSB_PROF
   HIP_TRY(h, hipMalloc(&h->b.prof, cap * PROF_WORDS * sizeof(unsigned long long)));
   HIP_TRY(h, hipMemset(h->b.prof, 0, cap * PROF_WORDS * sizeof(unsigned long long)));
@@ -886,16 +901,27 @@ int monsoon_variant(monsoon_t* h, int32_t* lanes_per_game, int32_t* waves_per_si
   return MONSOON_OK;
 }
 
-// Make the handle's device current.
-static hipError_t bind_device(monsoon_t* h) { return hipSetDevice(h->device); }
+// Make the handle's device current and, with join, the handle's stream whole again: a split call (launch_play) left
+// sub-batches running on the handle's other streams, and whatever is enqueued on or waits for `stream` next must come
+// after them.  Every entry point passes through here before it touches the stream; only monsoon_play_rounds_dev and
+// monsoon_decide_round_dev ask for no join, so that a call's first sub-batch follows the one before it without waiting
+// for that call's last.
+static hipError_t bind_device(monsoon_t* h, bool join) {
+  hipError_t e = hipSetDevice(h->device);
+  if (join) {
+    for (int s = 1; s < h->split_live && e == hipSuccess; s++) e = hipStreamWaitEvent(h->stream, h->split_done[s], 0);
+    h->split_live = 0;
+  }
+  return e;
+}
 
-static int check_ready(monsoon_t* h) {
+static int check_ready(monsoon_t* h, bool join = true) {
   if (!h) return MONSOON_ERR_ARG;
   if (h->n <= 0) {
     h->err = "no games loaded: call monsoon_reset first";
     return MONSOON_ERR_STATE;
   }
-  hipError_t e = bind_device(h);
+  hipError_t e = bind_device(h, join);
   if (e != hipSuccess) {
     h->err = std::string("hipSetDevice: ") + hipGetErrorString(e);
     return MONSOON_ERR_DEVICE;
@@ -1424,18 +1450,32 @@ static int timing_begin(monsoon_t* h, size_t* slot) {
       return MONSOON_ERR_DEVICE;
     }
     h->ev_pool.emplace_back(e0, e1);
+    h->ev_split.push_back(0);
   }
   *slot = h->ev_used++;
+  h->ev_split[*slot] = 0;
   HIP_TRY(h, hipEventRecord(h->ev_pool[*slot].first, h->stream));
   return MONSOON_OK;
 }
 
+// kernel_ms is the time the GPU was busy with the timed calls, kernel_launches counts API calls (a split call is one).
+// An unsplit call's share is elapsed(start, end), both on the handle's stream.  A split call k records its start on the
+// handle's stream before its first sub-batch and its end behind its last sub-batch, on that one's stream; its first
+// sub-batch may run while call k-1's last still does, so its share is
+//     min(elapsed(start_k, end_k), elapsed(end_{k-1}, end_k)):
+// consecutive calls never count the same wall time twice, and the sum cannot exceed the wall time around them.  (Call
+// k-1 of an earlier drain ended before a synchronisation that start_k follows: the first term is the smaller one.)
 static int drain_timing(monsoon_t* h) {
   for (size_t i = 0; i < h->ev_used; i++) {
     auto& pr = h->ev_pool[i];
     HIP_TRY(h, hipEventSynchronize(pr.second));
     float ms = 0;
     HIP_TRY(h, hipEventElapsedTime(&ms, pr.first, pr.second));
+    if (i > 0 && h->ev_split[i]) {
+      float since_prev = 0;
+      HIP_TRY(h, hipEventElapsedTime(&since_prev, h->ev_pool[i - 1].second, pr.second));
+      ms = std::max(0.0f, std::min(ms, since_prev));
+    }
     h->kernel_ms += ms;
     h->kernel_launches++;
   }
@@ -1466,15 +1506,11 @@ static const int g_lds_pad = getenv("MONSOON_LDS_PAD") ? atoi(getenv("MONSOON_LD
 // `rounds` decisions of every loaded game in ONE launch (1 = a decision round; max_turns + 1 = whole games: the extra
 // round turns "still running at the cap" into a result).
 // vs = true: k_play_vs, the kernel that knows the scripted bot (the build's default variant, whatever the handle's is).
-static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false) {
+// split = true (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below.
+static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false, bool split = false) {
   if (h->bot_rows && !vs) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
-  }
-  size_t slot = 0;
-  if (timed) {
-    int rc = timing_begin(h, &slot);
-    if (rc) return rc;
   }
   const VariantOps* v = vs ? monsoon_vs_expert_ops() : h->var;
   const int lds = v->lds_bytes + g_lds_pad;
@@ -1491,40 +1527,90 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   if (const char* e = getenv("MONSOON_GRID")) grid = atoi(e);
   // the persistent form needs a wavefront for every one of its POP_PARTS ranges
   const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
+  // A persistent launch ends with a drain: the counters are dry, every wavefront finishes the game it holds and leaves,
+  // and the next launch on the stream starts nothing until the slowest one has (profiles/launch_tail.md).  Games are
+  // independent, so a call is split into `parts` sub-batches of games, each a persistent launch of the full grid on a
+  // stream of its own: while the first drains, the waiting workgroups of the next take the freed slots, and while the last
+  // drains, the first sub-batch of the NEXT call does -- it is queued behind this call's first on the handle's stream and
+  // waits for nothing else.  Only the last call before a synchronisation keeps its drain.  Not while the stream is being
+  // captured (a graph holds one stream's work), and only where every sub-batch is still persistent.  MONSOON_SPLIT = 0 / 1:
+  // one launch; read per call, like MONSOON_GRID.
+  int parts = 1;
+  if (split && !vs && pers) {
+    parts = 2;
+    if (const char* e = getenv("MONSOON_SPLIT")) parts = std::min(std::max(atoi(e), 1), (int)SPLIT_MAX);
+    if (n / parts <= grid) parts = 1;
+    if (parts > 1) {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
+      if (cs != hipStreamCaptureStatusNone) parts = 1;
+    }
+  }
+  // Sub-batches follow each other stream by stream only while calls are cut alike: another number of parts moves the
+  // games between the streams, another grid (one decision per launch has twice the grid of several) moves the overflow
+  // blocks.  Such a call, an unsplit one included, goes behind everything in flight.
+  if (h->split_live && (parts != h->split_live || grid != h->split_grid)) HIP_TRY(h, bind_device(h));
   if (!pers) grid = n;   // a wavefront per game
-  {   // work-stack overflow blocks for every workgroup of this grid
-    int rc = grow_ovf(h, (size_t)grid * v->lanes);
+  {   // work-stack overflow blocks for every workgroup of this grid, of every sub-batch
+    int rc = grow_ovf(h, (size_t)parts * grid * v->lanes);
     if (rc) return rc;
   }
-  v->play(grid, lds, h->stream, h->b, n, max_turns, rounds, write_scores, pers, h->parity);
-  // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
-  // must leave the parity alone, or the next persistent launch would start from the stale counts of the one before.
-  if (pers) h->parity ^= 1;
-  HIP_TRY(h, hipGetLastError());
-  if (timed) HIP_TRY(h, hipEventRecord(h->ev_pool[slot].second, h->stream));
+  for (int s = 1; s < parts; s++) {
+    if (!h->split_stream[s]) HIP_TRY(h, hipStreamCreateWithFlags(&h->split_stream[s], hipStreamNonBlocking));
+    if (!h->split_done[s]) HIP_TRY(h, hipEventCreateWithFlags(&h->split_done[s], hipEventDisableTiming));
+  }
+  if (parts > 1 && !h->split_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
+  size_t slot = 0;
+  if (timed) {
+    int rc = timing_begin(h, &slot);
+    if (rc) return rc;
+  }
+  if (parts > 1 && !h->split_live) {
+    // fork: the first split call after other work starts its other streams behind what the handle's stream holds (a
+    // reset, new weights, a join); the calls after it follow sub-batch by sub-batch
+    HIP_TRY(h, hipEventRecord(h->split_fork, h->stream));
+    for (int s = 1; s < parts; s++) HIP_TRY(h, hipStreamWaitEvent(h->split_stream[s], h->split_fork, 0));
+  }
+  for (int s = 0; s < parts; s++) {
+    const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
+    v->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, max_turns, rounds, write_scores, pers, h->parity[s], g0, s);
+    // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
+    // must leave the parity alone, or the next persistent launch would start from the stale counts of the one before.
+    if (pers) h->parity[s] ^= 1;
+    HIP_TRY(h, hipGetLastError());
+    if (s) HIP_TRY(h, hipEventRecord(h->split_done[s], h->split_stream[s]));
+  }
+  if (parts > 1) {
+    h->split_live = parts;
+    h->split_grid = grid;
+  }
+  if (timed) {
+    h->ev_split[slot] = parts > 1;
+    HIP_TRY(h, hipEventRecord(h->ev_pool[slot].second, parts > 1 ? h->split_stream[parts - 1] : h->stream));
+  }
   return MONSOON_OK;
 }
 
 int monsoon_decide_round_dev(monsoon_t* h) {
-  int rc = check_ready(h);
+  int rc = check_ready(h, false);   // no join: launch_play
   if (rc) return rc;
   if (!h->b.weights) {
     h->err = "monsoon_decide_round_dev: upload weights and assign players first";
     return MONSOON_ERR_STATE;
   }
-  return launch_play(h, h->n, 0x7fff, 1, 0, true);
+  return launch_play(h, h->n, 0x7fff, 1, 0, true, false, true);
 }
 
 // `rounds` decisions of every loaded game in one launch: a game's record stays in LDS from its first to its last decision
 // of the call (asynchronous on the handle's stream, like monsoon_decide_round_dev = rounds 1).
 int monsoon_play_rounds_dev(monsoon_t* h, int32_t rounds) {
-  int rc = check_ready(h);
+  int rc = check_ready(h, false);   // no join: launch_play
   if (rc) return rc;
   if (rounds <= 0 || !h->b.weights) {
     h->err = "monsoon_play_rounds_dev: rounds must be positive; upload weights and assign players first";
     return rounds <= 0 ? MONSOON_ERR_ARG : MONSOON_ERR_STATE;
   }
-  return launch_play(h, h->n, 0x7fff, rounds, 0, true);
+  return launch_play(h, h->n, 0x7fff, rounds, 0, true, false, true);
 }
 
 int monsoon_sync(monsoon_t* h) {
@@ -1726,6 +1812,7 @@ int monsoon_get_stats(monsoon_t* h, monsoon_stats* out) {
 // Raw counter words; out = 192 u64 (profiling builds: k_decide phase cycles at 8.., function scopes at 32.. / 64..).
 int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
   if (!h || !out) return MONSOON_ERR_ARG;
+  HIP_TRY(h, bind_device(h));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   memset(out, 0, 192 * sizeof(unsigned long long));
   {
@@ -1760,10 +1847,13 @@ int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
     {
       std::vector<unsigned long long> st, en;
       unsigned long long newest = 0;
+      // a launch of several decisions per game lasts longer than 10 ms here: scripts/launch_tail.py widens the window
+      // (monsoon_reset_stats cleared the older stamps)
+      const unsigned long long window = 100000ull * (unsigned long long)(getenv("MONSOON_PROF_WINDOW_MS") ? atoi(getenv("MONSOON_PROF_WINDOW_MS")) : 10);
       for (int g = 0; g < h->n; g++) newest = std::max(newest, v[(size_t)g * PROF_WORDS + 137]);
       for (int g = 0; g < h->n; g++) {
         unsigned long long a = v[(size_t)g * PROF_WORDS + 136], e = v[(size_t)g * PROF_WORDS + 137];
-        if (e > a && e + 1000000ull > newest) {   // stamps of the last launch only (within 10 ms of the newest)
+        if (e > a && e + window > newest) {   // stamps of the last launch only (within 10 ms of the newest)
           st.push_back(a);
           en.push_back(e);
         }
@@ -1821,7 +1911,10 @@ int monsoon_kernel_time(monsoon_t* h, double* total_ms, int64_t* launches) {
   return MONSOON_OK;
 }
 
-void* monsoon_stream(monsoon_t* h) { return h ? (void*)h->stream : nullptr; }
+void* monsoon_stream(monsoon_t* h) {
+  if (h && h->split_live) bind_device(h);   // what the caller orders behind the stream comes after every sub-batch of a split call
+  return h ? (void*)h->stream : nullptr;
+}
 
 // ---- vector env (env.inc) -----------------------------------------------------------------------
 }  // extern "C"

@@ -9,8 +9,9 @@ hipError_t v_occupancy(int* blocks_per_cu, int lds_bytes) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_play<VAR_U, VAR_W>, 64, lds_bytes);
 }
 void v_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,
-            int parity) {
-  hipLaunchKernelGGL((k_play<VAR_U, VAR_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, write_scores, persistent, parity);
+            int parity, int g0, int half) {
+  hipLaunchKernelGGL((k_play<VAR_U, VAR_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, write_scores, persistent, parity,
+                     g0, half);
 }
 const VariantOps kOps = {VAR_U, VAR_W, PlayLds<VAR_U>::TOTAL, v_occupancy, v_play};
 }  // namespace

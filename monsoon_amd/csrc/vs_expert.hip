@@ -41,7 +41,7 @@ hipError_t vs_occupancy(int* blocks_per_cu, int lds_bytes) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_play_vs<VS_U, VS_W>, 64, lds_bytes);
 }
 void vs_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,
-             int parity) {
+             int parity, int /*g0*/, int /*half*/) {   // never split: the whole batch, the first pair of counter sets
   hipLaunchKernelGGL((k_play_vs<VS_U, VS_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, write_scores, persistent, parity);
 }
 const VariantOps kOps = {VS_U, VS_W, PlayLds<VS_U>::TOTAL, vs_occupancy, vs_play};
