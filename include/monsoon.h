@@ -259,7 +259,9 @@ int monsoon_decide_round_dev(monsoon_t* h);   /* asynchronous on the handle's st
  * half fills the GPU while this call's second half runs out of games (MONSOON_SPLIT=0 in the environment, read per
  * call: always one launch on the handle's stream).  Every other entry point, monsoon_sync and monsoon_stream included,
  * first makes the handle's stream wait for that half: a caller that orders work of its own behind these two calls
- * fetches monsoon_stream after them, or calls monsoon_sync. */
+ * fetches monsoon_stream after them, or calls monsoon_sync.  While the handle's stream is being captured into a graph
+ * both calls record a single launch of one workgroup per game (never split, untimed), which may be replayed any number
+ * of times in a row; fetch monsoon_stream after the last eager call and before the capture begins. */
 int monsoon_play_rounds_dev(monsoon_t* h, int32_t rounds);
 int monsoon_sync(monsoon_t* h);
 

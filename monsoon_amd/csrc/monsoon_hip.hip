@@ -1489,11 +1489,21 @@ static int drain_timing(monsoon_t* h) {
 // cannot know whether a capture exists, and sizing for the largest grid any later rollout may choose would cost every
 // env hundreds of MB it may never use.)  Growth at least doubles the buffer, so the kept blocks together stay smaller than
 // the live one however the requests creep upward.  No synchronisation: nothing is freed under work in flight.
+// A captured call may be the first to need the larger block (launch_play: a wavefront per game while capturing), and an
+// allocation is refused while a stream of the thread captures in the default mode: the thread's capture mode is relaxed
+// around it.
 static int grow_ovf(monsoon_t* h, size_t lanes) {
   if (lanes <= h->ovf_lanes) return MONSOON_OK;
   lanes = std::max(lanes, 2 * h->ovf_lanes);
   uint32_t* grown = nullptr;
-  HIP_TRY(h, hipMalloc(&grown, lanes * OVF_WORDS * 4));
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  HIP_TRY(h, hipThreadExchangeStreamCaptureMode(&mode));
+  const hipError_t e = hipMalloc(&grown, lanes * OVF_WORDS * 4);
+  HIP_TRY(h, hipThreadExchangeStreamCaptureMode(&mode));
+  if (e != hipSuccess) {
+    h->err = std::string("hipMalloc of the work-stack overflow blocks: ") + hipGetErrorString(e);
+    return MONSOON_ERR_DEVICE;
+  }
   if (h->b.wk_ovf) h->ovf_retired.push_back(h->b.wk_ovf);
   h->b.wk_ovf = grown;
   h->ovf_lanes = lanes;
@@ -1525,8 +1535,17 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   // one decision per game and launch: two waves per slot measured best; many decisions per game: exactly the resident waves
   int grid = rounds > 1 ? grid_waves : 2 * grid_waves;
   if (const char* e = getenv("MONSOON_GRID")) grid = atoi(e);
+  // A call recorded into a graph is replayed as it stands, any number of times in a row.  The persistent form cannot be:
+  // `parity` is a kernel argument, a launch counts its own counter set up and clears only the other one, so the second
+  // replay in a row would start from the first one's counts and every wavefront would play one game only.  While the
+  // stream is capturing, the call is therefore the non-persistent form (no counters, the parities stay as they are),
+  // one launch on the handle's stream, and untimed (the handle's timing events must not become nodes of the graph).
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
+  const bool capturing = cs != hipStreamCaptureStatusNone;
+  if (capturing) timed = false;
   // the persistent form needs a wavefront for every one of its POP_PARTS ranges
-  const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
+  const int pers = (g_persistent && !capturing && grid < n && grid >= POP_PARTS) ? 1 : 0;
   // A persistent launch ends with a drain: the counters are dry, every wavefront finishes the game it holds and leaves,
   // and the next launch on the stream starts nothing until the slowest one has (profiles/launch_tail.md).  Games are
   // independent, so a call is split into `parts` sub-batches of games, each a persistent launch of the full grid on a
@@ -1540,11 +1559,6 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
     parts = 2;
     if (const char* e = getenv("MONSOON_SPLIT")) parts = std::min(std::max(atoi(e), 1), (int)SPLIT_MAX);
     if (n / parts <= grid) parts = 1;
-    if (parts > 1) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-      if (cs != hipStreamCaptureStatusNone) parts = 1;
-    }
   }
   // Sub-batches follow each other stream by stream only while calls are cut alike: another number of parts moves the
   // games between the streams, another grid (one decision per launch has twice the grid of several) moves the overflow

@@ -72,8 +72,9 @@ def test_split_fallback(monkeypatch, n):
 
 
 def test_sub_batch_boundary(monkeypatch):
-    """257 games, grid 16: halves of 128 and 129.  Reads between the calls join the two streams; a call of one decision
-    has another grid than one of several and a reset replaces games under both halves."""
+    """257 games, grid 16: halves of 128 and 129.  Reads between the calls join the two streams; calls of one decision and
+    of several alternate (under the forced MONSOON_GRID they share one grid: the join for a changed grid or cut is pinned
+    in test_split_transitions_gpu.py) and a reset replaces games under both halves."""
     n = 257
     p = Pair(monkeypatch, n, 16, 7000)
     sub = np.array([0, 1, 126, 127, 128, 129, 130, 255, 256])
