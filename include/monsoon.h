@@ -108,7 +108,9 @@ int monsoon_status(monsoon_t* h, int32_t* out);
 
 /* The fault code that stopped each loaded game, else the first build-limit code one of its look-aheads hit (0 = none): out[n].  The reference's exceptions are swallowed by
  * its agent layer (evo/heuristic_agent.py:48-51, evo/fitness.py:170-174,208-210); codes in msb_base.h, >= 16 are
- * limits of this build. */
+ * limits of this build -- except 18, the recursion guard (40 nested abilities / moves: the reference's own recursion ends in
+ * RecursionError there, on every record alike).  29 is the work stack's word budget running out before that guard trips: a
+ * limit of this build that no record changes; no game of the searches behind tests/golden/deep_steps.json.gz reports it. */
 int monsoon_game_faults(monsoon_t* h, uint8_t* out);
 
 /* Canonical state record of game idx (layout: monsoon_amd/csrc/canon.h), the comparand of the
@@ -166,7 +168,8 @@ int monsoon_rollout(monsoon_t* h, const double* weights, int32_t n_individuals, 
  * the fault that stopped the game, else the first capacity code one of its look-aheads hit).  Codes >= 16 are limits
  * of this build's record, not reference behaviour (the exception the reference swallows at evo/fitness.py:170-174,
  * 208-210 is code 1): such games are replayed on a build with a larger record -- libmonsoon_hip_ext.so ->
- * libmonsoon_hip_big.so, as monsoon_amd/fitness.py does -- and their rows of the result replaced. */
+ * libmonsoon_hip_big.so, as monsoon_amd/fitness.py does -- and their rows of the result replaced.  18 (the recursion guard: the
+ * reference raises RecursionError at that step) is not replayed; 29 (the work stack's word budget) is, and stays. */
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches);
 
 /* The evolved agent against the reference's scripted bot (play_vs_expert.py: HeuristicAgent.select_action on one side,

@@ -121,6 +121,8 @@ enum : int {
                             // reference's bot can repeat a USE that does nothing for ever)
   FAULT_OPP_BOUND = 28,     // vector env: the heuristic opponent still to play after 64 decisions in one call (kernels.h
                             // play_game<U, true>; a no-op USE that wins the argmax once wins it for ever)
+  FAULT_WORK_STACK = 29,    // the work stack's word budget (state.h SK_CAP - SK_MARGIN) ran out before the recursion guard
+                            // tripped: a limit of this build, where 18 is the reference's own RecursionError
 };
 
 // ---- static card table -----------------------------------------------------------------

@@ -28,9 +28,14 @@ static inline void msb_fault_trace(int code) {
 
 #if defined(MSB_COUNT_FRAMES) && !defined(__HIPCC__)
 #define MSB_COUNT_EVENT(i_) msb_frame_count[i_]++
+#define MSB_COUNT_MAX(i_, v_) (msb_frame_count[i_] = (v_) > msb_frame_count[i_] ? (v_) : msb_frame_count[i_])
 static long long msb_frame_count[64];   // study build of the host library: handler invocations per frame type, [0] = all, [15] = deepest stack, [16..27] = histogram of sp / 4, [32..47] = F_MOVE by state, [48..49] = F_RUNAB by state, [50..] = events inside move()
+// [12] = most words wk_reserve counted where the depth guard or the word budget ended a step, [13] = largest H_DEPTH written,
+// [14] = most evictions pending (Wk::seg).  [12..15] are maxima: a caller zeroes them through orc_frame_counts() before a step
+// to read that step's own figures (scripts/deep_step_search.py).
 #else
 #define MSB_COUNT_EVENT(i_)
+#define MSB_COUNT_MAX(i_, v_)
 #endif
 
 namespace msb {
@@ -1340,6 +1345,7 @@ struct Engine {
   // the eviction block, the top frame slides down and an F_EVICTED frame {hdr: n} marks the place: when that frame is
   // on top again, the n words come back.  Handlers never notice.
   MSB_HD MSB_INL void wk_evict(Wk& k, int fn) {
+    static_assert(M::SKW >= SK_CAP || M::SKW <= 255, "a resident stack that evicts: the eviction mark keeps its word count in one header byte");
     const int fs = frame_words(fn), n = k.sp - fs;
     for (int i = 0; i < n; i++) M::ovf_st(k.base + i, m.sk_ld(i));
     for (int j = 0; j < fs; j++) m.sk_st(1 + j, m.sk_ld(n + j));
@@ -1436,10 +1442,12 @@ struct Engine {
     wk_push_ctx(k, sv);
     const int d = m.ld8(H_DEPTH);
     if (d >= MAX_DEPTH || !wk_reserve(k)) {
-      set_fault(FAULT_DEPTH);
+      MSB_COUNT_MAX(12, k.base + k.sp - k.seg);
+      set_fault(d >= MAX_DEPTH ? FAULT_DEPTH : FAULT_WORK_STACK);
       return;
     }
     m.st8(H_DEPTH, d + 1);
+    MSB_COUNT_MAX(13, d + 1);
     wk_push(k, (uint32_t)(spell & 0xffff) | ((uint32_t)(pos_pk & 0xff) << 16));
     wk_push(k, mk_hdr(F_RUNAB, 0, e, d | (src ? 0x80 : 0)));
   }
@@ -1686,10 +1694,12 @@ struct Engine {
     wk_push_ctx(k, sv);
     const int d = m.ld8(H_DEPTH);
     if (d >= MAX_DEPTH || !wk_reserve(k)) {
-      set_fault(FAULT_DEPTH);
+      MSB_COUNT_MAX(12, k.base + k.sp - k.seg);
+      set_fault(d >= MAX_DEPTH ? FAULT_DEPTH : FAULT_WORK_STACK);
       return -1;
     }
     m.st8(H_DEPTH, d + 1);
+    MSB_COUNT_MAX(13, d + 1);
     return d;
   }
   // (a move's three data words hold nothing until it first waits for a nested call: only the header is written here)
@@ -2559,6 +2569,7 @@ struct Engine {
       msb_frame_count[fn]++;
       msb_frame_count[0]++;
       if (k.base + k.sp > msb_frame_count[15]) msb_frame_count[15] = k.base + k.sp;
+      MSB_COUNT_MAX(14, k.seg);
       msb_frame_count[16 + (k.sp < 47 ? k.sp / 4 : 11)]++;
       if (fn == F_MOVE) msb_frame_count[32 + (hdr_st(hdr) & 15)]++;
       if (fn == F_RUNAB) msb_frame_count[48 + (hdr_st(hdr) & 1)]++;

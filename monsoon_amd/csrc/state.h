@@ -182,8 +182,10 @@ constexpr int LDS_RECORDS = WK_OVF_LDS + 16;         // first LDS byte the kerne
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
 // a handler runs, everything below the top frame is EVICTED to the workgroup's block in HBM and comes back when the
 // frames above it have run (rules.h wk_evict): a chain of more than a few nested abilities -- 2 % of the steps of a
-// neutral-deck game.  A stack deeper than SK_CAP - SK_MARGIN words in all ends the step with FAULT_DEPTH (40 nested
-// abilities / moves, where the reference's own recursion limit is restated, need about 530).
+// neutral-deck game.  A stack deeper than SK_CAP - SK_MARGIN words in all ends the step with FAULT_WORK_STACK, a limit of this
+// build with a code of its own: the recursion guard (FAULT_DEPTH, 40 nested abilities / moves, where the reference's own
+// recursion ends in RecursionError) must bind first.  Measured where the guard trips (tests/test_deep_steps_cpu.py, the
+// guard games of 524 288 C5 games): 307 words at the most, the eviction marks not counted.
 constexpr int SK_CAP = 640;
 constexpr int SK_MARGIN = 32;
 constexpr int SK_NEED = 12;   // the most one handler pushes before it returns to run() (an ability: F_AFTER 2 + the damage -> destroy -> next ability chain 6; F_EACH 8; F_TURN 7)

@@ -118,7 +118,8 @@ def fitness_from_counts(counts, games_per_individual):
     return [float((counts[i, 0] + 0.5 * counts[i, 1]) / games_per_individual) for i in range(len(counts))]
 
 
-CAPACITY_CODE = 16   # fault codes >= this are limits of a build's record (csrc/msb_base.h), not reference behaviour ...
+CAPACITY_CODE = 16   # fault codes >= this are limits of a build's record (csrc/msb_base.h), not reference behaviour
+#                      (29, the work stack's word budget, among them: the same on every record, so the ladder ends by reporting it) ...
 DEPTH_CODE = 18      # ... except the recursion guard: 40 nested abilities / moves.  Where that trips the reference's own
 #                      recursion ends in RecursionError (raising the guard to 200 changes no game; the reference's trace of such
 #                      a game is part of tests/golden/trace_heuristic_c5_big.npz), and the guard is the same on every record: such
@@ -272,7 +273,9 @@ class FitnessEvaluator:
         self.depth_faults += int((faults == DEPTH_CODE).sum())
         if left:
             msg = (f"{left} of {len(matches)} games still end on a limit of the largest record (fault codes "
-                   f"{sorted(set(faults[record_limited(faults)].tolist()))}): scored as draws, parity with the reference unpinned for them")
+                   f"{sorted(set(faults[record_limited(faults)].tolist()))}): scored as draws, parity with the reference unpinned for them"
+                   f" (depth_faults so far: {self.depth_faults} games ended by the recursion guard, code {DEPTH_CODE}, the reference's"
+                   " RecursionError: draws there too, not counted here)")
             if self.strict:
                 raise RuntimeError(msg)
             import warnings

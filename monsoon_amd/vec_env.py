@@ -80,6 +80,10 @@ class VecEnv:
     def __init__(self, max_slots, device=0, extended=0, lanes_per_game=0):
         """extended = 0 / 1 / 2 selects the record build (1: decks holding ua20 / b005).  Raises MonsoonError when no
         gfx950 device is usable."""
+        # torch ships a ROCm runtime of its own.  It has to be the first one the process loads: once libmonsoon_hip*.so has
+        # pulled in the system's, a torch imported afterwards finds no device (torch.cuda.is_available() is False).  The
+        # env's views are torch tensors, so torch is needed anyway: import it before the handle loads the library.
+        import torch  # noqa: F401
         self.engine = BatchEngine(max_slots, device=device, lanes_per_game=lanes_per_game, extended=extended)
         self.device = device
         self.extended = extended

@@ -593,7 +593,32 @@ void orc_np_gauss(uint32_t seed, int n, double* values, int64_t* stream_pos) {
   }
 }
 #if defined(MSB_COUNT_FRAMES)
-long long* orc_frame_counts() { return msb_frame_count; }   // study build (scripts/frame_stats.py)
+// study build (scripts/frame_stats.py, scripts/deep_step_search.py): the counters are plain statics -- one thread only; a
+// caller zeroes the maxima [12..15] to read one step's own figures
+long long* orc_frame_counts() { return msb_frame_count; }
+// One step's own work-stack figures for every legal action of game gi, each on a copy: out[a] = {fault, deepest H_DEPTH,
+// most words, most evictions pending, words where the guard or the budget ended the step}; fault = 255 where a is not legal.
+void orc_lookahead_counts(void* h, int gi, int32_t* out156x5) {
+  Game& g = ((Oracle*)h)->games[gi];
+  Engine<FlatMem> e = engine(g);
+  uint64_t mask[3];
+  e.legal_mask(mask);
+  for (int a = 0; a < 156; a++) {
+    int32_t* o = out156x5 + 5 * a;
+    o[0] = 255;
+    o[1] = o[2] = o[3] = o[4] = 0;
+    if (!(mask[a >> 6] >> (a & 63) & 1)) continue;
+    Game c = g;
+    Engine<FlatMem> ce = engine(c);
+    msb_frame_count[12] = msb_frame_count[13] = msb_frame_count[14] = msb_frame_count[15] = 0;
+    ce.step(a);
+    o[0] = ce.fault();
+    o[1] = (int32_t)msb_frame_count[13];
+    o[2] = (int32_t)msb_frame_count[15];
+    o[3] = (int32_t)msb_frame_count[14];
+    o[4] = (int32_t)msb_frame_count[12];
+  }
+}
 #endif
 int orc_pyset_list(const uint8_t* keys, int n, uint8_t* out) { return pyset_list(keys, n, out); }
 double orc_score(const double* w, const double* before, const double* after) {

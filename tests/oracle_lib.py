@@ -18,6 +18,10 @@ LIB_PATH_BIG = os.path.join(ORACLE_DIR, "liboracle_big.so")   # large extended r
 PRODUCT_HOST = tuple(os.path.join(ORACLE_DIR, n) for n in ("libproduct_host.so", "libproduct_host_ext.so", "libproduct_host_big.so"))
 # ... and with the device's 21-word resident work stack, so that the eviction path of wk_reserve runs on the CPU too
 PRODUCT_HOST_EVICT = tuple(os.path.join(ORACLE_DIR, n) for n in ("libproduct_host_evict.so", "libproduct_host_evict_ext.so"))
+# ... counting the depth, words and pending evictions of a step (-DMSB_COUNT_FRAMES; one thread only)
+PRODUCT_HOST_COUNT = tuple(os.path.join(ORACLE_DIR, n) for n in ("libproduct_host_count.so", "libproduct_host_count_ext.so"))
+# the recursive oracle with its recursion guard at 200 instead of 40 levels
+ORACLE_DEPTH200 = tuple(os.path.join(ORACLE_DIR, n) for n in ("liboracle_depth200.so", "liboracle_depth200_ext.so"))
 
 
 def build():
@@ -31,7 +35,8 @@ def lib(extended=False, core=None):
     core = core or os.environ.get("MSB_ORACLE_CORE", "oracle")   # "product": the host build of the product's rules core
     key = (extended, core)
     if key not in _libs:
-        paths = {"product": PRODUCT_HOST, "product_evict": PRODUCT_HOST_EVICT}.get(core, (LIB_PATH, LIB_PATH_EXT, LIB_PATH_BIG))
+        paths = {"product": PRODUCT_HOST, "product_evict": PRODUCT_HOST_EVICT, "product_count": PRODUCT_HOST_COUNT,
+                 "depth200": ORACLE_DEPTH200}.get(core, (LIB_PATH, LIB_PATH_EXT, LIB_PATH_BIG))
         path = extended if isinstance(extended, str) else paths[int(extended)]
         if not os.path.exists(path):
             build()
@@ -64,6 +69,10 @@ def lib(extended=False, core=None):
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.orc_score.restype = ctypes.c_double
         L.orc_score.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        if core == "product_count":
+            L.orc_frame_counts.restype = ctypes.POINTER(ctypes.c_longlong)
+            L.orc_lookahead_counts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+            L.orc_lookahead_counts.restype = None
         L.orc_rng_u32.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
         L.orc_rng_random.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
         L.orc_rng_randint.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -171,6 +180,20 @@ class Oracle:
         n = ctypes.c_int()
         f = self.L.orc_scn_op(self.h, i, _p(op), _p(log), 256, ctypes.byref(n))
         return f, log[:2 * n.value].reshape(-1, 2).tolist()
+
+    def lookahead_counts(self, i):
+        """core="product_count" only: int32[156, 5] = {fault (255 = not legal), deepest H_DEPTH, most words, most evictions
+        pending, words where the guard or the budget ended the step} of every legal action's step, each on a copy."""
+        out = np.zeros((156, 5), dtype=np.int32)
+        self.L.orc_lookahead_counts(self.h, i, _p(out))
+        return out
+
+    def step_counts(self, i, action):
+        """core="product_count" only: step(i, action) and that step's own (depth, words, evictions pending, words at the guard)."""
+        c = self.L.orc_frame_counts()
+        c[12] = c[13] = c[14] = c[15] = 0
+        r = self.step(i, action)
+        return r, (int(c[13]), int(c[15]), int(c[14]), int(c[12]))
 
     def lookahead_faults(self, i):
         """Fault code of each legal action's look-ahead (255 = not legal); 20 = flagged as unsupported by this build."""

@@ -226,6 +226,8 @@ def test_recursion_guard_is_not_a_record_limit_and_strict_mode_raises():
     from monsoon_amd.config import EvolutionaryConfig
     from monsoon_amd.fitness import MATCH_DTYPE, FitnessEvaluator, record_limited, tiered_rollout
     assert record_limited(np.array([0, 1, 16, 18, 22], dtype=np.uint8)).tolist() == [False, False, True, False, True]
+    # 29, the work stack's word budget, is a limit of the build like any other capacity code: never filed with the guard's 18
+    assert record_limited(np.array([18, 29, 28, 2], dtype=np.uint8)).tolist() == [False, True, True, False]
     m = np.zeros(4, dtype=MATCH_DTYPE)
     m["seed"] = np.arange(4)
     pairs = np.zeros((1, 2, 12), dtype=np.uint8)
@@ -260,6 +262,42 @@ def test_recursion_guard_is_not_a_record_limit_and_strict_mode_raises():
                 assert fe.capacity_faults == 1 and fe.depth_faults == 1 and any("still end on a limit" in str(x.message) for x in w)
         finally:
             F.tiered_rollout = orig
+
+
+def test_work_stack_budget_code_is_reported_as_a_limit_and_never_as_the_guard():
+    """Code 29 (the work stack's word budget, the same on every record) climbs the ladder like any capacity code, stays, and is
+    reported as a limit; the guard's 18 next to it is neither replayed nor counted, and the warning names both figures."""
+    import warnings
+    from monsoon_amd.config import EvolutionaryConfig
+    from monsoon_amd.fitness import MATCH_DTYPE, FitnessEvaluator, tiered_rollout
+    import monsoon_amd.fitness as F
+    m = np.zeros(3, dtype=MATCH_DTYPE)
+    m["seed"] = np.arange(3)
+    pairs = np.zeros((1, 2, 12), dtype=np.uint8)
+    calls = []
+
+    def play(tier, sub, sub_pairs):
+        calls.append((tier, sub["seed"].tolist()))
+        f = np.array([{0: 18, 1: 29, 2: 0}[int(s)] for s in sub["seed"]], dtype=np.uint8)
+        r = np.where(f != 0, -1, 0).astype(np.int8)
+        c = np.zeros((1, 3), dtype=np.int64)
+        c[0] = [(r == 0).sum(), (r == -1).sum(), len(sub)]
+        return c, r, np.full(len(sub), 7, dtype=np.int32), f
+    counts, results, steps, faults, replays, sizes = tiered_rollout(play, 1, m, pairs)
+    assert calls == [(0, [0, 1, 2]), (1, [1]), (2, [1])] and faults.tolist() == [18, 29, 0] and counts[0].tolist() == [1, 2, 3]
+    fe = FitnessEvaluator(EvolutionaryConfig(max_turns=5))
+    fe._engine = lambda tier: None
+    orig = F.tiered_rollout
+    F.tiered_rollout = lambda play_, n, mm, pp, concurrent=False: tiered_rollout(play, n, mm, pp, concurrent=concurrent)
+    try:
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            fe._hip_rollout(np.zeros((1, 10)), m, pairs, 5)
+    finally:
+        F.tiered_rollout = orig
+    assert fe.capacity_faults == 1 and fe.depth_faults == 1
+    text = [str(x.message) for x in w if "still end on a limit" in str(x.message)]
+    assert len(text) == 1 and "[29]" in text[0] and "depth_faults so far: 1" in text[0]
 
 
 def test_single_process_evaluation_does_not_import_torch_distributed():
