@@ -33,6 +33,7 @@
 #include "canon.h"
 #include "coop_features.h"
 #include "coop_draw.h"
+#include "pass_glue.h"
 
 namespace msbk {
 using namespace msb;
@@ -391,8 +392,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     }
 #endif
     const msb_u64x4 lm = pe.legal_mask_v();
-    // the legal set as wave-uniform scalars; `rem` loses the U lowest actions after every pass, so a lane finds its
-    // action among the first U set bits (at most U - 1 steps, on the scalar unit for the common part)
+    // the legal set as wave-uniform scalars; `rem` loses the U lowest actions with every pass, which hands them to its
+    // candidate lanes from the scalar unit (pass_glue.h)
     const uint64_t mask[3] = {uni64(lm[0]), uni64(lm[1]), uni64(lm[2])};
     uint64_t rem[3] = {mask[0], mask[1], mask[2]};
     const int n_legal = __popcll(mask[0]) + __popcll(mask[1]) + __popcll(mask[2]);
@@ -438,26 +439,21 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     int feat_ok = 0;                  // wf[20..29] holds the features of the best successor so far
     int la_fault = 0;                 // first build-limit fault a look-ahead of this decision hit
     for (int base = 0; base < n_legal; base += U) {
-      int k = base + lane;
       double s = 0.0;   // except Exception -> 0.0 (evo/heuristic_agent.py:48-51)
       int a = NONE_A;
       int my_fault = 0;
       int my_feat = 0;
       int f = 0;
       bool raises = false;
+      const int n_act = n_legal - base < U ? n_legal - base : U;   // (uniform) the candidates of this pass: lanes 0 .. n_act-1
       {   // copy.deepcopy (stream window included) for the whole pass: lane l writes granule l of every column in use
-        const int n_act = n_legal - base < U ? n_legal - base : U;
         __syncthreads();
         for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
       }
-      const bool active = lane < U && k < n_legal;
-      if (active) a = nth_set_bit(rem, lane);
-      for (int i = 0; i < U; i++) {   // uniform: drop this pass's actions
-        if (rem[0]) rem[0] &= rem[0] - 1;
-        else if (rem[1]) rem[1] &= rem[1] - 1;
-        else rem[2] &= rem[2] - 1;
-      }
+      const bool active = lane < n_act;
+      // lane l takes the (base + l)-th legal action, handed out by the scalar unit; `rem` loses them (pass_glue.h)
+      pass_actions(rem, n_act, [&](const int l, const int act) { a = lane == l ? act : a; });
 #if defined(MSB_STUDY_REPEAT)
       // study build only (scripts/step_cost.sh): the look-ahead step (or a prefix of it, MSB_STUDY_CUT_AT) and its clone
       // executed once more, so that the difference of two counter runs is the cost of exactly that
@@ -467,7 +463,6 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 #else
         if (active) ce.step(a);
 #endif
-        const int n_act = n_legal - base < U ? n_legal - base : U;
         __syncthreads();
         for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
