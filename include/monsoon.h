@@ -215,6 +215,46 @@ int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_ind
  * (150 us per game in numpy, 79 s for one C5 generation). */
 int monsoon_draw_decks(monsoon_t* h, const uint32_t* seeds, int32_t n, const uint8_t* pool, int32_t pool_n, uint8_t* out_pairs);
 
+/* Per-game decks of a deck schedule on the device (utils.py:121-242, DeckEvolutionConfig; the per-game mode of
+ * monsoon_amd/decks.py): for every game seed the pair that get_deck_configuration(generation) draws from a stream of the
+ * game's own -> out_pairs[n][2][12], P1's deck first.
+ *
+ * The stream is Python's generator, random.Random(seed | generation << 32 | game_seed << 64 | tag << 96): CPython seeds an
+ * int with init_by_array over its 32-bit words, here always the four words {seed, generation, game_seed, tag} since
+ * tag != 0 (the Python layer: 1 = evaluate_population, 2 = evaluate_vs_expert).  A game's pair depends on these four words
+ * and the schedule below, not on its place in game_seeds, on the device or rank, or on any other game.
+ *
+ * The draws, as Lib/random.py makes them (random: two outputs; _randbelow(n): u32 >> (32 - n.bit_length()) until < n;
+ * sample(pop, k): the pool path for len(pop) <= 21 (+ 64 for k > 5), else the set path):
+ *   phase 1 (explore), per side, P1 first: sample(archetype, n_preserve), then sample(pool, 12 - n_preserve); preserved
+ *           and new cards may repeat, as in the reference.  n_preserve = 12 is the archetype itself without a draw
+ *           (generate_random_deck with preserve_ratio == 1.0).  The caller computes n_preserve =
+ *           min(int(12 * (1.0 - ratio)), 12) in the reference's own float arithmetic; the device does none of it.
+ *   phase 2 (balance): random() < balance_archetype_ratio for P1, then for P2; then sample(pool, 12) for each side whose
+ *           test failed, P1 first; the other side plays its archetype.  n_preserve is ignored.
+ * The exploit phase draws nothing and has no phase number here.  pool[side][0..pool_n[side]) are card indices in
+ * available_cards order (utils.py:63-88), 12 <= pool_n <= 128: random.choices, which the reference falls back to for a
+ * pool of fewer than 12 cards, is not restated (no faction has such a pool).
+ *
+ * A game may use the first 624 outputs of its stream (one twist; the draws above took at most 90 in 72 000 test games).  Games that
+ * would need more are counted and the call fails with MONSOON_ERR_STATE: none is truncated silently.
+ * Host buffers in and out; needs no loaded games.  MONSOON_ERR_ARG: n <= 0, tag == 0, a phase other than 1 / 2,
+ * n_preserve outside 0..12, a pool size outside 12..128, an archetype or pool entry that is not a card index. */
+typedef struct {
+  uint32_t seed;         /* the schedule's seed, low 32 bits */
+  uint32_t generation;
+  uint32_t tag;          /* != 0 */
+  int32_t phase;         /* 1 explore, 2 balance */
+  int32_t n_preserve;    /* explore: archetype cards kept, 0..12 */
+  int32_t pool_n[2];
+  double balance_archetype_ratio;
+  uint8_t archetype[2][12];
+  uint8_t pool[2][128];
+} monsoon_deck_schedule;
+int monsoon_draw_schedule(monsoon_t* h, const monsoon_deck_schedule* schedule, const uint32_t* game_seeds, int32_t n, uint8_t* out_pairs);
+/* HIP-event time of the kernel inside the handle's last monsoon_draw_schedule call, without its copies (0 before one). */
+int monsoon_draw_schedule_time(monsoon_t* h, double* kernel_ms);
+
 /* GA operators on the device.  The host GA (monsoon_amd/population.py, as the reference's
  * evo/population.py) stays the default and the bit-exact path; these are the same operators over the same numpy stream
  * for a driver that wants the population to stay next to the rollouts.

@@ -60,6 +60,12 @@ class EnvAfter(ctypes.Structure):    # monsoon_env_after: caller-owned device bu
                                                       "before_features")]
 
 
+class DeckSchedule(ctypes.Structure):   # monsoon_deck_schedule
+    _fields_ = [("seed", ctypes.c_uint32), ("generation", ctypes.c_uint32), ("tag", ctypes.c_uint32), ("phase", ctypes.c_int32),
+                ("n_preserve", ctypes.c_int32), ("pool_n", ctypes.c_int32 * 2), ("balance_archetype_ratio", ctypes.c_double),
+                ("archetype", ctypes.c_uint8 * 24), ("pool", ctypes.c_uint8 * 256)]
+
+
 SIGNATURES = {
     "monsoon_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "monsoon_destroy": (None, [ctypes.c_void_p]),
@@ -97,6 +103,8 @@ SIGNATURES = {
                                                  ctypes.c_void_p]),
     "monsoon_rollout_faults": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_draw_decks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "monsoon_draw_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "monsoon_draw_schedule_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
     "monsoon_ga_offspring": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]),

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "deck_schedule.h"
 #include "env_after.h"
 #include "env_snap.h"
 #include "kernels.h"
@@ -504,6 +506,41 @@ __global__ void __launch_bounds__(64) k_draw_decks(int n, const uint32_t* seeds,
   if (over) atomicAdd(overrun, 1);
 }
 
+// monsoon_draw_schedule: the per-game decks of a deck schedule (deck_schedule.h restates the stream and the draws).  One
+// wavefront per game, like k_draw_decks.  init_by_array starts from init_genrand(19650218), the same 624 words for every
+// game: the host computes them once per handle (mt_init) and the wave copies them to LDS.  Lane 0 runs the two key-mixing
+// loops (624 + 623 dependent steps, serial by nature), one cooperative twist and the tempering (in place) leave the
+// stream's first 624 outputs in LDS, and lane 0 walks the draws over its own copy of the archetypes and pools.
+constexpr int DS_CARD_BYTES = 24 + 2 * DS_POOL_MAX;   // archetype[2][12] | pool[2][128], contiguous in monsoon_deck_schedule
+static_assert(sizeof(monsoon_deck_schedule) == 320 && offsetof(monsoon_deck_schedule, archetype) == 40 &&
+                  offsetof(monsoon_deck_schedule, pool) == 64,
+              "k_draw_schedule copies archetype and pool as one block");
+__global__ void __launch_bounds__(64) k_draw_schedule(int n, const monsoon_deck_schedule* sc, const uint32_t* mt_init, const uint32_t* game_seeds,
+                                                      uint32_t* out, int* overrun) {
+  __shared__ uint32_t mt[MT_N];
+  __shared__ uint8_t cards[DS_CARD_BYTES];
+  __shared__ uint32_t pair[6];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  if (g >= n) return;
+  for (int k = lane; k < MT_N; k += 64) mt[k] = mt_init[k];
+  const uint8_t* src = &sc->archetype[0][0];
+  for (int k = lane; k < DS_CARD_BYTES; k += 64) cards[k] = src[k];
+  __syncthreads();
+  if (lane == 0) {
+    const uint32_t key[4] = {sc->seed, sc->generation, game_seeds[g], sc->tag};
+    ds_key_mix(mt, key);
+  }
+  __syncthreads();
+  wave_twist_lds((MSB_AS_LDS uint32_t*)mt, lane);
+  for (int k = lane; k < MT_N; k += 64) mt[k] = mt_temper(mt[k]);
+  __syncthreads();
+  if (lane != 0) return;
+  DsStream s{mt, 0, 0};
+  ds_walk(s, sc->phase, sc->n_preserve, sc->balance_archetype_ratio, cards, cards + 24, sc->pool_n, (uint8_t*)pair);
+  for (int k = 0; k < 6; k++) out[(size_t)g * 6 + k] = pair[k];
+  if (s.over) atomicAdd(overrun, 1);
+}
+
 // the vector env (monsoon_env_reset / monsoon_env_step_dev)
 #include "env.inc"
 
@@ -694,6 +731,10 @@ struct monsoon {
   int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
   uint8_t* d_snap_flag = nullptr;   // [cap], inside d_env: the loaded flags of monsoon_env_load_dev when the caller keeps none
   int cu_count = 0;           // compute units of the device (queried once per handle)
+  // monsoon_draw_schedule: init_genrand(19650218), uploaded by the first call; the kernel's time in the last call
+  uint32_t* d_mt_init = nullptr;
+  hipEvent_t draw_ev[2] = {};
+  double draw_ms = 0;
 };
 
 static std::string g_create_error;
@@ -780,9 +821,11 @@ void monsoon_destroy(monsoon_t* h) {
   if (h->split_fork) hipEventDestroy(h->split_fork);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w};
+                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init};
   for (void* p : ptrs)
     if (p) hipFree(p);
+  for (hipEvent_t e : h->draw_ev)
+    if (e) hipEventDestroy(e);
   for (uint32_t* p : h->ovf_retired) hipFree(p);
   for (auto& pr : h->ev_pool) {
     hipEventDestroy(pr.first);
@@ -1021,6 +1064,91 @@ int monsoon_draw_decks(monsoon_t* h, const uint32_t* seeds, int32_t n, const uin
     return done(MONSOON_ERR_STATE);
   }
   return done(MONSOON_OK);
+}
+
+int monsoon_draw_schedule(monsoon_t* h, const monsoon_deck_schedule* sc, const uint32_t* game_seeds, int32_t n, uint8_t* out_pairs) {
+  if (!h || !sc || !game_seeds || !out_pairs || n <= 0 || sc->tag == 0 || (sc->phase != DS_EXPLORE && sc->phase != DS_BALANCE) ||
+      sc->n_preserve < 0 || sc->n_preserve > 12) {
+    if (h) h->err = "monsoon_draw_schedule: bad argument (n > 0, tag != 0, phase 1 or 2, 0 <= n_preserve <= 12)";
+    return MONSOON_ERR_ARG;
+  }
+  for (int side = 0; side < 2; side++) {
+    if (sc->pool_n[side] < 12 || sc->pool_n[side] > DS_POOL_MAX) {
+      h->err = "monsoon_draw_schedule: bad argument (12 <= pool_n <= 128)";
+      return MONSOON_ERR_ARG;
+    }
+    for (int i = 0; i < 12 + sc->pool_n[side]; i++)
+      if ((i < 12 ? sc->archetype[side][i] : sc->pool[side][i - 12]) >= NUM_CARDS) {
+        h->err = std::string("monsoon_draw_schedule: ") + (i < 12 ? "archetype" : "pool") + " entry " + std::to_string(i < 12 ? i : i - 12) + " of side " +
+                 std::to_string(side) + " is not a card index";
+        return MONSOON_ERR_ARG;
+      }
+  }
+  HIP_TRY(h, bind_device(h));
+  if (!h->d_mt_init) {
+    std::vector<uint32_t> mt(MT_N);   // init_genrand(19650218) (mt19937.h: mt_seed)
+    mt[0] = DS_INIT_SEED;
+    for (int i = 1; i < MT_N; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+    uint32_t* d = nullptr;
+    HIP_TRY(h, hipMalloc(&d, MT_N * 4));
+    hipError_t e = hipMemcpy(d, mt.data(), MT_N * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      hipFree(d);
+      h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+      return MONSOON_ERR_DEVICE;
+    }
+    h->d_mt_init = d;
+  }
+  for (hipEvent_t& e : h->draw_ev)
+    if (!e) HIP_TRY(h, hipEventCreate(&e));
+  uint32_t *d_seeds = nullptr, *d_out = nullptr;
+  monsoon_deck_schedule* d_sc = nullptr;
+  int* d_over = nullptr;
+  auto done = [&](int rc) {
+    hipFree(d_seeds);
+    hipFree(d_sc);
+    hipFree(d_out);
+    hipFree(d_over);
+    return rc;
+  };
+#define DS_TRY(call)                                                  \
+  do {                                                                \
+    hipError_t e_ = (call);                                           \
+    if (e_ != hipSuccess) {                                           \
+      h->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
+      return done(MONSOON_ERR_DEVICE);                                \
+    }                                                                 \
+  } while (0)
+  DS_TRY(hipMalloc(&d_seeds, (size_t)n * 4));
+  DS_TRY(hipMalloc(&d_sc, sizeof(monsoon_deck_schedule)));
+  DS_TRY(hipMalloc(&d_out, (size_t)n * 24));
+  DS_TRY(hipMalloc(&d_over, 4));
+  DS_TRY(hipMemcpyAsync(d_seeds, game_seeds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  DS_TRY(hipMemcpyAsync(d_sc, sc, sizeof(monsoon_deck_schedule), hipMemcpyHostToDevice, h->stream));
+  DS_TRY(hipMemsetAsync(d_over, 0, 4, h->stream));
+  DS_TRY(hipEventRecord(h->draw_ev[0], h->stream));
+  hipLaunchKernelGGL(k_draw_schedule, dim3(n), dim3(64), 0, h->stream, n, d_sc, h->d_mt_init, d_seeds, d_out, d_over);
+  DS_TRY(hipGetLastError());
+  DS_TRY(hipEventRecord(h->draw_ev[1], h->stream));
+  int over = 0;
+  float ms = 0;
+  DS_TRY(hipMemcpyAsync(out_pairs, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
+  DS_TRY(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, h->stream));
+  DS_TRY(hipStreamSynchronize(h->stream));
+  DS_TRY(hipEventElapsedTime(&ms, h->draw_ev[0], h->draw_ev[1]));
+#undef DS_TRY
+  h->draw_ms = ms;
+  if (over) {
+    h->err = "monsoon_draw_schedule: " + std::to_string(over) + " game(s) needed more than 624 outputs of their stream";
+    return done(MONSOON_ERR_STATE);
+  }
+  return done(MONSOON_OK);
+}
+
+int monsoon_draw_schedule_time(monsoon_t* h, double* kernel_ms) {
+  if (!h || !kernel_ms) return MONSOON_ERR_ARG;
+  *kernel_ms = h->draw_ms;
+  return MONSOON_OK;
 }
 
 int monsoon_ga_offspring(monsoon_t* h, monsoon_np_state* st, const double* parents_w, const double* parents_s, int32_t mu, int32_t dim,

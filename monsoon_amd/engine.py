@@ -297,6 +297,30 @@ class BatchEngine:
             self._ck(self.lib.monsoon_draw_decks(self.h, _ptr(seeds), len(seeds), _ptr(pool), len(pool), _ptr(out)), "monsoon_draw_decks")
         return out
 
+    def draw_schedule(self, params, game_seeds):
+        """uint8[n][2][12]: the per-game decks of a deck schedule, drawn on the device (monsoon_draw_schedule).  params:
+        DeckEvolutionConfig.schedule_params(generation, tag), or a dict of the same fields; game_seeds: uint32[n].  Every
+        pair equals DeckEvolutionConfig.game_decks(generation, game_seed, tag)."""
+        from ._lib import DeckSchedule
+        game_seeds = np.ascontiguousarray(game_seeds, dtype=np.uint32)
+        arch = np.ascontiguousarray(params["archetype"], dtype=np.uint8)
+        pool = np.ascontiguousarray(params["pool"], dtype=np.uint8)
+        if arch.shape != (2, 12) or pool.shape != (2, 128):
+            raise ValueError(f"archetype must be [2][12] and pool [2][128], got {arch.shape} and {pool.shape}")
+        sc = DeckSchedule(int(params["seed"]), int(params["generation"]), int(params["tag"]), int(params["phase"]), int(params["n_preserve"]),
+                          (ctypes.c_int32 * 2)(*[int(v) for v in params["pool_n"]]), float(params["balance_archetype_ratio"]))
+        ctypes.memmove(sc.archetype, arch.ctypes.data, 24)
+        ctypes.memmove(sc.pool, pool.ctypes.data, 256)
+        out = np.zeros((len(game_seeds), 2, 12), dtype=np.uint8)
+        self._ck(self.lib.monsoon_draw_schedule(self.h, ctypes.byref(sc), _ptr(game_seeds), len(game_seeds), _ptr(out)), "monsoon_draw_schedule")
+        return out
+
+    def draw_schedule_time(self):
+        """ms of the kernel inside the last draw_schedule call (HIP events; the call's copies are not in it)."""
+        ms = ctypes.c_double()
+        self._ck(self.lib.monsoon_draw_schedule_time(self.h, ctypes.byref(ms)), "monsoon_draw_schedule_time")
+        return ms.value
+
     # ---- GA operators on the device (SURVEY §8f rank 4; the host GA stays the default) -------------------------
     def ga_offspring(self, np_state, parents_w, parents_s, n_offspring, tau, tau_prime, min_sigma):
         """Population.generate_offspring on the device over numpy's global stream.  np_state: RandomState.get_state()

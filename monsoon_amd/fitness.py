@@ -202,7 +202,7 @@ def tiered_rollout(play, n_rows, matches, deck_pairs, concurrent=False):
 
 
 class FitnessEvaluator:
-    def __init__(self, config, deck_config=None, rollout_fn=None, device=None, deck_draw_fn=None, strict=False):
+    def __init__(self, config, deck_config=None, rollout_fn=None, device=None, deck_draw_fn=None, strict=False, schedule_draw_fn=None):
         self.config = config
         self.deck_config = deck_config      # monsoon_amd.decks.DeckEvolutionConfig (utils.py:121-242) or None = config.deck both sides
         self.total_games = 0
@@ -214,6 +214,7 @@ class FitnessEvaluator:
         self.use_hall_of_fame = True
         self._rollout_fn = rollout_fn
         self._deck_draw_fn = deck_draw_fn   # test hook like rollout_fn: (pre-stream seeds, pool) -> uint8[n][2][12]
+        self._schedule_draw_fn = schedule_draw_fn   # likewise for a per-game deck schedule: (schedule_params, game seeds) -> uint8[n][2][12]
         self._device = device
         self._engines = {}
         self.eval_times = []            # wall seconds of every evaluate_population call (the first one creates the engine)
@@ -284,10 +285,11 @@ class FitnessEvaluator:
         self.last_rollout = (results, steps, faults)
         return counts
 
-    def _decks_for(self, matches, generation):
+    def _decks_for(self, matches, generation, tag=1):
         """Deck pairs [n_decks][2][12] for a schedule; fills matches["deck"].  Without a deck_config: config.deck both
         sides.  With one: utils.py:155-219 per GAME, as games/evolutionary_stormbound.py:52 draws them (one pair for
-        the whole generation while the schedule is in its exploit phase)."""
+        the whole generation while the schedule is in its exploit phase).  tag: the stream tag of a per-game deck_config
+        (decks.TAG_POPULATION / TAG_EXPERT), unused otherwise."""
         from .cards import C5_STREAM_XOR, RANDOM_DECK, deck_indices, draw_random_decks_numpy, observable_pool
         if self.deck_config is None and self.config.deck == RANDOM_DECK:
             # configuration C5: two decks per game from the 109 observable cards, drawn by the game's own pre-stream
@@ -304,11 +306,23 @@ class FitnessEvaluator:
         if self.deck_config.is_static(generation):
             d1, d2 = self.deck_config.get_deck_configuration(generation)
             return np.stack([deck_indices(d1), deck_indices(d2)])[None]
+        matches["deck"] = np.arange(len(matches))
         pairs = np.zeros((len(matches), 2, 12), dtype=np.uint8)
+        if self.deck_config.per_game:
+            # every game draws from a stream of its own (decks.game_decks): on the device, unless a stand-in plays the games
+            # or the schedule is one the device entry does not take (schedule_params is None: the host draw stays)
+            params = self.deck_config.schedule_params(generation, tag)
+            if params is not None and self._schedule_draw_fn is not None:
+                return self._schedule_draw_fn(params, matches["seed"])
+            if params is not None and self._rollout_fn is None:
+                return self._engine(0).draw_schedule(params, matches["seed"])
+            for k, seed in enumerate(matches["seed"]):
+                d1, d2 = self.deck_config.game_decks(generation, seed, tag)
+                pairs[k, 0], pairs[k, 1] = deck_indices(d1), deck_indices(d2)
+            return pairs
         for k in range(len(matches)):
             d1, d2 = self.deck_config.get_deck_configuration(generation)
             pairs[k, 0], pairs[k, 1] = deck_indices(d1), deck_indices(d2)
-        matches["deck"] = np.arange(len(matches))
         return pairs
 
     @staticmethod
@@ -347,7 +361,7 @@ class FitnessEvaluator:
             from .cards import RANDOM_DECK
             dist = self._dist()
             mine = matches
-            if self.deck_config is None and cfg.deck == RANDOM_DECK:
+            if (self.deck_config is None and cfg.deck == RANDOM_DECK) or (self.deck_config is not None and self.deck_config.per_game):
                 # per-game decks that depend on the game's seed alone: every rank draws only the games it plays
                 if dist is not None:
                     mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size()).copy()
@@ -379,7 +393,8 @@ class FitnessEvaluator:
         of expert_schedule; returns its score (wins + 0.5 * draws) / games.  self.last_vs_expert keeps the raw
         counts[n][3] = {wins, draws, games}.  Decks, tiers, sharding and the all-reduce are evaluate_population's; the hall
         of fame, the total_* statistics and a DeckEvolutionConfig's sequential stream are left alone, so the fitness
-        evaluate_population returns does not depend on whether this was called."""
+        evaluate_population returns does not depend on whether this was called.  In a random phase of a deck schedule the
+        games play the schedule's own decks if it is a per_game=True one (stream tag 2), random109 decks otherwise."""
         from .cards import RANDOM_DECK
         cfg = self.config
         n = len(population)
@@ -392,17 +407,19 @@ class FitnessEvaluator:
         mine = matches
         if dist is not None:
             mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size()).copy()
-        per_game = self.deck_config is not None and not self.deck_config.is_static(generation)
-        if per_game:
-            # The random phase of a DeckEvolutionConfig draws every game's decks from ONE sequential stream: drawing from it
+        from .decks import TAG_EXPERT
+        detour = self.deck_config is not None and not self.deck_config.is_static(generation) and not self.deck_config.per_game
+        if detour:
+            # The random phase of a sequential DeckEvolutionConfig draws every game's decks from ONE stream: drawing from it
             # here would change the decks of the next evaluate_population.  These games take their decks as configuration C5
-            # does instead, each from its own seed's pre-stream.
+            # does instead, each from its own seed's pre-stream.  (A per_game=True schedule has no such stream: its games
+            # play the schedule's own decks, drawn with the stream tag of this call.)
             deck_config, deck, self.deck_config = self.deck_config, cfg.deck, None
             cfg.deck = RANDOM_DECK
         try:
-            deck_pairs = self._decks_for(mine, generation) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
+            deck_pairs = self._decks_for(mine, generation, TAG_EXPERT) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
         finally:
-            if per_game:
+            if detour:
                 self.deck_config, cfg.deck = deck_config, deck
         fn = self._rollout_fn or self._hip_rollout
         counts = np.zeros((n, 3), dtype=np.int64)
