@@ -5,6 +5,10 @@ generation 0) -> FitnessEvaluator.evaluate_population -> assign / (mu+lambda) se
 training_log.csv row -> periodic checkpoint; then results_summary.txt.  With config.expert_eval_interval
 the parents also play the reference's scripted bot every that many generations (evaluate_vs_expert):
 co-evolutionary fitness is relative, the bot is the yardstick that stays put.
+
+As ranks of a torch.distributed job every rank runs the whole loop over the same numpy stream: the evaluator shards the
+games and sums the counters, so all ranks hold the same populations and return the same results.  Rank 0 alone prints
+and writes the run's files.
 """
 import os
 import time
@@ -65,7 +69,16 @@ class EvolutionEngine:
                 self._save_checkpoint()
         return self._finalize_training(time.time() - self.start_time)
 
+    @staticmethod
+    def _writes():
+        """True in a single process and on rank 0 of a job of several: the one process that prints and writes the run's files
+        (found as FitnessEvaluator._dist finds the job: torch.distributed is never imported here)."""
+        dist = FitnessEvaluator._dist()
+        return dist is None or dist.get_rank() == 0
+
     def _log_generation(self, generation_time, vs_expert=None):
+        if not self._writes():
+            return
         stats = self.population.get_population_stats()
         ev = self.fitness_evaluator.get_stats()
         print(f"gen {stats['generation']}: best {stats['best_fitness']:.4f} mean {stats['mean_fitness']:.4f} "
@@ -85,6 +98,8 @@ class EvolutionEngine:
                     + ((f",{vs_expert[0]:.6f},{vs_expert[1]:.6f}" if vs_expert else ",,") if self.config.expert_eval_interval else "") + "\n")
 
     def _save_checkpoint(self):
+        if not self._writes():
+            return
         stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
         self.population.save_population(os.path.join(self.results_dir, f"checkpoint_gen{self.population.generation}_{stamp}.pkl"))
 
@@ -92,14 +107,16 @@ class EvolutionEngine:
         stats = self.population.get_population_stats()
         best, best_fitness = self.population.get_best_individual()
         final = os.path.join(self.results_dir, "final_population.pkl")
-        self.population.save_population(final)
+        if self._writes():
+            self.population.save_population(final)
         results = {"total_time": total_time, "generations": self.population.generation, "final_stats": stats,
                    "best_fitness": best_fitness, "best_weights": best.get_weights().tolist(),
                    "evaluation_stats": self.fitness_evaluator.get_stats(), "final_population_file": final}
-        with open(os.path.join(self.results_dir, "results_summary.txt"), "w") as f:
-            f.write(f"generations {self.population.generation}\nbest_fitness {best_fitness:.6f}\n")
-            for name, w in zip(FEATURE_NAMES, best.get_weights()):
-                f.write(f"{name} {w:.6f}\n")
+        if self._writes():
+            with open(os.path.join(self.results_dir, "results_summary.txt"), "w") as f:
+                f.write(f"generations {self.population.generation}\nbest_fitness {best_fitness:.6f}\n")
+                for name, w in zip(FEATURE_NAMES, best.get_weights()):
+                    f.write(f"{name} {w:.6f}\n")
         return results
 
     def load_checkpoint(self, checkpoint_file):

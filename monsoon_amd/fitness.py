@@ -207,8 +207,10 @@ class FitnessEvaluator:
         self.deck_config = deck_config      # monsoon_amd.decks.DeckEvolutionConfig (utils.py:121-242) or None = config.deck both sides
         self.total_games = 0
         self.total_time = 0.0
-        self.total_env_steps = 0
+        self.total_env_steps = 0        # this rank's own look-ahead steps and decisions (bench.py sums them over ranks itself) ...
         self.total_decisions = 0
+        self.job_env_steps = 0          # ... and every rank's, summed in the evaluation's one all_reduce: what get_stats reports
+        self.job_decisions = 0          #     (a single process: the same figures)
         self.hall_of_fame = []
         self.hall_of_fame_size = 5
         self.use_hall_of_fame = True
@@ -376,10 +378,15 @@ class FitnessEvaluator:
                         mine["deck"] = np.arange(len(mine))
             fn = self._rollout_fn or self._hip_rollout
             counts = np.zeros((n_total, 3), dtype=np.int64)
+            before = self.total_env_steps, self.total_decisions
             if len(mine):
                 counts += np.asarray(fn(weights, mine, deck_pairs, cfg.max_turns), dtype=np.int64)
+            played = [self.total_env_steps - before[0], self.total_decisions - before[1], 0]
             if dist is not None:
-                counts = self._all_reduce_counts(dist, counts)
+                # this rank's env-steps and decisions ride along as one more row: still one collective per evaluation
+                counts, played = self._all_reduce_counts(dist, counts, played)
+            self.job_env_steps += int(played[0])
+            self.job_decisions += int(played[1])
         self.total_games += len(matches)
         self.total_time += time.time() - start
         self.eval_times.append(time.time() - start)
@@ -433,13 +440,18 @@ class FitnessEvaluator:
         return fitness_from_counts(counts, games)
 
     @staticmethod
-    def _all_reduce_counts(dist, counts):
+    def _all_reduce_counts(dist, counts, extra=None):
+        """counts[n][3] summed over ranks; with extra (three integers of this rank) appended as a last row of the same
+        tensor, (summed counts, summed extra)."""
         import torch
+        if extra is not None:
+            counts = np.concatenate([np.asarray(counts, dtype=np.int64), np.asarray(extra, dtype=np.int64).reshape(1, 3)])
         t = torch.from_numpy(np.ascontiguousarray(counts))
         if dist.get_backend() == "nccl":   # RCCL: the tensor must live on this rank's GPU
             t = t.cuda()
         dist.all_reduce(t)   # sum over ranks; <= 48 KB at N = 4096
-        return t.cpu().numpy()
+        out = t.cpu().numpy()
+        return out if extra is None else (out[:-1], out[-1])
 
     # evo/fitness.py:247-259: copies of the five best of this generation
     def _update_hall_of_fame(self, population, fitness):
@@ -450,9 +462,9 @@ class FitnessEvaluator:
         return {"total_games": self.total_games, "total_time": self.total_time,
                 "avg_time_per_game": self.total_time / max(self.total_games, 1),
                 "games_per_second": self.total_games / max(self.total_time, 1e-6),
-                "env_steps": self.total_env_steps, "capacity_replays": self.capacity_replays, "capacity_faults": self.capacity_faults,
+                "env_steps": self.job_env_steps, "capacity_replays": self.capacity_replays, "capacity_faults": self.capacity_faults,
                 "depth_faults": self.depth_faults,
-                "env_steps_per_second": self.total_env_steps / max(self.total_time, 1e-6)}
+                "env_steps_per_second": self.job_env_steps / max(self.total_time, 1e-6)}
 
     def kernel_time(self):
         """(ms, launches) of the hot kernel over every engine this evaluator has created (HIP events on their streams)."""
@@ -468,6 +480,8 @@ class FitnessEvaluator:
         self.total_time = 0.0
         self.total_env_steps = 0
         self.total_decisions = 0
+        self.job_env_steps = 0
+        self.job_decisions = 0
         for eng in self._engines.values():
             if eng is not None:
                 eng.reset_stats()

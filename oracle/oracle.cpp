@@ -347,7 +347,7 @@ uint64_t orc_rollout_batch(void* h, int n, const double* w, int max_turns, int n
 
 // A whole schedule of rollouts on n_threads host threads (the CPU side of the large GPU-vs-CPU comparisons): match k =
 // {p1, p2, seed, deck} plays weights[p1] against weights[p2] on deck pair deck_pairs[deck]; per match: result, decisions,
-// the fault orc_game_fault reports.  Returns the total look-ahead steps.
+// the fault monsoon_rollout_faults reports.  Returns the total look-ahead steps.
 struct OrcMatch {
   int32_t p1, p2;
   uint32_t seed, deck;
@@ -370,7 +370,10 @@ uint64_t orc_rollout_schedule(const double* weights, const OrcMatch* matches, in
       if (orc_reset(h, 0, m.seed, d, d + 12, 0, 0) == 0) r = orc_rollout(h, 0, weights + (size_t)m.p1 * 10, weights + (size_t)m.p2 * 10, max_turns, nullptr, nullptr, &ns, &nl, &fl);
       results[i] = (int8_t)r;
       steps[i] = ns;
-      faults[i] = (uint8_t)orc_game_fault(h, 0);
+      // monsoon_rollout_faults: a committed step whose observation raises stops the game too (FAULT_INT_CARD, a code the
+      // record does not hold: the rollout's own), unless the game has a code of its own to report
+      int gf = orc_game_fault(h, 0);
+      faults[i] = (uint8_t)((gf == 0 && fl) ? fl : gf);
       mine += nl;
     }
     total += mine;

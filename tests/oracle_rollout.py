@@ -8,9 +8,10 @@ import oracle_lib
 THREADS = 1   # host threads of oracle_rollout_tier (oracle_rollout_fn_mt raises it)
 
 
-def oracle_rollout_tier(weights, matches, deck_pairs, max_turns, tier, threads=None):
+def oracle_rollout_tier(weights, matches, deck_pairs, max_turns, tier, threads=None, want_lookahead=False):
     """(counts, results, steps, faults) of the schedule on ONE build of the oracle (tier 0 standard, 1 extended, 2 large):
-    orc_rollout_schedule, a loop over the matches on `threads` host threads inside the oracle library."""
+    orc_rollout_schedule, a loop over the matches on `threads` host threads inside the oracle library.  want_lookahead: a
+    fifth element, the look-ahead steps of all its games (what monsoon_get_stats calls lookahead_steps)."""
     import ctypes
     weights = np.ascontiguousarray(weights, dtype=np.float64)
     deck_pairs = np.ascontiguousarray(np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12))
@@ -23,12 +24,15 @@ def oracle_rollout_tier(weights, matches, deck_pairs, max_turns, tier, threads=N
     steps = np.zeros(len(m), dtype=np.int32)
     faults = np.zeros(len(m), dtype=np.uint8)
     p = oracle_lib._p
+    lookahead = 0
     if len(m):
-        L.orc_rollout_schedule(p(weights), p(m), len(m), p(deck_pairs), max_turns, threads or THREADS, p(results), p(steps), p(faults))
+        lookahead = L.orc_rollout_schedule(p(weights), p(m), len(m), p(deck_pairs), max_turns, threads or THREADS, p(results), p(steps), p(faults))
     counts = np.zeros((len(weights), 3), dtype=np.int64)
     np.add.at(counts[:, 0], m["p1"], results == 0)
     np.add.at(counts[:, 1], m["p1"], results == -1)
     np.add.at(counts[:, 2], m["p1"], 1)
+    if want_lookahead:
+        return counts, results, steps, faults, int(lookahead)
     return counts, results, steps, faults
 
 

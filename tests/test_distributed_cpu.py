@@ -5,6 +5,7 @@ import os
 import socket
 
 import numpy as np
+import pytest
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
@@ -184,3 +185,95 @@ def test_replace_capacity_faulted_rewrites_only_the_overflowing_rows():
     assert faults.tolist() == [0, 0, 0, 16, 1, 0]                  # what not even the replay could hold stays flagged
     assert counts.tolist() == [[2, 0, 2], [0, 0, 2], [1, 1, 2]]
     assert replace_capacity_faulted(counts, results, steps, np.zeros(6, dtype=np.uint8), m, replay) == 0
+
+
+# ---- the job shapes of tests/test_sharded_gpu.py without a GPU: world 2 and 3, gloo, every rank on the CPU oracle ---------------
+# A clean job takes 4 s of wall time (either world size; most of it three Python starts) where these tests were written.  The
+# launcher ends a job after five times CLEAN_JOB_SECONDS, a figure three times the measured one for a slower test machine.
+CLEAN_JOB_SECONDS = 12
+
+
+def _job(world, tmp_path_factory):
+    import sharded_job as J
+    out_dir = tmp_path_factory.mktemp(f"world{world}")
+    _, ranks = J.run_job(world, "oracle", out_dir, CLEAN_JOB_SECONDS)
+    return world, str(out_dir), ranks
+
+
+@pytest.fixture(scope="module")
+def job2(tmp_path_factory):
+    """(world, out_dir, rank files) of the one two-rank job, which ran every scenario of tests/sharded_job.py and the GA loop."""
+    return _job(2, tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def job3(tmp_path_factory):
+    return _job(3, tmp_path_factory)
+
+
+@pytest.fixture(params=[2, 3])
+def job(request):
+    return request.getfixturevalue(f"job{request.param}")
+
+
+def test_every_sharded_evaluation_equals_the_single_process_replay(job):
+    """Ring with a fixed deck, configuration C5's decks, both modes of a deck schedule with the bot's games, and the rest
+    below, each at world 2 and 3: fitness on every rank, every rank's block of games and deck pairs, the rows put back in
+    schedule order and the counters summed over the ranks equal the single process's; get_stats' env-steps are the
+    job's, on every rank, while total_env_steps stays the rank's own."""
+    import sharded_job as J
+    world, _, ranks = job
+    for key in J.EVALUATIONS:
+        total = J.check_evaluation(ranks, key)
+        if not key.startswith("pg_vs"):
+            assert total[J.COUNTERS.index("total_env_steps")] > 1000 and max(int(g[key + ".counters"][5]) for g in ranks) < total[5]
+
+
+def test_round_robin_with_a_hall_of_fame_sharded(job):
+    """4 individuals, 2 games per pairing, generations 1 and 2: the second one's 56 games hold 32 against the hall of fame
+    (p2 >= 4; 28 games per rank at world 2).  Both generations' fitness and the hall's weights equal the replay's."""
+    import sharded_job as J
+    world, _, ranks = job
+    m = np.concatenate([g["hall_gen2.matches"] for g in ranks])
+    assert len(m) == 56 and int((m[:, 1] >= 4).sum()) == 32 and len(np.concatenate([g["hall_gen1.matches"] for g in ranks])) == 24
+    assert [len(g["hall_gen2.matches"]) for g in ranks] == ([28, 28] if world == 2 else [14, 14, 28])
+    for key in ("hall_gen1", "hall_gen2"):
+        J.check_evaluation(ranks, key)
+        assert all(g[key + ".hall"].shape == (4, 10) for g in ranks)
+    assert len(set(J.reference()["hall_gen2.fitness"].tolist())) > 1
+
+
+def test_mixed_tier_schedule_counts_sharded(job):
+    """Configuration C5 on the 5 x 6 ring: every rank's shard has games on both records (sizes asserted from numpy's own
+    draws), each rank runs the tier ladder and _uncount on its shard, and tier sizes, replays and faults add up to the
+    single process's, with the two tiers played from two host threads and one after the other."""
+    import sharded_job as J
+    world, _, ranks = job
+    assert J.c5_shards_by_numpy(world) == J.C5_SHARDS[world]
+    for key in ("c5_on", "c5_off"):
+        assert [(int(g[key + ".counters"][0] + g[key + ".counters"][1]), int(g[key + ".counters"][1])) for g in ranks] == J.C5_SHARDS[world]
+        total = J.check_evaluation(ranks, key)
+        assert total[:2].tolist() == [15, 15]
+    assert all(np.array_equal(g["c5_on.results"], g["c5_off.results"]) and np.array_equal(g["c5_on.steps"], g["c5_off.steps"]) for g in ranks)
+
+
+def test_rank_without_a_game_still_joins_the_reduce(job):
+    """2 individuals: at world 3 rank 0 has no game, plays none, and returns the same fitness."""
+    import sharded_job as J
+    world, _, ranks = job
+    J.check_evaluation(ranks, "empty")
+    assert [len(g["empty.matches"]) for g in ranks] == ([6, 6] if world == 2 else [0, 6, 6])
+
+
+def test_ga_loop_under_two_ranks_has_one_writer(job2):
+    """EvolutionEngine as two ranks sharing one results_dir: one header and one row per generation in training_log.csv
+    (every column but time and throughput equal to the single process's file), one checkpoint, one final_population.pkl
+    equal to the single process's, one results_summary.txt; both ranks hold the single process's populations after
+    every generation and return its best_fitness, best_weights and generations."""
+    import sharded_job as J
+    _, out_dir, ranks = job2
+    ref = J.reference()
+    J.check_ga_files(os.path.join(out_dir, "ga_off"), ref["ga_dir"])
+    J.check_ga_runs([(ref, "ga_off"), (ranks[0], "ga_off"), (ranks[1], "ga_off")])
+    own = [int(g["ga_off.stats"][2]) for g in ranks]
+    assert all(int(g["ga_off.stats"][0]) == sum(own) == int(ref["ga_off.stats"][0]) for g in ranks) and min(own) > 0
