@@ -232,7 +232,8 @@ int monsoon_draw_decks(monsoon_t* h, const uint32_t* seeds, int32_t n, const uin
  *           min(int(12 * (1.0 - ratio)), 12) in the reference's own float arithmetic; the device does none of it.
  *   phase 2 (balance): random() < balance_archetype_ratio for P1, then for P2; then sample(pool, 12) for each side whose
  *           test failed, P1 first; the other side plays its archetype.  n_preserve is ignored.
- * The exploit phase draws nothing and has no phase number here.  pool[side][0..pool_n[side]) are card indices in
+ * The exploit phase draws nothing and monsoon_draw_schedule refuses its phase number (0; monsoon_env_set_schedule takes
+ * it).  pool[side][0..pool_n[side]) are card indices in
  * available_cards order (utils.py:63-88), 12 <= pool_n <= 128: random.choices, which the reference falls back to for a
  * pool of fewer than 12 cards, is not restated (no faction has such a pool).
  *
@@ -244,7 +245,7 @@ typedef struct {
   uint32_t seed;         /* the schedule's seed, low 32 bits */
   uint32_t generation;
   uint32_t tag;          /* != 0 */
-  int32_t phase;         /* 1 explore, 2 balance */
+  int32_t phase;         /* 1 explore, 2 balance; 0 static (monsoon_env_set_schedule only): both sides play their archetype */
   int32_t n_preserve;    /* explore: archetype cards kept, 0..12 */
   int32_t pool_n[2];
   double balance_archetype_ratio;
@@ -284,7 +285,8 @@ int monsoon_ga_select(monsoon_t* h, const double* fitness, int32_t n, int32_t* o
 
 /* Diagnostics: 192 raw counter words (words 0-4 back monsoon_get_stats; words 6 / 7 count the vector env's committed
  * agent / opponent steps since monsoon_env_reset, word 7 those of either opponent kind, scripted bot or heuristic agent;
- * word 16 the heuristic opponent's look-ahead transitions since monsoon_env_reset; a profiling build (-DMSB_PROF=1,
+ * word 16 the heuristic opponent's look-ahead transitions since monsoon_env_reset; word 17 the episodes of a schedule-mode
+ * env since monsoon_env_reset whose deck walk ran past the 624 outputs of its stream (monsoon_env_set_schedule); a profiling build (-DMSB_PROF=1,
  * scripts only) adds k_decide phase cycles at 8..15, per-function cycles / calls at 32..63 / 64..95, last-launch
  * occupancy at 96..101 and call entry / exit cycles at 128..159 / 160..191; the rest is zero).
  * No reference counterpart. */
@@ -326,7 +328,9 @@ void* monsoon_stream(monsoon_t* h);
  * Episode k of slot i starts from seed seed0[i] + k * seed_stride (mod 2^32).  Without a pool it is
  * monsoon_reset(seed, decks[i], factions) with factions[i] for episode 0 and {0, 0} (monsoon_reset's NULL factions) for
  * the later ones; episode 0 equals monsoon_reset(seed0[i], decks[i], factions[i]) bit for bit.  With a pool, every
- * episode (episode 0 included) plays the decks monsoon_draw_decks draws from seed ^ 0x9E3779B9 (configuration C5).
+ * episode (episode 0 included) plays the decks monsoon_draw_decks draws from seed ^ 0x9E3779B9 (configuration C5).  Without
+ * decks and without a pool -- schedule mode, after monsoon_env_set_schedule -- every episode (episode 0 included) plays the
+ * pair the handle's deck schedule draws for its seed, see there; factions as without a pool.
  *
  * An episode ends after a committed step (the agent's or the bot's) that faults, whose observation would raise
  * (FAULT_INT_CARD: the reference's step returns get_observation()), that leaves a winner (have_winner), or that brings its
@@ -348,7 +352,8 @@ typedef struct {
   int32_t agent_side;    /* with opponent 1 or 2: 0 = agent plays FIRST, 1 = SECOND (the opponent plays the other side) */
   uint32_t seed_stride;  /* episode k of slot i starts from seed0[i] + k * seed_stride (mod 2^32); 0 = n */
   int32_t max_steps;     /* an episode reaching this many committed steps (agent + bot) ends truncated; 0 = no limit, <= 65535 */
-  int32_t pool_n;        /* 0 = every episode of slot i uses the slot's reset decks; 12..128 = fresh decks per episode */
+  int32_t pool_n;        /* 0 = every episode of slot i uses the slot's reset decks (NULL decks: the handle's schedule draws
+                            them per episode, monsoon_env_set_schedule); 12..128 = fresh decks per episode */
   uint8_t pool[128];     /*   drawn as monsoon_draw_decks draws them, from the episode seed ^ 0x9E3779B9 */
 } monsoon_env_config;
 
@@ -370,7 +375,8 @@ typedef struct {          /* caller-owned DEVICE buffers, n entries each; any ma
 /* Allocates the env's workspace, binds the views (kept until the next monsoon_env_reset), loads episode 0 of every slot
  * (with opponent 1 and agent_side 1 the bot's opening turn is played) and writes its observation and legal mask; the
  * per-call views read as after a step that ended nothing.  Host arguments: seed0[n], decks[n][2][12] (NULL, and only NULL,
- * with a pool), factions[n][2] or NULL.  A deck or pool card this build does not support is refused (MONSOON_ERR_ARG).
+ * with a pool; NULL without a pool = schedule mode, MONSOON_ERR_ARG unless the handle holds a schedule), factions[n][2] or
+ * NULL.  A deck or pool card this build does not support is refused (MONSOON_ERR_ARG).
  * Synchronises.  The env's slots are the handle's loaded games: monsoon_state_hash, monsoon_observe, monsoon_state_save
  * and the rest work on them; monsoon_reset or monsoon_rollout ends env mode. */
 int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon_env_views* views, int32_t n,
@@ -390,6 +396,49 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev);
  * reallocated while an opponent-2 env is loaded, so a captured step stays valid: a call with more rows then, a row outside
  * [0, n_individuals) or an n different from the loaded env's returns MONSOON_ERR_ARG.  Synchronises. */
 int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_individuals, const int32_t* rows, int32_t n);
+
+/* Schedule mode: the third source of episode decks, beside the reset decks and the pool.  The handle keeps ONE deck schedule
+ * in a device buffer that is allocated by the first call and never moved while an env is loaded.  monsoon_env_reset with
+ * decks == NULL and pool_n == 0 plays schedule mode if the handle holds a schedule (MONSOON_ERR_ARG otherwise); with decks
+ * or a pool it plays as ever and ignores the stored schedule.
+ *
+ * Episode k of slot i starts from s = seed0[i] + k * seed_stride as in the other modes.  Its decks are the pair
+ * get_deck_configuration(generation) draws from random.Random(seed | generation << 32 | s << 64 | tag << 96): the
+ * monsoon_draw_schedule contract above, keyed by the episode's seed, with seed, generation, tag, phase, n_preserve, ratio,
+ * archetypes and pools those of the schedule the handle holds AT THE MOMENT THE EPISODE STARTS, drawn on the device by the
+ * kernel that seeds the episode.  Episode 0 draws too.  The Python layer uses tag 3 (decks.TAG_ENV), so that an env episode
+ * never shares its decks with the population's (1) or the bot's (2) game of the same seed.  Factions: factions[i] for
+ * episode 0, {0, 0} afterwards.  Episode rules, opponents, afterstates and snapshots are those of the other modes: a
+ * restored slot keeps the decks of its entry until that episode ends and then draws from the schedule current then, with the
+ * destination's seed.
+ *
+ * Phase 0 (static; here only, monsoon_draw_schedule refuses it) is the schedule's exploit phase: both sides play their
+ * archetype, no stream is read, n_preserve, pool_n and pool are ignored.
+ *
+ * monsoon_env_set_schedule(sc != NULL) validates, stores the schedule behind everything already enqueued on the handle's
+ * stream, and synchronises.  With a schedule-mode env loaded the new schedule applies to every episode that starts from the
+ * next monsoon_env_step_dev on -- also a captured one: the graph holds the buffer's address, not its contents -- while
+ * running episodes keep their decks.  MONSOON_ERR_ARG: tag == 0, a phase outside 0..2, n_preserve outside 0..12, in phases
+ * 1 / 2 a pool size outside 12..128, an archetype entry or (phases 1 / 2) a pool entry that is not a card index or that
+ * this record build does not support (ua20 and b005 need the extended record; every faction's pool holds ua20).
+ * sc == NULL clears the schedule; MONSOON_ERR_STATE while a schedule-mode env is loaded.
+ *
+ * A walk that would read past the first 624 outputs of its stream cannot fail an asynchronous step: such an episode is
+ * counted (monsoon_debug_counters word 17, per env since monsoon_env_reset) and plays a pair of valid card indices that is
+ * not the specification's draw.  No test game came near (at most 90 outputs). */
+int monsoon_env_set_schedule(monsoon_t* h, const monsoon_deck_schedule* schedule);
+
+/* The decks of every slot's current episode -> out_dev, uint8[n][2][12] of caller-owned DEVICE memory, P1's deck first: what
+ * a learner on drawn decks is playing (the observation shows the hand, not the deck).  All three deck modes.  One
+ * device-to-device copy on the handle's stream: asynchronous, no allocation or synchronisation, capturable.
+ * MONSOON_ERR_STATE without a loaded env, MONSOON_ERR_ARG for a NULL out_dev. */
+int monsoon_env_decks_dev(monsoon_t* h, void* out_dev);
+
+/* Measurement: the HIP-event time of the reseed kernel -- the launch that seeds, and in pool and schedule mode draws the
+ * decks of, the episodes that start -- inside the handle's last monsoon_env_step_dev -> *kernel_ms (0 if that step was not
+ * timed).  enable != 0: every later step records an event pair round that launch (two host calls per step; never while the
+ * stream is being captured); enable == 0 stops that.  Off by default.  Synchronises.  MONSOON_ERR_ARG for a NULL argument. */
+int monsoon_env_reseed_time(monsoon_t* h, int32_t enable, double* kernel_ms);
 
 /* Afterstates: the successor of every legal action of every slot's current state, for a learner that evaluates them
  * itself (afterstate TD, a value network over the successor's observation).  It is the reference's 1-ply look-ahead

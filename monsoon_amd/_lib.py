@@ -123,6 +123,9 @@ SIGNATURES = {
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
+    "monsoon_env_set_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule)]),
+    "monsoon_env_decks_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "monsoon_env_reseed_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "monsoon_env_afterstates_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvAfter), ctypes.c_int32]),
     "monsoon_env_entry_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "monsoon_env_save_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),

@@ -10,8 +10,8 @@
 //   sample(pop, k)  setsize = 21, + 4 ** ceil(log(3k, 4)) = 64 for k in 6..12
 //                   n <= setsize: j = randbelow(n - i); take pool[j]; pool[j] = pool[n - i - 1]    (pool path)
 //                   else:         j = randbelow(n) until j is new; take pop[j]                     (set path)
-// One text for the kernel (k_draw_schedule: lane 0 of the game's wavefront walks, the stream's first 624 outputs lie in
-// LDS) and for the host check (tests/deck_schedule_check.cpp).  Plain pointers, no device intrinsics.
+// One text for the kernels (k_draw_schedule, and k_env_reseed_schedule for the vector env's episodes: lane 0 of the game's
+// wavefront walks, the stream's first 624 outputs lie in LDS) and for the host check (tests/deck_schedule_check.cpp).  Plain pointers, no device intrinsics.
 //
 // A game may read the first 624 outputs of its stream (one twist); the draws of a deck pair took at most 90 in the host
 // check's 72 000 games.  Reading past the window sets DsStream::over and yields 0, every loop below ends on it, and the caller reports
@@ -23,7 +23,7 @@ namespace msb {
 
 constexpr uint32_t DS_INIT_SEED = 19650218u;   // init_by_array starts from init_genrand(19650218), the same for every key
 constexpr int DS_POOL_MAX = 128;
-enum : int { DS_EXPLORE = 1, DS_BALANCE = 2 };
+enum : int { DS_STATIC = 0, DS_EXPLORE = 1, DS_BALANCE = 2 };   // DS_STATIC: the exploit phase, the vector env's schedule only (k_env_reseed_schedule)
 
 // init_by_array(key[4]) over mt = init_genrand(19650218): 624 + 623 dependent steps.  The previous word stays in a
 // register, so a step waits for arithmetic only, never for the store before it.
@@ -107,10 +107,13 @@ MSB_HD inline void ds_sample(DsStream& s, uint8_t* pop, int n, int k, uint8_t* o
 //   explore: per side, P1 first: sample(archetype, n_preserve) then sample(pool, 12 - n_preserve); n_preserve = 12 is
 //            the archetype itself, no draws (generate_random_deck's preserve_ratio == 1.0)
 //   balance: random() < ratio for P1, then for P2; then sample(pool, 12) per side whose test failed, P1 first
+//   static:  both archetypes, no draw: the stream is not read, n_preserve and the pools are ignored
 MSB_HD inline void ds_walk(DsStream& s, int phase, int n_preserve, double ratio, uint8_t* arch, uint8_t* pool, const int32_t* pool_n,
                            uint8_t* out24) {
   bool keep[2] = {n_preserve >= 12, n_preserve >= 12};
-  if (phase == DS_BALANCE) {
+  if (phase == DS_STATIC) {
+    keep[0] = keep[1] = true;
+  } else if (phase == DS_BALANCE) {
     n_preserve = 0;
     for (int side = 0; side < 2; side++) keep[side] = ds_random(s) < ratio;
   }

@@ -29,6 +29,15 @@ struct EnvDev {
   int cap;                  // max_games: the stride of opp_list
 };
 
+// What a schedule-mode env (monsoon_env_reset without decks or pool after monsoon_env_set_schedule) needs on top: an
+// argument of k_env_reseed_schedule alone.  EnvDev stays as it is, so every other env kernel keeps its argument block and
+// its code (scripts/isa_diff.sh).  sched null = the loaded env is not in schedule mode.
+struct EnvSched {
+  const monsoon_deck_schedule* sched;   // the handle's schedule: read when an episode starts, rewritten between steps
+  const uint32_t* mt_init;              // [624]: init_genrand(19650218), where every key mixing starts
+  uint32_t* over;                       // episodes since monsoon_env_reset whose walk ran past the 624 outputs (monsoon_debug_counters word 17)
+};
+
 // k_env_opp<U, W> at the build's default variant (env_opp.hip): one wavefront per listed slot plays the opponent's turn.
 struct EnvOppOps {
   int lanes, wpe;   // U, W

@@ -11,6 +11,8 @@
 //   k_env_after_opp  (opponent 2) lane per listed slot: env_finish (list 0) or the state views (list 1).
 //   k_env_reseed  wavefront per slot (grid n): marked slots only -- the next episode's stream (k_seed's code) and, with a
 //                 pool, its decks (k_draw_decks' code).
+//   k_env_reseed_schedule  launched in its place by a schedule-mode env: the decks are the pair the handle's deck schedule
+//                 draws for the episode's seed (k_draw_schedule's code), then the stream as above.
 //   k_env_init    lane per slot, marked slots only: init_game, the bot's opening turn when the agent is SECOND, then the
 //                 observation, legal bytes and to_play of the new episode's first state.  With the heuristic opponent, a
 //                 new episode that opens with the opponent is put on slot list 1, and k_env_opp / k_env_after_opp follow.
@@ -213,6 +215,46 @@ __global__ void __launch_bounds__(64) k_env_reseed(DevBuffers b, EnvDev v, int n
     __syncthreads();
   }
   wave_seed_game(b, g, seed, t, lane);
+}
+
+// k_env_reseed for a schedule-mode env: the next episode's decks are the pair that the schedule the handle holds NOW
+// (monsoon_env_set_schedule) draws from random.Random(seed32 | generation << 32 | episode seed << 64 | tag << 96), as
+// k_draw_schedule draws a game's.  The static LDS is k_draw_schedule's (2 808 bytes, less than k_env_reseed's 7 616): mt
+// serves the schedule's stream before wave_seed_game reuses it.  A walk that runs past the 624 outputs cannot fail
+// the call (as the pool's cannot): it is counted, and its pair holds card indices of the schedule (the loops of
+// deck_schedule.h end on a zero output) but is not the specification's draw.
+__global__ void __launch_bounds__(64) k_env_reseed_schedule(DevBuffers b, EnvDev v, int n, EnvSched es) {
+  __shared__ uint32_t mt[MT_N];
+  __shared__ uint8_t cards[DS_CARD_BYTES];   // archetype[2][12] | pool[2][128]
+  __shared__ uint32_t pair[6];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  if (g >= n || !v.mark[g]) return;
+  const uint32_t seed = env_seed(v, g);
+  const monsoon_deck_schedule* sc = es.sched;
+  const int phase = sc->phase;
+  const uint8_t* src = &sc->archetype[0][0];
+  for (int k = lane; k < DS_CARD_BYTES; k += 64) cards[k] = src[k];
+  if (phase != DS_STATIC) {   // (uniform) the static phase reads no stream
+    for (int k = lane; k < MT_N; k += 64) mt[k] = es.mt_init[k];
+    __syncthreads();
+    if (lane == 0) {
+      const uint32_t key[4] = {sc->seed, sc->generation, seed, sc->tag};
+      ds_key_mix(mt, key);
+    }
+    __syncthreads();
+    wave_twist_lds((MSB_AS_LDS uint32_t*)mt, lane);
+    for (int k = lane; k < MT_N; k += 64) mt[k] = mt_temper(mt[k]);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    DsStream s{mt, 0, 0};
+    ds_walk(s, phase, sc->n_preserve, sc->balance_archetype_ratio, cards, cards + 24, sc->pool_n, (uint8_t*)pair);
+    uint32_t* out = (uint32_t*)(v.decks + (size_t)g * 24);   // 4-byte aligned: d_env's decks start at 16 * cap
+    for (int k = 0; k < 6; k++) out[k] = pair[k];
+    if (s.over) atomicAdd(es.over, 1u);
+  }
+  __syncthreads();
+  wave_seed_game(b, g, seed, (MSB_AS_LDS uint32_t*)mt, lane);
 }
 
 // The first state of the next episode of every marked slot (k_init's code), the bot's opening turn, the slot's views.

@@ -719,6 +719,7 @@ struct monsoon {
   EnvDev env;
   int env_n = 0;
   bool env_on = false;
+  EnvSched env_sched = {};   // sched non-null: the loaded env is in schedule mode (k_env_reseed_schedule)
   // the env's heuristic opponent (monsoon_env_set_opponents): d_opp is sized by max_games and allocated once; the weight
   // table is never moved while an opponent-2 env is loaded (a captured step points to it)
   uint8_t* d_opp = nullptr;   // rows i32 [cap] | slot lists i32 [2][cap] | look-ahead transitions u32 [cap] | list counts i32 [2 * ENV_COUNT_STRIDE] | pop counters i32 [2][POP_PARTS * POP_STRIDE]
@@ -731,8 +732,17 @@ struct monsoon {
   int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
   uint8_t* d_snap_flag = nullptr;   // [cap], inside d_env: the loaded flags of monsoon_env_load_dev when the caller keeps none
   int cu_count = 0;           // compute units of the device (queried once per handle)
-  // monsoon_draw_schedule: init_genrand(19650218), uploaded by the first call; the kernel's time in the last call
+  // monsoon_draw_schedule and the env's schedule mode: init_genrand(19650218), uploaded by the first call that needs it
+  // (ensure_mt_init); the draw kernel's time in the last monsoon_draw_schedule call
   uint32_t* d_mt_init = nullptr;
+  // monsoon_env_set_schedule: the handle's schedule, allocated by the first call and never moved (a captured step of a
+  // schedule-mode env points to it): monsoon_deck_schedule | u32 overrun counter of the loaded env
+  uint8_t* d_sched = nullptr;
+  bool sched_set = false;     // d_sched holds a schedule
+  // monsoon_env_reseed_time: when on, every eager step records an event pair round the reseed kernel
+  bool reseed_timed = false;
+  bool reseed_have = false;   // the pair was recorded by a step
+  hipEvent_t reseed_ev[2] = {};
   hipEvent_t draw_ev[2] = {};
   double draw_ms = 0;
 };
@@ -821,10 +831,12 @@ void monsoon_destroy(monsoon_t* h) {
   if (h->split_fork) hipEventDestroy(h->split_fork);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init};
+                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init, h->d_sched};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (hipEvent_t e : h->draw_ev)
+    if (e) hipEventDestroy(e);
+  for (hipEvent_t e : h->reseed_ev)
     if (e) hipEventDestroy(e);
   for (uint32_t* p : h->ovf_retired) hipFree(p);
   for (auto& pr : h->ev_pool) {
@@ -1066,6 +1078,25 @@ int monsoon_draw_decks(monsoon_t* h, const uint32_t* seeds, int32_t n, const uin
   return done(MONSOON_OK);
 }
 
+// init_genrand(19650218) on the device, once per handle: where the key mixing of every schedule stream starts
+// (k_draw_schedule, k_env_reseed_schedule).  The device is bound.
+static int ensure_mt_init(monsoon_t* h) {
+  if (h->d_mt_init) return MONSOON_OK;
+  std::vector<uint32_t> mt(MT_N);   // (mt19937.h: mt_seed)
+  mt[0] = DS_INIT_SEED;
+  for (int i = 1; i < MT_N; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+  uint32_t* d = nullptr;
+  HIP_TRY(h, hipMalloc(&d, MT_N * 4));
+  hipError_t e = hipMemcpy(d, mt.data(), MT_N * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    hipFree(d);
+    h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
+    return MONSOON_ERR_DEVICE;
+  }
+  h->d_mt_init = d;
+  return MONSOON_OK;
+}
+
 int monsoon_draw_schedule(monsoon_t* h, const monsoon_deck_schedule* sc, const uint32_t* game_seeds, int32_t n, uint8_t* out_pairs) {
   if (!h || !sc || !game_seeds || !out_pairs || n <= 0 || sc->tag == 0 || (sc->phase != DS_EXPLORE && sc->phase != DS_BALANCE) ||
       sc->n_preserve < 0 || sc->n_preserve > 12) {
@@ -1085,20 +1116,8 @@ int monsoon_draw_schedule(monsoon_t* h, const monsoon_deck_schedule* sc, const u
       }
   }
   HIP_TRY(h, bind_device(h));
-  if (!h->d_mt_init) {
-    std::vector<uint32_t> mt(MT_N);   // init_genrand(19650218) (mt19937.h: mt_seed)
-    mt[0] = DS_INIT_SEED;
-    for (int i = 1; i < MT_N; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-    uint32_t* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, MT_N * 4));
-    hipError_t e = hipMemcpy(d, mt.data(), MT_N * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      hipFree(d);
-      h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
-      return MONSOON_ERR_DEVICE;
-    }
-    h->d_mt_init = d;
-  }
+  int rc_mt = ensure_mt_init(h);
+  if (rc_mt) return rc_mt;
   for (hipEvent_t& e : h->draw_ev)
     if (!e) HIP_TRY(h, hipEventCreate(&e));
   uint32_t *d_seeds = nullptr, *d_out = nullptr;
@@ -1974,6 +1993,11 @@ int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
       HIP_TRY(h, hipMemcpy(st.data(), h->env.opp_lookahead, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
       for (int i = 0; i < h->env_n; i++) out[16] += st[i];
     }
+    if (h->env_sched.sched) {   // a schedule-mode env: episodes whose deck walk ran past its stream's 624 outputs
+      uint32_t over = 0;
+      HIP_TRY(h, hipMemcpy(&over, h->env_sched.over, 4, hipMemcpyDeviceToHost));
+      out[17] = over;
+    }
   }
 #if defined(MSB_PROF) && MSB_PROF
   {
@@ -2122,6 +2146,85 @@ int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_ind
   return MONSOON_OK;
 }
 
+// The stream and the decks of the next episode of every marked slot: k_env_reseed, or its sibling in schedule mode.
+static void launch_env_reseed(monsoon_t* h, int n) {
+  if (h->env_sched.sched) hipLaunchKernelGGL(k_env_reseed_schedule, dim3(n), dim3(64), 0, h->stream, h->b, h->env, n, h->env_sched);
+  else hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, h->env, n);
+}
+
+int monsoon_env_set_schedule(monsoon_t* h, const monsoon_deck_schedule* sc) {
+  if (!h) return MONSOON_ERR_ARG;
+  const bool in_use = h->env_on && h->env_sched.sched;
+  if (!sc) {
+    if (in_use) {
+      h->err = "monsoon_env_set_schedule: a schedule-mode env is loaded: its schedule can be replaced, not cleared";
+      return MONSOON_ERR_STATE;
+    }
+    h->sched_set = false;
+    return MONSOON_OK;
+  }
+  const bool draws = sc->phase != DS_STATIC;
+  const char* bad = nullptr;
+  if (sc->tag == 0) bad = "tag must not be 0";
+  else if (sc->phase != DS_STATIC && sc->phase != DS_EXPLORE && sc->phase != DS_BALANCE) bad = "phase must be 0 (static), 1 (explore) or 2 (balance)";
+  else if (sc->n_preserve < 0 || sc->n_preserve > 12) bad = "0 <= n_preserve <= 12";
+  else if (draws && (sc->pool_n[0] < 12 || sc->pool_n[0] > DS_POOL_MAX || sc->pool_n[1] < 12 || sc->pool_n[1] > DS_POOL_MAX)) bad = "12 <= pool_n <= 128";
+  if (bad) {
+    h->err = std::string("monsoon_env_set_schedule: ") + bad;
+    return MONSOON_ERR_ARG;
+  }
+  for (int side = 0; side < 2; side++) {
+    int rc = check_decks(h, sc->archetype[side], 12, "monsoon_env_set_schedule (archetype)");
+    if (!rc && draws) rc = check_decks(h, sc->pool[side], (size_t)sc->pool_n[side], "monsoon_env_set_schedule (pool)");
+    if (rc) return rc;
+  }
+  HIP_TRY(h, bind_device(h));
+  if (!h->d_sched) {
+    HIP_TRY(h, hipMalloc(&h->d_sched, sizeof(monsoon_deck_schedule) + 64));
+    HIP_TRY(h, hipMemsetAsync(h->d_sched, 0, sizeof(monsoon_deck_schedule) + 64, h->stream));
+  }
+  // behind every step already enqueued: the episodes they start draw from the schedule of their time
+  HIP_TRY(h, hipMemcpyAsync(h->d_sched, sc, sizeof(monsoon_deck_schedule), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->sched_set = true;
+  return MONSOON_OK;
+}
+
+// Measurement (scripts/env_schedule_bench.py): the reseed kernel of the last eager step, by an event pair of the handle.
+int monsoon_env_reseed_time(monsoon_t* h, int32_t enable, double* kernel_ms) {
+  if (!h || !kernel_ms) return MONSOON_ERR_ARG;
+  *kernel_ms = 0;
+  HIP_TRY(h, bind_device(h));
+  if (h->reseed_have) {
+    float ms = 0;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipEventElapsedTime(&ms, h->reseed_ev[0], h->reseed_ev[1]));
+    *kernel_ms = ms;
+  }
+  if (enable)
+    for (hipEvent_t& e : h->reseed_ev)
+      if (!e) HIP_TRY(h, hipEventCreate(&e));
+  h->reseed_timed = enable != 0;
+  if (!enable) h->reseed_have = false;
+  return MONSOON_OK;
+}
+
+// One device-to-device copy on the handle's stream: no allocation or synchronisation (graph-capturable).
+int monsoon_env_decks_dev(monsoon_t* h, void* out_dev) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!h->env_on) {
+    h->err = "monsoon_env_decks_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+    return MONSOON_ERR_STATE;
+  }
+  if (!out_dev) {
+    h->err = "monsoon_env_decks_dev: out_dev is NULL";
+    return MONSOON_ERR_ARG;
+  }
+  HIP_TRY(h, bind_device(h));
+  HIP_TRY(h, hipMemcpyAsync(out_dev, h->env.decks, (size_t)h->env_n * 24, hipMemcpyDeviceToDevice, h->stream));
+  return MONSOON_OK;
+}
+
 int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon_env_views* views, int32_t n, const uint32_t* seed0,
                       const uint8_t* decks, const uint8_t* factions) {
   if (!h) return MONSOON_ERR_ARG;
@@ -2132,7 +2235,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   else if (cfg->agent_side != 0 && cfg->agent_side != 1) bad = "agent_side must be 0 or 1";
   else if (cfg->max_steps < 0 || cfg->max_steps > 65535) bad = "0 <= max_steps <= 65535";
   else if (cfg->pool_n != 0 && (cfg->pool_n < 12 || cfg->pool_n > 128)) bad = "pool_n must be 0 or 12..128";
-  else if (!cfg->pool_n && !decks) bad = "decks are required without a pool";
+  else if (!cfg->pool_n && !decks && !h->sched_set) bad = "decks are required without a pool or a schedule (monsoon_env_set_schedule)";
   else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
   else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
   else if (cfg->opponent == 2 && h->opp_n && h->opp_n != n) bad = "n differs from the n of monsoon_env_set_opponents";
@@ -2144,9 +2247,16 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     h->err = "monsoon_env_reset: opponent 2 needs monsoon_env_set_opponents first";
     return MONSOON_ERR_STATE;
   }
-  int rc = cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)") : check_decks(h, decks, (size_t)n * 24, "monsoon_env_reset");
+  const bool by_schedule = !cfg->pool_n && !decks;   // the stored schedule's cards were checked by monsoon_env_set_schedule
+  int rc = by_schedule ? MONSOON_OK
+           : cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)")
+                         : check_decks(h, decks, (size_t)n * 24, "monsoon_env_reset");
   if (rc) return rc;
   HIP_TRY(h, bind_device(h));
+  if (by_schedule) {
+    rc = ensure_mt_init(h);
+    if (rc) return rc;
+  }
   rc = fold_stats(h);   // statistics live in the per-game rows that are about to be cleared
   if (rc) return rc;
   h->env_on = false;
@@ -2175,6 +2285,11 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   v.opp_count = nullptr;
   v.opp_pop = nullptr;
   v.opp_lookahead = nullptr;
+  h->env_sched = EnvSched{};
+  if (by_schedule) {
+    h->env_sched = EnvSched{(const monsoon_deck_schedule*)h->d_sched, h->d_mt_init, (uint32_t*)(h->d_sched + sizeof(monsoon_deck_schedule))};
+    HIP_TRY(h, hipMemsetAsync(h->env_sched.over, 0, 4, h->stream));
+  }
   if (cfg->opponent == 2) {
     v.opp_rows = (const int32_t*)h->d_opp;
     v.opp_list = (int32_t*)(h->d_opp + 4 * cap);
@@ -2225,7 +2340,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   HIP_TRY(h, hipMemsetAsync(v.bot_steps, 0, (size_t)n * 4, h->stream));
   HIP_TRY(h, hipMemsetAsync(v.mark, 1, (size_t)n, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->b.meta, 0, (size_t)n * sizeof(GameMeta), h->stream));
-  hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, v, n);
+  launch_env_reseed(h, n);
   hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, v, n, 1);
   HIP_TRY(h, hipGetLastError());
   if (cfg->opponent == 2) {   // the opening turns of the episodes the opponent starts (list 1)
@@ -2259,7 +2374,14 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
     int rc = launch_env_opp(h, n, 0);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_env_reseed, dim3(n), dim3(64), 0, h->stream, h->b, h->env, n);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  const bool timed = h->reseed_timed && hipStreamIsCapturing(h->stream, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusNone;
+  if (timed) HIP_TRY(h, hipEventRecord(h->reseed_ev[0], h->stream));
+  launch_env_reseed(h, n);
+  if (timed) {
+    HIP_TRY(h, hipEventRecord(h->reseed_ev[1], h->stream));
+    h->reseed_have = true;
+  }
   hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, 0);
   HIP_TRY(h, hipGetLastError());
   if (h->env.opponent == 2) return launch_env_opp(h, n, 1);

@@ -18,6 +18,7 @@ FACTION_OF = {c["id"]: c["faction"] for c in CARD_META}
 
 # stream tags of the per-game mode: which caller a game's decks are drawn for (never 0: the key keeps four words)
 TAG_POPULATION, TAG_EXPERT = 1, 2
+TAG_ENV = 3   # the vector env's episodes and EvolutionaryGame (VecEnv.reset(deck_schedule=...))
 
 
 def available_cards(faction):
@@ -134,6 +135,28 @@ class DeckEvolutionConfig:
         return {"seed": self.seed32, "generation": int(generation), "tag": int(tag), "phase": phase, "n_preserve": n_preserve,
                 "balance_archetype_ratio": float(self.balance_archetype_ratio), "archetype": arch,
                 "pool_n": np.array([len(p) for p in pools], dtype=np.int32), "pool": pool}
+
+    def env_schedule(self, generation):
+        """The fields of monsoon_deck_schedule for the vector env (VecEnv.reset(deck_schedule=...), monsoon_env_set_schedule):
+        schedule_params(generation, TAG_ENV), and in the exploit phase -- which the env needs for a curriculum that
+        crosses phases -- phase 0 with the archetypes instead of None (the device reads no stream; n_preserve, pool_n and
+        pool are ignored there and left zero).  ValueError where schedule_params returns None for another reason: an
+        archetype that is not 12 cards, a pool outside 12..128."""
+        import numpy as np
+        from .cards import CARD_INDEX
+        if not self.per_game:
+            raise ValueError("env_schedule needs DeckEvolutionConfig(per_game=True)")
+        if len(self.player1_archetype) != 12 or len(self.player2_archetype) != 12:
+            raise ValueError("the device draws for archetypes of exactly 12 cards")
+        if not self.is_static(generation):
+            params = self.schedule_params(generation, TAG_ENV)
+            if params is None:
+                raise ValueError("the device draws from faction pools of 12..128 cards")
+            return params
+        arch = np.array([[CARD_INDEX[c] for c in a] for a in (self.player1_archetype, self.player2_archetype)], dtype=np.uint8)
+        return {"seed": self.seed32, "generation": int(generation), "tag": TAG_ENV, "phase": 0, "n_preserve": 0,
+                "balance_archetype_ratio": float(self.balance_archetype_ratio), "archetype": arch,
+                "pool_n": np.zeros(2, dtype=np.int32), "pool": np.zeros((2, 128), dtype=np.uint8)}
 
     def is_static(self, generation):
         """True while every game of the generation gets the same pair (exploit phase)."""

@@ -208,6 +208,31 @@ class BatchEngine:
             rows = np.ascontiguousarray(rows, dtype=np.int32)
         self._ck(self.lib.monsoon_env_set_opponents(self.h, _ptr(weights), len(weights), _ptr(rows), int(n)), "monsoon_env_set_opponents")
 
+    def debug_counters(self):
+        """monsoon_debug_counters: the 192 raw counter words as uint64 (include/monsoon.h; synchronises)."""
+        out = np.zeros(192, dtype=np.uint64)
+        self._ck(self.lib.monsoon_debug_counters(self.h, _ptr(out)), "monsoon_debug_counters")
+        return out
+
+    def env_set_schedule(self, params):
+        """monsoon_env_set_schedule: params = the fields of monsoon_deck_schedule (DeckEvolutionConfig.env_schedule, or a
+        dict of the same fields; phase 0 = both archetypes, no draw), None clears the handle's schedule.  The schedule
+        applies to every episode of a schedule-mode env that starts from the next step on.  Synchronises."""
+        sc = None if params is None else self._deck_schedule(params)
+        self._ck(self.lib.monsoon_env_set_schedule(self.h, None if sc is None else ctypes.byref(sc)), "monsoon_env_set_schedule")
+
+    def env_decks_dev(self, out_ptr):
+        """monsoon_env_decks_dev: the decks of every slot's current episode, uint8[n][2][12], into device memory at out_ptr
+        (asynchronous on the handle's stream)."""
+        self._ck(self.lib.monsoon_env_decks_dev(self.h, ctypes.c_void_p(out_ptr)), "monsoon_env_decks_dev")
+
+    def env_reseed_time(self, enable=True):
+        """monsoon_env_reseed_time: ms of the reseed kernel inside the last env step (0.0 if it was not timed); enable:
+        whether later steps are timed (HIP events round that launch).  Synchronises."""
+        ms = ctypes.c_double()
+        self._ck(self.lib.monsoon_env_reseed_time(self.h, int(bool(enable)), ctypes.byref(ms)), "monsoon_env_reseed_time")
+        return ms.value
+
     def env_step_dev(self, actions_ptr):
         """monsoon_env_step_dev on n bytes of device memory at actions_ptr (asynchronous on the handle's stream)."""
         self._ck(self.lib.monsoon_env_step_dev(self.h, ctypes.c_void_p(actions_ptr)), "monsoon_env_step_dev")
@@ -297,12 +322,10 @@ class BatchEngine:
             self._ck(self.lib.monsoon_draw_decks(self.h, _ptr(seeds), len(seeds), _ptr(pool), len(pool), _ptr(out)), "monsoon_draw_decks")
         return out
 
-    def draw_schedule(self, params, game_seeds):
-        """uint8[n][2][12]: the per-game decks of a deck schedule, drawn on the device (monsoon_draw_schedule).  params:
-        DeckEvolutionConfig.schedule_params(generation, tag), or a dict of the same fields; game_seeds: uint32[n].  Every
-        pair equals DeckEvolutionConfig.game_decks(generation, game_seed, tag)."""
+    @staticmethod
+    def _deck_schedule(params):
+        """_lib.DeckSchedule (monsoon_deck_schedule) from a dict of its fields."""
         from ._lib import DeckSchedule
-        game_seeds = np.ascontiguousarray(game_seeds, dtype=np.uint32)
         arch = np.ascontiguousarray(params["archetype"], dtype=np.uint8)
         pool = np.ascontiguousarray(params["pool"], dtype=np.uint8)
         if arch.shape != (2, 12) or pool.shape != (2, 128):
@@ -311,6 +334,14 @@ class BatchEngine:
                           (ctypes.c_int32 * 2)(*[int(v) for v in params["pool_n"]]), float(params["balance_archetype_ratio"]))
         ctypes.memmove(sc.archetype, arch.ctypes.data, 24)
         ctypes.memmove(sc.pool, pool.ctypes.data, 256)
+        return sc
+
+    def draw_schedule(self, params, game_seeds):
+        """uint8[n][2][12]: the per-game decks of a deck schedule, drawn on the device (monsoon_draw_schedule).  params:
+        DeckEvolutionConfig.schedule_params(generation, tag), or a dict of the same fields; game_seeds: uint32[n].  Every
+        pair equals DeckEvolutionConfig.game_decks(generation, game_seed, tag)."""
+        game_seeds = np.ascontiguousarray(game_seeds, dtype=np.uint32)
+        sc = self._deck_schedule(params)
         out = np.zeros((len(game_seeds), 2, 12), dtype=np.uint8)
         self._ck(self.lib.monsoon_draw_schedule(self.h, ctypes.byref(sc), _ptr(game_seeds), len(game_seeds), _ptr(out)), "monsoon_draw_schedule")
         return out

@@ -10,7 +10,7 @@ player, to_play(), legal_actions().  A step the reference would raise on raises 
 """
 import numpy as np
 
-from .cards import CARD_IDS, deck_indices
+from .cards import CARD_IDS, deck_indices, needs_extended
 from .engine import BatchEngine
 
 FACTION = {"NEUTRAL": 0, "WINTER": 1, "SWARM": 2, "IRONCLAD": 3, "SHADOWFEN": 4}   # enums.py:44-49
@@ -160,6 +160,41 @@ class Game:
 
     def action_to_string(self, action_number):
         return action_to_string(action_number)
+
+
+class EvolutionaryGame(Game):
+    """games/evolutionary_stormbound.py:31-68 over Game: a game whose decks come from a deck schedule
+    (monsoon_amd.decks.DeckEvolutionConfig) at `generation`, and whose factions are the config's.  With a per-game config
+    the pair is deck_config.game_decks(generation, seed, TAG_ENV) -- the decks of the VecEnv episode that starts from the
+    same seed (VecEnv.reset(deck_schedule=deck_config, generation=generation)) -- else get_deck_configuration(generation)
+    from the config's sequential stream, as in the reference.  deck_config None is the default pair Stormbound plays.  A
+    pair that holds ua20 or b005 is played on the extended record build (extended=None; 0 / 1 / 2 names the build, e.g. the
+    one a VecEnv runs on: the standard and the extended records keep hand and deck differently -- value entries and object
+    ids, DESIGN.md §2a -- and play a deck that holds a card twice, as explore decks often do, differently)."""
+
+    def __init__(self, seed=None, generation=0, deck_config=None, device=0, extended=None):
+        from .decks import TAG_ENV
+        if seed is None:
+            seed = int(np.random.randint(0, 2**32, dtype=np.uint64))
+        seed = int(seed) & 0xFFFFFFFF
+        self.generation = int(generation)
+        self.deck_config = deck_config
+        if deck_config is None:
+            self.player1_deck, self.player2_deck = "IRONCLAD", "SWARM"
+            factions = (FACTION["IRONCLAD"], FACTION["SWARM"])
+        else:
+            if getattr(deck_config, "per_game", False):
+                self.player1_deck, self.player2_deck = deck_config.game_decks(self.generation, seed, TAG_ENV)
+            else:
+                self.player1_deck, self.player2_deck = deck_config.get_deck_configuration(self.generation)
+            factions = (int(deck_config.player1_faction), int(deck_config.player2_faction))
+        pair = np.stack([deck_indices(self.player1_deck), deck_indices(self.player2_deck)])
+        engine = BatchEngine(1, device=device, extended=int(needs_extended(pair) if extended is None else extended))
+        self.env = Stormbound(seed, self.player1_deck, self.player2_deck, factions[0], factions[1], device=device, engine=engine)
+
+    def get_phase_info(self):
+        """DeckEvolutionConfig.get_phase_info of this game's generation (None without a config)."""
+        return None if self.deck_config is None else self.deck_config.get_phase_info(self.generation)
 
 
 def card_name(index):

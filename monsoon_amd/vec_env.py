@@ -6,6 +6,8 @@ legal_actions, reset, expert_agent as the opponent), each an endless sequence of
 re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.  The
 opponent can also be the reference's HeuristicAgent with GA weights ("heuristic": seven launches per step).
 `snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device.
+Episode decks come from the reset decks, from a pool, or from a deck schedule (`reset(deck_schedule=...)`: the GA's
+exploit / explore / balance curriculum, drawn on the device per episode; `set_deck_schedule` moves its generation).
 torch is used for device memory and stream ordering only; there is no CPU fallback.
 """
 import ctypes
@@ -91,6 +93,8 @@ class VecEnv:
         self.views = None
         self._heuristic = False   # an opponent-2 env is loaded
         self._after = {}          # obs -> ((n, K), tensors, _lib.EnvAfter): the latest shape per obs flag, reused until it changes
+        self._schedule = None     # the deck_schedule given to reset (a DeckEvolutionConfig or a dict) while a schedule-mode env is loaded
+        self._decks = None        # decks()' tensor
 
     def close(self):
         if self.engine is not None:
@@ -118,20 +122,35 @@ class VecEnv:
         return views
 
     def reset(self, seed0, decks=None, factions=None, opponent="none", agent_side=0, max_steps=0, pool=None, seed_stride=0,
-              opponent_weights=None, opponent_rows=None):
+              opponent_weights=None, opponent_rows=None, deck_schedule=None, generation=None):
         """Episode 0 of every slot: slot i plays seed0[i] with decks[i] ([n][2][12] or one [2][12] pair for all) and
         factions[i]; episode k then starts from seed0[i] + k * seed_stride (0 = n).  pool (12..128 card indices) draws
         fresh decks for every episode instead (decks must be None).  opponent "expert" puts the reference's scripted bot on
         the side that agent_side does not play; "heuristic" puts the reference's HeuristicAgent there, slot i playing row
         opponent_rows[i] (None = row 0) of opponent_weights ([10] or [k][10] float64, e.g. WeightVector.weights or a
-        Population's individuals).  max_steps > 0 truncates episodes.  Returns the view tensors (a dict)."""
+        Population's individuals).  max_steps > 0 truncates episodes.  Returns the view tensors (a dict).
+
+        deck_schedule (decks and pool must be None) draws the decks of every episode, episode 0 included, from a deck
+        schedule on the device: a DeckEvolutionConfig(per_game=True) at `generation`, or a dict of the fields of
+        monsoon_deck_schedule (DeckEvolutionConfig.env_schedule; a `generation` given here replaces the dict's; None = 0 for a
+        config).  The episode that
+        starts from seed s plays deck_schedule.game_decks(generation, s, decks.TAG_ENV) of the schedule in force when it
+        starts; set_deck_schedule moves the generation between steps; decks() tells what every slot is playing.  Factions
+        stay those of `factions` (episode 0 only, as ever).  Every faction's pool holds ua20 and Shadowfen's b005, so a
+        schedule made from a config needs VecEnv(extended=1) once it draws (explore and balance phases): on the standard
+        build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised."""
         import torch
         if opponent not in OPPONENTS:
             raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
         seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
         n = len(seed0)
-        if pool is None and decks is None:
-            raise ValueError("decks are required without a pool")
+        sched = None
+        if deck_schedule is not None:
+            if decks is not None or pool is not None:
+                raise ValueError("deck_schedule draws every episode's decks: decks and pool must be None")
+            sched = self._schedule_params(deck_schedule, generation)
+        elif pool is None and decks is None:
+            raise ValueError("decks are required without a pool or a deck_schedule")
         opp = None
         if opponent == "heuristic":
             if opponent_weights is None:
@@ -163,8 +182,12 @@ class VecEnv:
             if opp is not None:
                 self.engine.env_set_opponents(opp[0], opp[1], n)
             self._heuristic = False
+            self._schedule = None
+            if sched is not None:
+                self.engine.env_set_schedule(sched)
             self.engine.env_reset(cfg, views, seed0, decks, factions)
             self._heuristic = opp is not None
+            self._schedule = deck_schedule
         finally:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return self.views
@@ -197,6 +220,44 @@ class VecEnv:
             self.engine.env_set_opponents(w, r, self.n)
         finally:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
+
+    @staticmethod
+    def _schedule_params(deck_schedule, generation):
+        """The fields of monsoon_deck_schedule at `generation` from a DeckEvolutionConfig(per_game=True) or a dict of them."""
+        if isinstance(deck_schedule, dict):
+            return deck_schedule if generation is None else dict(deck_schedule, generation=int(generation))
+        if not getattr(deck_schedule, "per_game", False):
+            raise ValueError("deck_schedule must be a DeckEvolutionConfig(per_game=True) or a dict of monsoon_deck_schedule's fields")
+        return deck_schedule.env_schedule(int(generation or 0))
+
+    def set_deck_schedule(self, generation, deck_schedule=None):
+        """Move a schedule-mode env to another generation (and, with deck_schedule, to another config or dict; None keeps
+        the one given to reset) between steps: every episode that starts from the next step on draws from it, running
+        episodes keep their decks, a captured step graph stays valid.  MonsoonError if the env was not reset with a
+        deck_schedule.  Synchronises the env's stream."""
+        import torch
+        if self._schedule is None:
+            raise MonsoonError("VecEnv.set_deck_schedule needs reset(deck_schedule=...) first")
+        new = self._schedule if deck_schedule is None else deck_schedule
+        params = self._schedule_params(new, generation)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        try:
+            self.engine.env_set_schedule(params)
+        finally:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        self._schedule = new
+
+    def decks(self):
+        """The decks of every slot's current episode (monsoon_env_decks_dev): a uint8 CUDA tensor [n][2][12] of card
+        indices, P1's deck first, in every deck mode.  Allocated on the first call per n and overwritten in place by every
+        later one (a later call allocates nothing and can be captured).  Stream ordering as in step."""
+        import torch
+        if self.views is None:
+            raise MonsoonError("VecEnv.decks before reset")
+        if self._decks is None or self._decks.shape[0] != self.n:
+            self._decks = torch.zeros((self.n, 2, 12), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        self._on_env_stream(lambda: self.engine.env_decks_dev(self._decks.data_ptr()))
+        return self._decks
 
     def step(self, actions):
         """Advance every slot: actions is a uint8 CUDA tensor [n] (255 = leave the slot alone, 155 = PASS, any other
