@@ -39,10 +39,7 @@ struct EnvSched {
 };
 
 // k_env_opp<U, W> at the build's default variant (env_opp.hip): one wavefront per listed slot plays the opponent's turn.
-struct EnvOppOps {
-  int lanes, wpe;   // U, W
-  int lds_bytes;    // dynamic LDS of one workgroup
-  hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
+struct EnvOppOps : KernelOps {
   void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list);
 };
 const EnvOppOps* monsoon_env_opp_ops();

@@ -54,8 +54,7 @@ __device__ MSB_INL bool env_after_step(ApiEngine& e, const DevBuffers& b, int g,
   if (f) {
     env_end(m, -1, f, false);
   } else if (e.have_winner()) {
-    const int b0 = e.pl_base(0), b1 = e.pl_base(1);
-    env_end(m, (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1, 0, false);
+    env_end(m, e.winner_of(e.pl_base(0), e.pl_base(1)), 0, false);
     m.flags |= 1;
   } else if (max_steps && m.steps >= max_steps) {
     env_end(m, -1, 0, true);

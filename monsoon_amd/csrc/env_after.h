@@ -1,10 +1,11 @@
 // env_after.h -- the afterstates of a vector-env slot (monsoon_env_afterstates_dev, include/monsoon.h): the hot kernel's
-// look-ahead without its decision.  after_slot<U> is play_game's pass loop (kernels.h) cut down to what a learner needs
-// from it: the slot's record goes from HBM into registers and its image into candidate column 0, the legal set comes from
-// legal_mask_v, and passes of U candidate lanes clone the record, step their action and hand the successor out -- status,
-// reward, winner, the ten features, the observation -- instead of scoring it.  There is no arg-max, no v_best, no commit
-// and no refill, and nothing of the handle is written: the record and its meta row are only read, the stream is read
-// through the two resident blocks.  k_env_after (env_after.hip) gives every slot to one wavefront.
+// look-ahead without its decision.  after_slot<U> composes the pieces play_game is made of (kernels.h PlayLds<U>,
+// legal_set, pass_actions, MSB_EACH_GRANULE): load and stage the slot's record, legal set, draw hint, "before" features,
+// then passes that clone the record, take their actions, step them and hand each successor out -- status, reward, winner,
+// the ten features, the observation -- instead of scoring it.  There is no arg-max, no v_best, no commit and no refill,
+// and nothing of the handle is written: the record and its meta row are only read, the stream is read through the two
+// resident blocks.
+// k_env_after (env_after.hip) gives every slot to one wavefront.
 #pragma once
 #include "env.h"
 
@@ -83,16 +84,6 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
 template <int U>
 __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after& o, const int K, const int g, const int lane) {
   typedef PlayLds<U> L;
-  typedef Engine<Col0Mem<U, L::PRIV>> ParEngine;
-  typedef Engine<LaneMem<U, L::PRIV, L::SKB, SKW>> CandEngine;
-  typedef Engine<SubColMem<U, L::PRIV>> SubEngine;
-  constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
-  constexpr bool COOP = U < 64 && GPL == 1;   // the features by the whole wave: as play_game chooses
-#if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
-  constexpr bool COOP_DRAW = GPL == 1;
-#else
-  constexpr bool COOP_DRAW = false;
-#endif
   const GameMeta meta = b.meta[g];
   uint8_t* const act_row = o.action + (size_t)g * K;
   if (meta.result != -2) {   // the episode ended before the agent could act: the next step reports it
@@ -100,75 +91,50 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
     for (int k = lane; k < K; k += 64) act_row[k] = 255;
     return;
   }
-  MSB_AS_LDS u32x4* priv = (MSB_AS_LDS u32x4*)(uintptr_t)L::PRIV;
-  MSB_AS_LDS double* wf = (MSB_AS_LDS double*)(uintptr_t)L::WF;
+  MSB_AS_LDS u32x4* priv = L::priv();
   const u32x4* grec = (const u32x4*)(b.state + (size_t)g * SW);
-  u32x4 v_par[GPL];   // granules lane, lane + 64, ... of the slot's record
-#define MSB_EACH_GRANULE(body_)                   \
-  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) { \
-    const int gr_ = lane + 64 * j_;               \
-    if (gr_ < SG) { body_; }                      \
-  }
-  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
-  MSB_EACH_GRANULE(v_par[j_] = grec[gr_])
-  ParEngine pe;
-  CandEngine ce;
-  // the image of the record in column 0; with the stream window attached it is what the clones start from
-  MSB_EACH_GRANULE(priv[gr_ * U] = v_par[j_])
+  u32x4 v_par[L::GPL];   // granules lane, lane + 64, ... of the slot's record
+  _Pragma("unroll") for (int j_ = 0; j_ < L::GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = grec[gr_])
+  typename L::ParEngine pe;
+  typename L::CandEngine ce;
+  // stage: the image of the record in column 0; with the stream window attached it is what the clones start from
+  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
   __syncthreads();
   if (lane == 0) attach_rng(pe, b, g, meta.rng);
   __syncthreads();
-  MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])
 
-  const msb_u64x4 lm = pe.legal_mask_v();
-  const uint64_t mask[3] = {uni64(lm[0]), uni64(lm[1]), uni64(lm[2])};
-  uint64_t rem[3] = {mask[0], mask[1], mask[2]};
-  const int n_legal = __popcll(mask[0]) + __popcll(mask[1]) + __popcll(mask[2]);
+  LegalSet ls = legal_set(pe);
+  const int n_legal = ls.n;
   const int n_do = n_legal < K ? n_legal : K;   // the afterstates this call hands out
   if (lane == 0) o.n_legal[g] = n_legal;
   for (int k = n_do + lane; k < K; k += 64) act_row[k] = 255;
-  if constexpr (COOP_DRAW) {
-    // what the first draw of the REPLACE candidates (actions 148..151) will find, resolved as play_game resolves it; a
-    // slot without such a candidate clears the word the slot before it left
-    uint32_t hint = 0u;
-    if ((mask[2] >> (148 - 128)) & 0xfull) {   // (uniform)
-      const bool u_ok = (meta.rng & 0xffffu) + 1u < (uint32_t)(2 * MT_N);
-      const uint32_t ra = u_ok ? peek_u32(b, g, meta.rng) : 0u, rb = u_ok ? peek_u32(b, g, meta.rng + 1u) : 0u;
-      int sl = lane;
-      asm volatile("" : "+v"(sl));
-      hint = coop_draw(pe, sl, ra, rb, u_ok);
-    }
-    if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = hint;
-  }
+  L::draw_hint(pe, b, g, meta.rng, ls.mask[2], lane);
   if (o.before_features && !pe.observation_raises()) {   // (uniform)
-    if constexpr (!COOP) {
-      if (lane == 0) pe.features(wf + 10);
+    if constexpr (!L::COOP) {   // (as play_game spells it)
+      if (lane == 0) pe.features(L::wf() + 10);
     } else {
       int sl = lane;   // (opaque, as in play_game)
       asm volatile("" : "+v"(sl));
-      coop_features<U>(pe, sl, true, wf + 10);
+      coop_features<U>(pe, sl, true, L::wf() + 10);
     }
     __syncthreads();
-    if (lane < 10) o.before_features[(size_t)g * 10 + lane] = wf[10 + lane];
+    if (lane < 10) o.before_features[(size_t)g * 10 + lane] = L::wf()[10 + lane];
   }
   __syncthreads();
 
   for (int base = 0; base < n_do; base += U) {
     const int n_act = n_do - base < U ? n_do - base : U;
-    {   // copy.deepcopy (stream window included) for the whole pass: lane l writes granule l of every column in use
+    {   // clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use
       __syncthreads();
-      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
+      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
       __syncthreads();
     }
     const bool active = lane < n_act;
     const size_t e = (size_t)g * K + base + (active ? lane : 0);   // this candidate's entry
     int a = 255;
-    if (active) a = nth_set_bit(rem, lane);
-    for (int i = 0; i < U; i++) {   // uniform: drop this pass's actions
-      if (rem[0]) rem[0] &= rem[0] - 1;
-      else if (rem[1]) rem[1] &= rem[1] - 1;
-      else rem[2] &= rem[2] - 1;
-    }
+    pass_actions(ls.rem, n_act, [&](const int l, const int act) { a = lane == l ? act : a; });
     int status = 0;
     if (active) {
       const int rd = ce.step(a);
@@ -177,10 +143,7 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
       int reward = 0, winner = -2;
       if (!f) {
         reward = rd & 1;
-        if (ce.have_winner()) {
-          const int b0 = ce.pl_base(0), b1 = ce.pl_base(1);
-          winner = (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1;
-        }
+        if (ce.have_winner()) winner = ce.winner_of(ce.pl_base(0), ce.pl_base(1));
       }
       status = f ? f : (ce.observation_raises() ? FAULT_INT_CARD : 0);
       o.action[e] = (uint8_t)a;
@@ -190,22 +153,13 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
     }
     const bool ok = active && status == 0;   // the successors that have features and an observation
     if (o.features) {   // (uniform)
-      if constexpr (!COOP) {
-        if (ok) {
-          double fa[10];
-          ce.features(fa);
-          for (int i = 0; i < 10; i++) o.features[e * 10 + i] = fa[i];
-        }
+      if constexpr (!L::COOP) {
+        double fa[10];
+        if (ok) L::cand_features(ce, fa, o.features + e * 10);
       } else {
         const unsigned long long part = __ballot(ok);   // (candidates sit on lanes 0 .. U-1)
         if (part) {
-          int sl = lane;   // (opaque, as in play_game)
-          asm volatile("" : "+v"(sl));
-          const int col = sl % U;
-          SubEngine se;
-          se.m.c16 = col * 16;
-          // the ten values of candidate c land in LDS at CF + c * 80 (the stacks are empty once the pass has stepped)
-          coop_features<U>(se, sl, (part >> col) & 1, (MSB_AS_LDS double*)(uintptr_t)(L::CF + col * 80));
+          L::coop_cand_features(part, lane, L::CF);   // (the stacks are empty once the pass has stepped)
           __syncthreads();
           for (int i = lane; i < U * 10; i += 64)
             if ((part >> (i / 10)) & 1) o.features[((size_t)g * K + base) * 10 + i] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[i];
@@ -218,7 +172,7 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
       MSB_AS_LDS uint8_t* ord = (MSB_AS_LDS uint8_t*)(uintptr_t)L::CF;   // (the features have left CF, the stacks are empty)
       for (int c = 0; c < n_act; c++) {
         if (!((part >> c) & 1)) continue;   // (uniform)
-        SubEngine se;
+        typename L::SubEngine se;
         se.m.c16 = c * 16;
         const int lo = se.local(), dn = se.pl_deck_n(lo);
         __syncthreads();   // the order of the candidate before has been read
@@ -240,14 +194,10 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
 #endif
     }
   }
-#undef MSB_EACH_GRANULE
 }
 
 // k_env_after<U, W> at the build's default variant (env_after.hip).
-struct EnvAfterOps {
-  int lanes, wpe;   // U, W
-  int lds_bytes;    // dynamic LDS of one workgroup
-  hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
+struct EnvAfterOps : KernelOps {
   void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, monsoon_env_after out, int n, int max_after);
 };
 const EnvAfterOps* monsoon_env_after_ops();

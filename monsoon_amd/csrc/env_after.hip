@@ -1,19 +1,11 @@
 // env_after.hip -- the afterstates of every legal action of every vector-env slot (monsoon_env_afterstates_dev,
 // include/monsoon.h): k_env_after runs the hot kernel's look-ahead for a learner instead of a score (env_after.h
-// after_slot<U>).  One instantiation per record build, at the build's default variant (the first entry of variants.def):
-// each instantiation is a full compilation of the rules core.  It serves every handle, whatever lanes_per_game it was
-// opened with.
+// after_slot<U>).  One instantiation per record build, at the build's default variant (kernels.h DEFAULT_U, DEFAULT_W).
 #include "env_after.h"
 
 using namespace msbk;
 
 namespace {
-
-#include "variants.def"
-#define X(U, W) {U, W},
-constexpr int kVariants[][2] = {MSB_VARIANTS(X)};
-#undef X
-constexpr int AFTER_U = kVariants[0][0], AFTER_W = kVariants[0][1];
 
 // One wavefront per slot at a time: the grid is the wavefronts the GPU holds at once (at most n), and wavefront w takes
 // slots w, w + grid, ...  Every slot is one decision's worth of look-ahead, so the slots are dealt out in advance: no pop
@@ -29,12 +21,12 @@ __global__ void __launch_bounds__(64, WPE) k_env_after(DevBuffers b, monsoon_env
 }
 
 hipError_t a_occupancy(int* blocks_per_cu, int lds_bytes) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_env_after<AFTER_U, AFTER_W>, 64, lds_bytes);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_env_after<DEFAULT_U, DEFAULT_W>, 64, lds_bytes);
 }
 void a_launch(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, monsoon_env_after out, int n, int max_after) {
-  hipLaunchKernelGGL((k_env_after<AFTER_U, AFTER_W>), dim3(grid), dim3(64), lds_bytes, stream, b, out, n, max_after);
+  hipLaunchKernelGGL((k_env_after<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, out, n, max_after);
 }
-const EnvAfterOps kOps = {AFTER_U, AFTER_W, PlayLds<AFTER_U>::TOTAL, a_occupancy, a_launch};
+const EnvAfterOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, a_occupancy}, a_launch};
 
 }  // namespace
 

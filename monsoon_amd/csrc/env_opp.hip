@@ -1,56 +1,40 @@
 // env_opp.hip -- the vector env's heuristic opponent (monsoon_env_config.opponent = 2): k_env_opp plays the reference's
 // HeuristicAgent for every slot on one of the env's two slot lists, with the hot kernel's decision loop
-// (kernels.h play_game<U, true>).  One instantiation per record build, at the build's default variant (the first entry
-// of variants.def): each instantiation is a full compilation of the rules core.  It serves every handle, whatever
-// lanes_per_game it was opened with.
+// (kernels.h play_game<U, true>).  One instantiation per record build, at the build's default variant (kernels.h
+// DEFAULT_U, DEFAULT_W).
 #include "env.h"
 
 using namespace msbk;
 
 namespace {
 
-#include "variants.def"
-#define X(U, W) {U, W},
-constexpr int kVariants[][2] = {MSB_VARIANTS(X)};
-#undef X
-constexpr int OPP_U = kVariants[0][0], OPP_W = kVariants[0][1];
-
-// Persistent wavefronts over list `list` (k_play's scheme: POP_PARTS ranges, one pop counter per range).  The list's
-// length is read on the device, so the launch captures into a graph; the waves of an empty range leave at once.  The
-// two launches of an env step use list 0 and list 1, and with them counter sets 0 and 1: each launch clears the other
-// set, so every replay of a captured step starts from cleared counters (monsoon_env_reset zeroes both).
+// Persistent wavefronts over list `list` (k_play's scheme, kernels.h pop_games: POP_PARTS ranges, one pop counter per
+// range).  The list's length is read on the device, so the launch captures into a graph; the waves of an empty range
+// leave at once -- most steps leave most waves nothing to do.  The two launches of an env step use list 0 and list 1, and
+// with them counter sets 0 and 1: each launch clears the other set, so every replay of a captured step starts from
+// cleared counters (monsoon_env_reset zeroes both).
 template <int U, int WPE>
 __global__ void __launch_bounds__(64, WPE) k_env_opp(DevBuffers b, EnvDev v, int list) {
   const int lane = threadIdx.x;
-  int* mine = v.opp_pop + list * POP_PARTS * POP_STRIDE;
-  int* other = v.opp_pop + (list ^ 1) * POP_PARTS * POP_STRIDE;
-  if (blockIdx.x == 0 && lane < POP_PARTS) other[lane * POP_STRIDE] = 0;
   const int n = __builtin_amdgcn_readfirstlane(v.opp_count[list * ENV_COUNT_STRIDE]);
-  const int part = blockIdx.x % POP_PARTS, rank = blockIdx.x / POP_PARTS;
-  const int lo = (int)((long long)n * part / POP_PARTS), hi = (int)((long long)n * (part + 1) / POP_PARTS);
-  int t = lo + rank;
-  if (t >= hi) return;   // uniform: most steps leave most waves nothing to do
-  const int waves = ((int)gridDim.x - part + POP_PARTS - 1) / POP_PARTS;
-  lds_init_wtab(b.wk_ovf + (size_t)blockIdx.x * (U * OVF_WORDS));
-  const int32_t* slots = v.opp_list + (size_t)list * v.cap;
-  const EnvPolicy pol{v.opp_rows, v.bot_steps, v.opp_lookahead, v.agent_side, v.max_steps};
-  while (t < hi) {
-    int nxt = 0x7fffffff;
-    if (lane == 0) nxt = lo + waves + atomicAdd(&mine[part * POP_STRIDE], 1);
-    const int g = __builtin_amdgcn_readfirstlane(slots[t]);
-    play_game<U, true>(b, g, lane, 0x7fff, ENV_OPP_BOUND, 0, pol);
-    __syncthreads();   // the LDS image is reused by the next slot
-    t = __builtin_amdgcn_readfirstlane(nxt);
-  }
+  pop_games(
+      v.opp_pop + list * POP_PARTS * POP_STRIDE, v.opp_pop + (list ^ 1) * POP_PARTS * POP_STRIDE, n, 0, 1, lane,
+      [&] { lds_init_wtab(b.wk_ovf + (size_t)blockIdx.x * (U * OVF_WORDS)); },
+      [&](const int t) {
+        const int32_t* slots = v.opp_list + (size_t)list * v.cap;
+        const EnvPolicy pol{v.opp_rows, v.bot_steps, v.opp_lookahead, v.agent_side, v.max_steps};
+        const int g = __builtin_amdgcn_readfirstlane(slots[t]);
+        play_game<U, true>(b, g, lane, 0x7fff, ENV_OPP_BOUND, 0, pol);
+      });
 }
 
 hipError_t o_occupancy(int* blocks_per_cu, int lds_bytes) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_env_opp<OPP_U, OPP_W>, 64, lds_bytes);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_env_opp<DEFAULT_U, DEFAULT_W>, 64, lds_bytes);
 }
 void o_launch(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list) {
-  hipLaunchKernelGGL((k_env_opp<OPP_U, OPP_W>), dim3(grid), dim3(64), lds_bytes, stream, b, v, list);
+  hipLaunchKernelGGL((k_env_opp<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, v, list);
 }
-const EnvOppOps kOps = {OPP_U, OPP_W, PlayLds<OPP_U>::TOTAL, o_occupancy, o_launch};
+const EnvOppOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, o_occupancy}, o_launch};
 
 }  // namespace
 

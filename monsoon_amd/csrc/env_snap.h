@@ -34,7 +34,7 @@ static_assert(offsetof(GameMeta, result) == 8 && offsetof(GameMeta, steps) == 12
 
 struct EnvSnapOps {
   int entry_bytes;
-  hipError_t (*occupancy)(int* blocks_per_cu);   // of the copy kernels (the smaller of the two)
+  hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);   // of the copy kernels (the smaller of the two).  lds_bytes is 0 for them: the argument is there so that the host's resident_waves() takes this query like a KernelOps one
   // grid = workgroups of SNAP_WAVES wavefronts
   void (*save)(int grid, hipStream_t stream, DevBuffers b, EnvDev v, int n, void* entries, const int32_t* slots, int m, uint32_t version);
   void (*load)(int grid, hipStream_t stream, DevBuffers b, EnvDev v, int n, const void* entries, int n_entries, const int32_t* src,

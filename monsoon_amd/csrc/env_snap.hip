@@ -120,11 +120,11 @@ __global__ void __launch_bounds__(64 * SNAP_WAVES) k_env_load(DevBuffers b, EnvD
   }
 }
 
-hipError_t s_occupancy(int* blocks_per_cu) {
+hipError_t s_occupancy(int* blocks_per_cu, int lds_bytes) {
   int a = 0, c = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_env_save, 64 * SNAP_WAVES, 0);
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_env_save, 64 * SNAP_WAVES, lds_bytes);
   if (e != hipSuccess) return e;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k_env_load, 64 * SNAP_WAVES, 0);
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k_env_load, 64 * SNAP_WAVES, lds_bytes);
   *blocks_per_cu = a < c ? a : c;
   return e;
 }

@@ -1,7 +1,10 @@
 // kernels.h -- device code shared by every translation unit of libmonsoon_hip.so: per-game buffers, stream-block
-// maintenance, and the hot kernel k_play as a template over {candidate lanes per game U, waves per SIMD W}.  Each
-// instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); monsoon_hip.hip holds the API kernels and the host side.
+// maintenance, the pieces of a decision's look-ahead (PlayLds<U>, legal_set, MSB_EACH_GRANULE), the decision loop made of
+// them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
+// {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
+// Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, env_opp.hip and env_after.hip hold one further
+// instantiation each; monsoon_hip.hip holds the API kernels and the host side.
 //
 // Execution model
 //   * Hot kernel k_play<U,W>: ONE WAVEFRONT PER GAME at a time (a persistent grid of resident wavefronts, each popping
@@ -207,25 +210,15 @@ constexpr int LDS_ORIGIN = LDS_RECORDS;
 // 10 weights + 10 "before" + 10 "best after" features | the candidates' work stacks (SKW words each, interleaved word by
 // word), which hold their "after" features once a pass has stepped
 // ------------------------------------------------------------------------------------------------
-__device__ MSB_INL int nth_set_bit(const uint64_t mask[3], int k) {
-  for (int w = 0; w < 3; w++) {
-    int c = __popcll(mask[w]);
-    if (k < c) {
-      uint64_t m = mask[w];
-      for (int i = 0; i < k; i++) m &= m - 1;
-      return w * 64 + __ffsll((long long)m) - 1;
-    }
-    k -= c;
-  }
-  return -1;
-}
-
 __device__ MSB_INL unsigned long long uni64(unsigned long long v) {   // a wave-uniform 64-bit value into scalar registers
   unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
   unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
   return ((unsigned long long)hi << 32) | lo;
 }
 
+// The pieces of a decision's look-ahead, named once per U: the LDS map, the engines, which forms the build uses, and the
+// steps of a decision that work on LDS and scalars.  play_game (below) and after_slot (env_after.h) compose them; a new
+// consumer of the look-ahead does too.
 template <int U>
 struct PlayLds {
   static constexpr int PRIV = LDS_ORIGIN;
@@ -234,7 +227,81 @@ struct PlayLds {
   static constexpr int SKB = WF + 240;               // work stacks of the U candidate lanes ...
   static constexpr int CF = SKB;                     // ... and, once a pass has stepped (stacks empty), their ten "after" features each (f64)
   static constexpr int TOTAL = SKB + U * SKW * 4;
+  typedef Engine<Col0Mem<U, PRIV>> ParEngine;               // the current record: candidate column 0
+  typedef Engine<LaneMem<U, PRIV, SKB, SKW>> CandEngine;    // candidate `lane`'s private copy
+  typedef Engine<SubColMem<U, PRIV>> SubEngine;             // candidate (lane % U)'s record, read only: the wave-cooperative features
+  static constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
+  // Features by the whole wave (coop_features.h) where a candidate has sub-lanes to spare, on the standard record.  The
+  // extended records keep the serial form: with 2 x 12 VGPRs of record per lane next to the phase's temporaries the
+  // register allocator spilled them (k_play<8,2>: 0 -> 312 spilled VGPRs, scratch 3 168 -> 3 408 B), see DESIGN.md section 4.
+  static constexpr bool COOP = U < 64 && GPL == 1;
+  // The weighted draw of the REPLACE candidates resolved once per decision by the whole wave (coop_draw.h): standard record.
+#if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
+  static constexpr bool COOP_DRAW = GPL == 1;
+#else
+  static constexpr bool COOP_DRAW = false;
+#endif
+  static __device__ MSB_INL MSB_AS_LDS u32x4* priv() { return (MSB_AS_LDS u32x4*)(uintptr_t)PRIV; }   // granule c of column l: priv()[c * U + l]
+  static __device__ MSB_INL MSB_AS_LDS double* wf() { return (MSB_AS_LDS double*)(uintptr_t)WF; }
+  // What the first draw of this decision's REPLACE steps (actions 148..151) will find, into DRAW_HINT_LDS (coop_draw.h);
+  // the candidates read it after the next barrier, wherever in the passes they sit.  A decision without such a
+  // candidate clears the word the one before it left.
+  static __device__ MSB_INL void draw_hint(ParEngine& pe, const DevBuffers& b, const int g, const uint32_t rng, const uint64_t mask2, const int lane) {
+    if constexpr (COOP_DRAW) {
+      uint32_t hint = 0u;
+      if ((mask2 >> (148 - 128)) & 0xfull) {   // (uniform)
+        const bool u_ok = (rng & 0xffffu) + 1u < (uint32_t)(2 * MT_N);
+        const uint32_t ra = u_ok ? peek_u32(b, g, rng) : 0u, rb = u_ok ? peek_u32(b, g, rng + 1u) : 0u;
+        int sl = lane;   // (opaque, as for the features below)
+        asm volatile("" : "+v"(sl));
+        hint = coop_draw(pe, sl, ra, rb, u_ok);
+      }
+      if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = hint;
+    }
+  }
+  // The features of the candidates in `part` (a ballot over lanes 0 .. U-1) by the whole wave: lane l is sub-lane l / U of
+  // candidate l % U, whose ten values land in LDS at dst + (l % U) * 80.  Returns that row.
+  static __device__ MSB_INL MSB_AS_LDS double* coop_cand_features(const unsigned long long part, const int lane, const int dst) {
+    int sl = lane;   // (opaque: what derives from it is computed here, not hoisted out of the game loop and spilled)
+    asm volatile("" : "+v"(sl));
+    const int col = sl % U;
+    const bool on = (part >> col) & 1;
+    SubEngine se;
+    se.m.c16 = col * 16;
+    MSB_AS_LDS double* cfc = (MSB_AS_LDS double*)(uintptr_t)(dst + col * 80);
+    coop_features<U>(se, sl, on, cfc);
+    return cfc;
+  }
+  // The serial form: candidate `lane` computes its own ten values (fa, for the score) and leaves them at dst.
+  template <class P>
+  static __device__ MSB_INL void cand_features(CandEngine& ce, double (&fa)[10], P dst) {
+    ce.features(fa);
+    for (int i = 0; i < 10; i++) dst[i] = fa[i];
+  }
 };
+
+// The legal set of the current record as wave-uniform scalars; `rem` loses the U lowest actions with every pass.
+struct LegalSet {
+  uint64_t mask[3], rem[3];
+  int n;
+};
+template <class E>
+__device__ MSB_INL LegalSet legal_set(E& pe) {
+  const msb_u64x4 lm = pe.legal_mask_v();
+  const uint64_t m0 = uni64(lm[0]), m1 = uni64(lm[1]), m2 = uni64(lm[2]);
+  const int n = __popcll(m0) + __popcll(m1) + __popcll(m2);
+  return LegalSet{{m0, m1, m2}, {m0, m1, m2}, n};
+}
+
+// Lane `lane_`'s share of a record: granules lane_, lane_ + 64, ... (gr_), the j_-th of them in element j_ of a register
+// array u32x4[GPL_].  The moves of a record between HBM, registers and the candidate columns are spelled with it in
+// place -- load: v[j_] = grec[gr_]; column c: priv[gr_ * U + c] -- and not as functions: handed the register array by
+// reference, pointer, value or lambda capture, a function cost k_play<8,5> up to 16 bytes of scratch.
+#define MSB_EACH_GRANULE(GPL_, lane_, body_)            \
+  _Pragma("unroll") for (int j_ = 0; j_ < GPL_; j_++) { \
+    const int gr_ = lane_ + 64 * j_;                    \
+    if (gr_ < SG) { body_; }                            \
+  }
 
 // The vector env's heuristic opponent (opponent 2, env_opp.hip): what play_game<U, true> needs beyond DevBuffers.
 constexpr int ENV_OPP_BOUND = 64;   // opponent decisions per call before FAULT_OPP_BOUND (a guard, include/monsoon.h)
@@ -255,15 +322,15 @@ struct EnvPolicy {
 // expert_action() and, unless that raised, step() on column 0 -- the current record's image with the stream window
 // attached -- and column 0 is then "the best successor" that the commit takes over.
 //
-// MSB_COMMIT_BEST is that commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
+// MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
 // whole wave (the used-up block becomes the new "next" block; the twist buffer is the column area, hence the second copy
 // of v_best); the committed successor's features (feat_ok: wf[20..29] holds them) become the "before" side of the next
-// decision.  It is a macro because the bot's round expands it a second time: the instantiations without a bot then see the
-// statements they always had, in place, and compile to the same instructions as before.
+// decision.  It is the one macro local to play_game: it moves the register arrays, and the bot's round expands it a
+// second time.
 #define MSB_COMMIT_BEST()                                                                           \
   __syncthreads();                                                                                  \
-  MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])                                                      \
+  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_best[j_])                                                      \
   __syncthreads();                                                                                  \
   {                                                                                                 \
     uint32_t new_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe.rng_pos());                 \
@@ -271,7 +338,7 @@ struct EnvPolicy {
     if (new_pos >= (uint32_t)MT_N) {                                                                \
       new_pos -= MT_N;                                                                              \
       wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);                                     \
-      MSB_EACH_GRANULE(priv[gr_ * U] = v_best[j_])                                                  \
+      MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_best[j_])                                                  \
       __syncthreads();                                                                              \
       cur ^= 1;                                                                                     \
       if (lane == 0) pe.rng_block_advance();                                                        \
@@ -281,26 +348,12 @@ struct EnvPolicy {
     have_before = feat_ok != 0;                                                                     \
     if (have_before && lane < 10) wf[10 + lane] = wf[20 + lane];                                    \
     __syncthreads();                                                                                \
-    MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])                                                     \
+    MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])                                                     \
   }
 template <int U, bool ENV = false, bool VS = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol) {
   typedef PlayLds<U> L;
-  typedef Engine<Col0Mem<U, L::PRIV>> ParEngine;
-  typedef Engine<LaneMem<U, L::PRIV, L::SKB, SKW>> CandEngine;
-  typedef Engine<SubColMem<U, L::PRIV>> SubEngine;   // candidate (lane % U)'s record, read only: the wave-cooperative features
-  constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
-  // Features by the whole wave (coop_features.h) where a candidate has sub-lanes to spare, on the standard record.  The
-  // extended records keep the serial form: with 2 x 12 VGPRs of record per lane next to the phase's temporaries the
-  // register allocator spilled them (k_play<8,2>: 0 -> 312 spilled VGPRs, scratch 3 168 -> 3 408 B), see DESIGN.md section 4.
-  constexpr bool COOP = U < 64 && GPL == 1;
-  // The weighted draw of the REPLACE candidates resolved once per decision by the whole wave (coop_draw.h): standard record.
-#if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
-  constexpr bool COOP_DRAW = GPL == 1;
-#else
-  constexpr bool COOP_DRAW = false;
-#endif
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
   if (meta.result != -2) {
@@ -311,27 +364,22 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     return;
   }
   PROF_DECL();
-  MSB_AS_LDS u32x4* priv = (MSB_AS_LDS u32x4*)(uintptr_t)L::PRIV;
-  MSB_AS_LDS double* wf = (MSB_AS_LDS double*)(uintptr_t)L::WF;
+  MSB_AS_LDS u32x4* priv = L::priv();
+  MSB_AS_LDS double* wf = L::wf();
   MSB_AS_LDS double* cf = (MSB_AS_LDS double*)(uintptr_t)(L::CF + (lane < U ? lane : 0) * 80);   // this candidate lane's features
   u32x4* grec = (u32x4*)(b.state + (size_t)g * SW);
-  u32x4 v_par[GPL], v_best[GPL];   // granules lane, lane + 64, ... of the current record / of the best successor so far
-#define MSB_EACH_GRANULE(body_)                   \
-  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) { \
-    const int gr_ = lane + 64 * j_;               \
-    if (gr_ < SG) { body_; }                      \
-  }
-  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
-  MSB_EACH_GRANULE(v_par[j_] = grec[gr_])   // coalesced 16-B-per-lane loads, straight into registers
-  _Pragma("unroll") for (int j_ = 0; j_ < GPL; j_++) v_best[j_] = v_par[j_];
-  ParEngine pe;
-  CandEngine ce;
-  // the image of the current record in column 0; with the stream window attached it is also what the clones start from
-  MSB_EACH_GRANULE(priv[gr_ * U] = v_par[j_])
+  u32x4 v_par[L::GPL], v_best[L::GPL];   // granules lane, lane + 64, ... of the current record / of the best successor so far
+  _Pragma("unroll") for (int j_ = 0; j_ < L::GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = grec[gr_])   // coalesced 16-B-per-lane loads, straight into registers
+  _Pragma("unroll") for (int j_ = 0; j_ < L::GPL; j_++) v_best[j_] = v_par[j_];
+  typename L::ParEngine pe;
+  typename L::CandEngine ce;
+  // stage: the image of the current record in column 0; with the stream window attached it is also what the clones start from
+  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
   __syncthreads();
   if (lane == 0) attach_rng(pe, b, g, meta.rng);
   __syncthreads();
-  MSB_EACH_GRANULE(v_par[j_] = priv[gr_ * U])
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])
   bool have_before = false;   // wf[10..19] holds the features of the CURRENT state (the committed successor's)
   double last_score = NAN;
   int played = 0;
@@ -343,7 +391,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     } else if (pe.have_winner() || meta.steps >= max_turns) {   // rollout contract: while not have_winner() and steps < max_turns
       int b0 = pe.pl_base(0), b1 = pe.pl_base(1);
       int res = -1;
-      if (pe.have_winner()) res = (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1;
+      if (pe.have_winner()) res = pe.winner_of(b0, b1);
       meta.result = (int8_t)res;
       if (pe.have_winner()) meta.flags |= 1;
       if (played == 0) {
@@ -356,7 +404,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if ((pe.local() == 0 ? meta.p1 : meta.p2) < 0) {   // (uniform) the scripted bot is to play
         int a = 155, f = 0, fs = 0;
         if (lane == 0) {   // (the other lanes wait at the barrier)
-          if constexpr (COOP_DRAW) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;   // the bot's own REPLACE draws serially
+          if constexpr (L::COOP_DRAW) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;   // the bot's own REPLACE draws serially
           a = ce.expert_action();
           f = ce.fault();   // random.choice([]) inside the bot: nothing is stepped, the game ends
           if (!f) {
@@ -369,7 +417,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         a = __builtin_amdgcn_readfirstlane(a);
         f = __builtin_amdgcn_readfirstlane(f);
         fs = __builtin_amdgcn_readfirstlane(fs);
-        MSB_EACH_GRANULE(v_best[j_] = priv[gr_ * U])   // the successor (if the bot raised: the record with its cursor moved on)
+        MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U])   // the successor (if the bot raised: the record with its cursor moved on)
         constexpr int feat_ok = 0;   // the bot's successor has no features: the next decision computes its "before" side
         MSB_COMMIT_BEST()
         if (!f) {   // one committed transition, no decision, no look-ahead
@@ -391,26 +439,10 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       asm volatile("" : : "v"(lm2[0]), "v"(lm2[1]), "v"(lm2[2]) : "memory");
     }
 #endif
-    const msb_u64x4 lm = pe.legal_mask_v();
-    // the legal set as wave-uniform scalars; `rem` loses the U lowest actions with every pass, which hands them to its
-    // candidate lanes from the scalar unit (pass_glue.h)
-    const uint64_t mask[3] = {uni64(lm[0]), uni64(lm[1]), uni64(lm[2])};
-    uint64_t rem[3] = {mask[0], mask[1], mask[2]};
-    const int n_legal = __popcll(mask[0]) + __popcll(mask[1]) + __popcll(mask[2]);
+    LegalSet ls = legal_set(pe);
+    const int n_legal = ls.n;
     PROF_MARK(1);   // legal mask
-    if constexpr (COOP_DRAW) {
-      // what the first draw of this decision's REPLACE steps (actions 148..151) will find; the candidates read it after
-      // the barrier below, wherever in the passes they sit
-      uint32_t hint = 0u;
-      if ((mask[2] >> (148 - 128)) & 0xfull) {   // (uniform)
-        const bool u_ok = (meta.rng & 0xffffu) + 1u < (uint32_t)(2 * MT_N);
-        const uint32_t ra = u_ok ? peek_u32(b, g, meta.rng) : 0u, rb = u_ok ? peek_u32(b, g, meta.rng + 1u) : 0u;
-        int sl = lane;   // (opaque, as for the features below)
-        asm volatile("" : "+v"(sl));
-        hint = coop_draw(pe, sl, ra, rb, u_ok);
-      }
-      if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = hint;
-    }
+    L::draw_hint(pe, b, g, meta.rng, ls.mask[2], lane);
     const bool before_raises = pe.observation_raises();
     // weights and "before" features are parked in LDS: 40 fewer live VGPRs across the recursive step calls
     {
@@ -418,8 +450,10 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if (lane < 10) wf[lane] = wt[lane];
       // The "before" features of this decision are the "after" features the previous decision computed for the
       // successor it committed (same state, same mover); only the first decision of a call computes them.
+      // (in place, like the hand-out of a pass's actions below: as a PlayLds function each of the two gave the extended
+      // record's k_play<4,3> seven scratch instructions more)
       if (!before_raises && !have_before) {   // (uniform)
-        if constexpr (!COOP) {
+        if constexpr (!L::COOP) {
           if (lane == 0) pe.features(wf + 10);
         } else {
           int sl = lane;   // (opaque: what derives from it is computed here, not hoisted out of the game loop and spilled)
@@ -440,20 +474,20 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     int la_fault = 0;                 // first build-limit fault a look-ahead of this decision hit
     for (int base = 0; base < n_legal; base += U) {
       double s = 0.0;   // except Exception -> 0.0 (evo/heuristic_agent.py:48-51)
-      int a = NONE_A;
       int my_fault = 0;
       int my_feat = 0;
       int f = 0;
       bool raises = false;
       const int n_act = n_legal - base < U ? n_legal - base : U;   // (uniform) the candidates of this pass: lanes 0 .. n_act-1
-      {   // copy.deepcopy (stream window included) for the whole pass: lane l writes granule l of every column in use
+      {   // clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use
         __syncthreads();
-        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
       }
       const bool active = lane < n_act;
       // lane l takes the (base + l)-th legal action, handed out by the scalar unit; `rem` loses them (pass_glue.h)
-      pass_actions(rem, n_act, [&](const int l, const int act) { a = lane == l ? act : a; });
+      int a = NONE_A;
+      pass_actions(ls.rem, n_act, [&](const int l, const int act) { a = lane == l ? act : a; });
 #if defined(MSB_STUDY_REPEAT)
       // study build only (scripts/step_cost.sh): the look-ahead step (or a prefix of it, MSB_STUDY_CUT_AT) and its clone
       // executed once more, so that the difference of two counter runs is the cost of exactly that
@@ -464,7 +498,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         if (active) ce.step(a);
 #endif
         __syncthreads();
-        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(priv[gr_ * U + col] = v_par[j_])
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
         __syncthreads();
       }
 #endif
@@ -478,7 +512,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       // The candidates that get features and a score; all of them run the same code now, so the whole wave works on it:
       // lane l is sub-lane l / U of candidate l % U (coop_features.h).  !COOP: the serial form.
       const bool scored = active && f == 0 && !before_raises && !raises;
-      if constexpr (!COOP) {
+      if constexpr (!L::COOP) {
         if (scored) {
           // the ten values go to LDS for the winner's sake (argmax below) and feed the score from registers
           double fa[10];
@@ -486,34 +520,25 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           {   // study build: the candidate's features and its score computed once more
             double fb[10];
             ce.features(fb);
-            double s2 = CandEngine::action_score_lds(wf, fb);
+            double s2 = L::CandEngine::action_score_lds(wf, fb);
             asm volatile("" : : "v"(s2), "v"(fb[0]), "v"(fb[9]) : "memory");
           }
 #endif
-          ce.features(fa);
-          for (int i = 0; i < 10; i++) cf[i] = fa[i];
-          s = CandEngine::action_score_lds(wf, fa);
+          L::cand_features(ce, fa, cf);
+          s = L::CandEngine::action_score_lds(wf, fa);
           my_feat = 1;
         }
       } else {
         const unsigned long long part = __ballot(scored);   // (candidates sit on lanes 0 .. U-1)
         if (part) {
-          int sl = lane;   // (opaque: what derives from it is computed here, not hoisted out of the game loop and spilled)
-          asm volatile("" : "+v"(sl));
-          const int col = sl % U;
-          const bool on = (part >> col) & 1;
-          SubEngine se;
-          se.m.c16 = col * 16;
-          MSB_AS_LDS double* cfc = (MSB_AS_LDS double*)(uintptr_t)(L::CF + col * 80);   // the features of this lane's candidate
-          // the ten values go to LDS (cf), for the score and for the winner's sake (argmax below)
+          // the ten values go to LDS (CF), for the score and for the winner's sake (argmax below)
 #if defined(MSB_STUDY_FEATURES)
           {   // study build: the candidates' features and their scores computed once more
-            coop_features<U>(se, sl, on, cfc);
-            double s2 = coop_score(wf, cfc);
+            double s2 = coop_score(wf, L::coop_cand_features(part, lane, L::CF));
             asm volatile("" : : "v"(s2) : "memory");
           }
 #endif
-          coop_features<U>(se, sl, on, cfc);
+          MSB_AS_LDS double* cfc = L::coop_cand_features(part, lane, L::CF);
           if (scored) {
             s = coop_score(wf, cfc);
             my_feat = 1;
@@ -556,7 +581,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         if (feat_ok && lane < 10)   // the winner keeps its features: the next decision's "before" side
           wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl * 10 + lane];
         __syncthreads();
-        MSB_EACH_GRANULE(v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
+        MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
       }
       PROF_MARK(6);   // argmax + new best into registers
     }
@@ -577,8 +602,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     }
     if constexpr (ENV) {   // the env's end rules (env.inc env_after_step): the fault above, then a winner, then truncation
       if (pe.have_winner()) {
-        const int b0 = pe.pl_base(0), b1 = pe.pl_base(1);
-        meta.result = (int8_t)((b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1);
+        meta.result = (int8_t)pe.winner_of(pe.pl_base(0), pe.pl_base(1));
         meta.flags |= 1;
         break;
       }
@@ -597,8 +621,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       meta.fault = FAULT_OPP_BOUND;
     }
   }
-  MSB_EACH_GRANULE(grec[gr_] = v_par[j_])
-#undef MSB_EACH_GRANULE
+  MSB_EACH_GRANULE(L::GPL, lane, grec[gr_] = v_par[j_])
 #undef MSB_COMMIT_BEST
   if (lane == 0) {
     b.meta[g] = meta;
@@ -627,6 +650,28 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_env_opp): `mine` / `other` are this launch's counter
+// set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
+// nothing for it leaves before enter(), which runs once ahead of the first game.
+template <class Enter, class Play>
+__device__ MSB_INL void pop_games(int* mine, int* other, const int n, const int g0, const int persistent, const int lane, Enter enter, Play play) {
+  if (persistent && blockIdx.x == 0 && lane < POP_PARTS) other[lane * POP_STRIDE] = 0;
+  const int part = blockIdx.x % POP_PARTS, rank = blockIdx.x / POP_PARTS;
+  const int waves = ((int)gridDim.x - part + POP_PARTS - 1) / POP_PARTS;   // wavefronts working on this range
+  const int lo = g0 + (persistent ? (int)((long long)n * part / POP_PARTS) : 0);
+  const int hi = g0 + (persistent ? (int)((long long)n * (part + 1) / POP_PARTS) : n);
+  int t = persistent ? lo + rank : g0 + (int)blockIdx.x;
+  if (t >= hi) return;   // uniform
+  enter();
+  while (t < hi) {
+    int nxt = 0x7fffffff;
+    if (persistent && lane == 0) nxt = lo + waves + atomicAdd(&mine[part * POP_STRIDE], 1);
+    play(t);
+    __syncthreads();   // the LDS image is reused by the next game
+    t = __builtin_amdgcn_readfirstlane(nxt);
+  }
+}
+
 template <int U, int WPE>
 __global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent, int parity,
                                                   int g0, int half) {
@@ -636,31 +681,31 @@ __global__ void __launch_bounds__(64, WPE) k_play(DevBuffers b, int n, int max_t
   // one game that is never refilled
   int* mine = b.pop + (2 * half + parity) * POP_PARTS * POP_STRIDE;
   int* other = b.pop + (2 * half + (parity ^ 1)) * POP_PARTS * POP_STRIDE;
-  if (persistent && blockIdx.x == 0 && lane < POP_PARTS) other[lane * POP_STRIDE] = 0;
-  const int part = blockIdx.x % POP_PARTS, rank = blockIdx.x / POP_PARTS;
-  const int waves = ((int)gridDim.x - part + POP_PARTS - 1) / POP_PARTS;   // wavefronts working on this range
-  const int lo = g0 + (persistent ? (int)((long long)n * part / POP_PARTS) : 0);
-  const int hi = g0 + (persistent ? (int)((long long)n * (part + 1) / POP_PARTS) : n);
-  int t = persistent ? lo + rank : g0 + (int)blockIdx.x;
-  while (t < hi) {
-    int nxt = 0x7fffffff;
-    if (persistent && lane == 0) nxt = lo + waves + atomicAdd(&mine[part * POP_STRIDE], 1);
-    play_game<U, false>(b, t, lane, max_turns, rounds, write_scores, EnvPolicy{});
-    __syncthreads();   // the LDS image is reused by the next game
-    t = __builtin_amdgcn_readfirstlane(nxt);
-  }
+  pop_games(mine, other, n, g0, persistent, lane, [] {},
+            [&](const int t) { play_game<U, false>(b, t, lane, max_turns, rounds, write_scores, EnvPolicy{}); });
 }
 
-// What the host needs to launch one variant (variant.hip defines one getter per instantiation).
-struct VariantOps {
+// What the host needs to launch a kernel that instantiates the look-ahead.
+struct KernelOps {
   int lanes, wpe;           // U, W
   int lds_bytes;            // dynamic LDS of one workgroup
   hipError_t (*occupancy)(int* blocks_per_cu, int lds_bytes);
+};
+// ... one k_play variant (variant.hip defines one getter per instantiation)
+struct VariantOps : KernelOps {
   void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int write_scores, int persistent,
                int parity, int g0, int half);   // games [g0, g0 + n) as sub-batch `half` (k_play_vs: 0, 0 only)
 };
 
-// k_play_vs<U, W> at the build's default variant (vs_expert.hip): the rollout kernel that knows the scripted bot.
+// The build's default variant, the first entry of variants.def: k_play_vs, k_env_opp and k_env_after exist at this one only
+// (each instantiation is a full compilation of the rules core) and serve every handle, whatever lanes_per_game it has.
+#include "variants.def"
+#define X(U, W) {U, W},
+constexpr int kVariants[][2] = {MSB_VARIANTS(X)};
+#undef X
+constexpr int DEFAULT_U = kVariants[0][0], DEFAULT_W = kVariants[0][1];
+
+// k_play_vs<DEFAULT_U, DEFAULT_W> (vs_expert.hip): the rollout kernel that knows the scripted bot.
 const VariantOps* monsoon_vs_expert_ops();
 
 }  // namespace msbk

@@ -1660,6 +1660,28 @@ static int grow_ovf(monsoon_t* h, size_t lanes) {
 static const int g_persistent = getenv("MONSOON_PERSIST") ? atoi(getenv("MONSOON_PERSIST")) : 1;
 static const int g_lds_pad = getenv("MONSOON_LDS_PAD") ? atoi(getenv("MONSOON_LDS_PAD")) : 0;   // occupancy experiments only
 
+// Compute units of the handle's device.
+static int device_cus(monsoon_t* h, int* out) {
+  if (!h->cu_count) {
+    hipDeviceProp_t prop;
+    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
+    h->cu_count = prop.multiProcessorCount;
+  }
+  *out = h->cu_count;
+  return MONSOON_OK;
+}
+
+// The workgroups of a kernel the device holds at once: what its occupancy query answers per compute unit, times the
+// compute units; `fallback` where the query answers nothing.
+static int resident_waves(monsoon_t* h, hipError_t (*occupancy)(int*, int), int lds_bytes, int fallback, int* out) {
+  int per_cu = 0, cus = 0;
+  const int rc = device_cus(h, &cus);
+  if (rc) return rc;
+  HIP_TRY(h, occupancy(&per_cu, lds_bytes));
+  *out = per_cu > 0 ? per_cu * cus : fallback;
+  return MONSOON_OK;
+}
+
 // `rounds` decisions of every loaded game in ONE launch (1 = a decision round; max_turns + 1 = whole games: the extra
 // round turns "still running at the cap" into a result).
 // vs = true: k_play_vs, the kernel that knows the scripted bot (the build's default variant, whatever the handle's is).
@@ -1673,11 +1695,8 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   const int lds = v->lds_bytes + g_lds_pad;
   int& grid_waves = vs ? h->vs_grid_waves : h->grid_waves;
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
-    HIP_TRY(h, v->occupancy(&per_cu, lds));
-    grid_waves = per_cu > 0 ? per_cu * prop.multiProcessorCount : 4096;
+    const int rc = resident_waves(h, v->occupancy, lds, 4096, &grid_waves);
+    if (rc) return rc;
   }
   // one decision per game and launch: two waves per slot measured best; many decisions per game: exactly the resident waves
   int grid = rounds > 1 ? grid_waves : 2 * grid_waves;
@@ -2085,17 +2104,6 @@ void* monsoon_stream(monsoon_t* h) {
 // ---- vector env (env.inc) -----------------------------------------------------------------------
 }  // extern "C"
 
-// Compute units of the handle's device.
-static int device_cus(monsoon_t* h, int* out) {
-  if (!h->cu_count) {
-    hipDeviceProp_t prop;
-    HIP_TRY(h, hipGetDeviceProperties(&prop, h->device));
-    h->cu_count = prop.multiProcessorCount;
-  }
-  *out = h->cu_count;
-  return MONSOON_OK;
-}
-
 // The heuristic opponent's turn for the slots of list `list`, then their views: two launches, no synchronisation.
 // k_env_opp reads the env's weight table through its own DevBuffers copy (monsoon_upload_weights' table is not touched).
 static int launch_env_opp(monsoon_t* h, int n, int list) {
@@ -2297,12 +2305,11 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     v.opp_count = (int32_t*)(h->d_opp + 16 * cap);
     v.opp_pop = (int*)(h->d_opp + 16 * cap + 4 * 2 * ENV_COUNT_STRIDE);
     const EnvOppOps* o = monsoon_env_opp_ops();
-    int per_cu = 0, cus = 0;
-    rc = device_cus(h, &cus);
+    int waves = 0;
+    rc = resident_waves(h, o->occupancy, o->lds_bytes, 4096, &waves);
     if (rc) return rc;
-    HIP_TRY(h, o->occupancy(&per_cu, o->lds_bytes));
     // persistent: the resident wavefronts, but no more than the slots, and one at least for each of the POP_PARTS ranges
-    h->opp_grid = std::max(POP_PARTS, std::min(per_cu > 0 ? per_cu * cus : 4096, n));
+    h->opp_grid = std::max(POP_PARTS, std::min(waves, n));
     rc = grow_ovf(h, (size_t)h->opp_grid * o->lanes);   // work-stack overflow blocks for every workgroup of k_env_opp
     if (rc) return rc;
     HIP_TRY(h, hipMemsetAsync(v.opp_count, 0, 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE), h->stream));
@@ -2311,22 +2318,16 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   {   // monsoon_env_afterstates_dev allocates nothing: its grid and the overflow blocks of its workgroups are settled here
     const EnvAfterOps* o = monsoon_env_after_ops();
     if (!h->after_waves) {
-      int per_cu = 0, cus = 0;
-      rc = device_cus(h, &cus);
+      rc = resident_waves(h, o->occupancy, o->lds_bytes, 4096, &h->after_waves);
       if (rc) return rc;
-      HIP_TRY(h, o->occupancy(&per_cu, o->lds_bytes));
-      h->after_waves = per_cu > 0 ? per_cu * cus : 4096;
     }
     h->after_grid = std::min(h->after_waves, n);
     rc = grow_ovf(h, (size_t)h->after_grid * o->lanes);
     if (rc) return rc;
   }
   if (!h->snap_blocks) {   // monsoon_env_save_dev / monsoon_env_load_dev query nothing
-    int per_cu = 0, cus = 0;
-    rc = device_cus(h, &cus);
+    rc = resident_waves(h, monsoon_env_snap_ops()->occupancy, 0, 1024, &h->snap_blocks);
     if (rc) return rc;
-    HIP_TRY(h, monsoon_env_snap_ops()->occupancy(&per_cu));
-    h->snap_blocks = per_cu > 0 ? per_cu * cus : 1024;
   }
   HIP_TRY(h, hipMemcpyAsync((void*)v.seed0, seed0, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
   if (decks) HIP_TRY(h, hipMemcpyAsync(v.decks, decks, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));

@@ -2340,6 +2340,8 @@ struct Engine {
 
   // Stormbound.have_winner, games/stormbound.py:560-561 (strict: a base at exactly 0 is alive)
   MSB_HD MSB_INL bool have_winner() const { return pl_base(0) < 0 || pl_base(1) < 0; }
+  // ... and who it is, from the two bases: 0 FIRST, 1 SECOND, -1 both fell (a draw)
+  MSB_HD static MSB_INL int winner_of(const int b0, const int b1) { return (b1 < 0 && b0 >= 0) ? 0 : (b0 < 0 && b1 >= 0) ? 1 : -1; }
 
   // Stormbound.legal_actions + Action.to_int, games/stormbound.py:528-557, 258-290 -> 156-bit mask
   // (three 64-bit words in a register vector)

@@ -13,7 +13,7 @@ void v_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, in
   hipLaunchKernelGGL((k_play<VAR_U, VAR_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, write_scores, persistent, parity,
                      g0, half);
 }
-const VariantOps kOps = {VAR_U, VAR_W, PlayLds<VAR_U>::TOTAL, v_occupancy, v_play};
+const VariantOps kOps = {{VAR_U, VAR_W, PlayLds<VAR_U>::TOTAL, v_occupancy}, v_play};
 }  // namespace
 
 #define MSB_CAT_(a, b, c) a##b##_##c
