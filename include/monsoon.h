@@ -208,6 +208,31 @@ int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_ind
                               int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                               int32_t* out_counts, int8_t* out_results, int32_t* out_steps);
 
+/* A rollout that writes down what it plays: everything monsoon_rollout_vs_expert does with the same arguments
+ * (MONSOON_PLAYER_EXPERT rows included: counts, results, steps, monsoon_rollout_faults, monsoon_get_stats,
+ * monsoon_state_hash of the last batch, the bot's rows staying in place), plus one log entry per COMMITTED STEP of every
+ * game.  Entry k of match i, at [i * max_turns + k], is the game's k-th committed step, so out_steps[i] is the number of
+ * entries of row i; behind them the row holds the padding values.
+ *  - A heuristic decision logs the action it committed, its best score -- the value monsoon_decide reports as out_score,
+ *    bit for bit -- and the number of legal actions it looked ahead over.  A decision whose commit faults is a logged
+ *    step, as it is a counted one.
+ *  - A step of the scripted bot logs its action, a NaN score and a legal count of 0 (the bot computes neither).  A bot
+ *    whose expert_action raises steps nothing and logs nothing.
+ * The log arrays are caller-owned HOST buffers; the device side lives in the handle, is grown on demand and copied out
+ * batch by batch.  A logged call plays min(max_games, max(1, 256 MiB / (11 * max_turns))) games per batch, so that a long
+ * max_turns cannot ask for tens of GB of device log; at max_turns = 200 this does not bind up to 65 536 games.  The kernel
+ * is one more instantiation of the decision loop at the build's default variant (k_play_log), whatever lanes_per_game the
+ * handle was created with.  MONSOON_ERR_ARG: a NULL log or log->action, and whatever monsoon_rollout_vs_expert refuses. */
+typedef struct {            /* caller-owned HOST buffers, row stride max_turns */
+  uint8_t* action;          /* [n_matches][max_turns]  required; 255 behind the game's last step */
+  double*  score;           /* [n_matches][max_turns]  may be NULL; the decision's best score (monsoon_decide's out_score);
+                                                       a NaN for a bot step and behind the last step */
+  int16_t* n_legal;         /* [n_matches][max_turns]  may be NULL; legal actions of the decision; 0 for a bot step and behind */
+} monsoon_rollout_log;
+int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                           int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
+                           int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log);
+
 /* Per-game decks of configuration C5 on the device: for every seed, numpy.random.RandomState(seed).choice(pool, 12,
  * replace=False) twice -> out_pairs[n][2][12] (card indices taken from pool[pool_n], 12 <= pool_n <= 128).  The caller
  * passes the pre-stream seeds (game seed ^ 0x9E3779B9).  Host buffers in and out; needs no loaded games.

@@ -66,6 +66,10 @@ class DeckSchedule(ctypes.Structure):   # monsoon_deck_schedule
                 ("archetype", ctypes.c_uint8 * 24), ("pool", ctypes.c_uint8 * 256)]
 
 
+class RolloutLog(ctypes.Structure):     # monsoon_rollout_log: caller-owned host buffers (score, n_legal: NULL = not wanted)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("action", "score", "n_legal")]
+
+
 SIGNATURES = {
     "monsoon_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "monsoon_destroy": (None, [ctypes.c_void_p]),
@@ -101,6 +105,9 @@ SIGNATURES = {
     "monsoon_rollout_vs_expert": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+    "monsoon_rollout_logged": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(RolloutLog)]),
     "monsoon_rollout_faults": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_draw_decks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "monsoon_draw_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),

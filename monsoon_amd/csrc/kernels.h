@@ -3,8 +3,8 @@
 // them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); vs_expert.hip, env_opp.hip and env_after.hip hold one further
-// instantiation each; monsoon_hip.hip holds the API kernels and the host side.
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, env_opp.hip and env_after.hip hold one
+// further instantiation each; monsoon_hip.hip holds the API kernels and the host side.
 //
 // Execution model
 //   * Hot kernel k_play<U,W>: ONE WAVEFRONT PER GAME at a time (a persistent grid of resident wavefronts, each popping
@@ -312,6 +312,25 @@ struct EnvPolicy {
   int agent_side, max_steps;
 };
 
+// Where play_game<.., LOG = true> writes down what it commits (k_play_log, play_log.hip): row g of each array, `stride`
+// entries apart, entry k being the game's k-th committed step.  score and n_legal may be null.
+struct PlayLog {
+  uint8_t* action;    // [n][stride]
+  double* score;      // [n][stride] the decision's best score (what b.best reports), NaN for a bot step
+  int16_t* n_legal;   // [n][stride] legal actions of the decision, 0 for a bot step
+  int stride;
+};
+// Entry meta.steps (before its increment) of game g, by lane 0: plain stores, like b.best[g].
+__device__ MSB_INL void log_step(const PlayLog& lg, const int g, const int lane, const int k, const int action, const double score,
+                                 const int n_legal) {
+  if (lane == 0 && k < lg.stride) {   // (k < max_turns = stride by the loop's own end rule)
+    const size_t at = (size_t)g * lg.stride + k;
+    lg.action[at] = (uint8_t)action;
+    if (lg.score) lg.score[at] = score;
+    if (lg.n_legal) lg.n_legal[at] = (int16_t)n_legal;
+  }
+}
+
 // Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
 // to the last; HBM sees one read and one write of it per call.
 // ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
@@ -321,6 +340,7 @@ struct EnvPolicy {
 // reference's scripted bot.  Its round runs no legal mask, clone, features or arg-max: candidate lane 0 runs
 // expert_action() and, unless that raised, step() on column 0 -- the current record's image with the stream window
 // attached -- and column 0 is then "the best successor" that the commit takes over.
+// LOG = true (k_play_log, play_log.hip; with VS = true): every committed step is written down in `lg`.
 //
 // MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
@@ -350,9 +370,9 @@ struct EnvPolicy {
     __syncthreads();                                                                                \
     MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])                                                     \
   }
-template <int U, bool ENV = false, bool VS = false>
+template <int U, bool ENV = false, bool VS = false, bool LOG = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
-                                  const EnvPolicy& pol) {
+                                  const EnvPolicy& pol, const PlayLog& lg = PlayLog{}) {
   typedef PlayLds<U> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -421,6 +441,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         constexpr int feat_ok = 0;   // the bot's successor has no features: the next decision computes its "before" side
         MSB_COMMIT_BEST()
         if (!f) {   // one committed transition, no decision, no look-ahead
+          if constexpr (LOG) log_step(lg, g, lane, meta.steps, a, NAN, 0);
           meta.steps++;
           meta.last_action = (uint8_t)a;
         }
@@ -586,6 +607,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       PROF_MARK(6);   // argmax + new best into registers
     }
     MSB_COMMIT_BEST()
+    if constexpr (LOG) log_step(lg, g, lane, meta.steps, run_a, run_s, n_legal);
     meta.steps++;
     meta.last_action = (uint8_t)run_a;
     meta.lookahead += (uint32_t)n_legal;   // every legal action is stepped exactly once; the commit re-executes nothing
@@ -650,7 +672,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
-// The loop itself, for every persistent kernel (k_play, k_play_vs, k_env_opp): `mine` / `other` are this launch's counter
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_env_opp): `mine` / `other` are this launch's counter
 // set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
 // nothing for it leaves before enter(), which runs once ahead of the first game.
 template <class Enter, class Play>
@@ -707,5 +729,12 @@ constexpr int DEFAULT_U = kVariants[0][0], DEFAULT_W = kVariants[0][1];
 
 // k_play_vs<DEFAULT_U, DEFAULT_W> (vs_expert.hip): the rollout kernel that knows the scripted bot.
 const VariantOps* monsoon_vs_expert_ops();
+
+// k_play_log<DEFAULT_U, DEFAULT_W> (play_log.hip): k_play_vs that writes every committed step into a PlayLog.
+struct LogOps : KernelOps {
+  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+               PlayLog lg);   // never split: the whole batch, the first pair of counter sets
+};
+const LogOps* monsoon_play_log_ops();
 
 }  // namespace msbk

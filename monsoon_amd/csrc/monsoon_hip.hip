@@ -684,6 +684,7 @@ struct monsoon {
   unsigned long long st_acc[ST_N], st_base[ST_N];   // statistics: totals of earlier batches, baseline of the loaded one
   int grid_waves = 0; // persistent grid size of k_decide (resident wavefronts), 0 = not yet queried
   int vs_grid_waves = 0;   // ... of k_play_vs (monsoon_rollout_vs_expert), 0 = not yet queried
+  int log_grid_waves = 0;  // ... of k_play_log (monsoon_rollout_logged), 0 = not yet queried
   bool bot_rows = false;   // the loaded games' p1 / p2 may be MONSOON_PLAYER_EXPERT: only k_play_vs may play them
   int n = 0;          // games loaded by the last reset
   int n_individuals = 0;   // rows of the uploaded weight table
@@ -708,6 +709,9 @@ struct monsoon {
   bool own_stream = false;
   int32_t* d_steps = nullptr;
   size_t matches_cap = 0;
+  // monsoon_rollout_logged: the log of one batch, grown on demand: scores f64 | legal counts i16 | actions u8, [rows][max_turns] each
+  uint8_t* d_log = nullptr;
+  size_t log_cap = 0;   // bytes
   // kernel timing: event pairs are created once and reused
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   std::vector<char> ev_split;   // pair i times a split call: its end event lies on the last sub-batch's stream (drain_timing)
@@ -831,7 +835,7 @@ void monsoon_destroy(monsoon_t* h) {
   if (h->split_fork) hipEventDestroy(h->split_fork);
   void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
                   h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init, h->d_sched};
+                  h->d_counts, h->d_results, h->d_steps, h->d_log, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init, h->d_sched};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (hipEvent_t e : h->draw_ev)
@@ -1685,15 +1689,18 @@ static int resident_waves(monsoon_t* h, hipError_t (*occupancy)(int*, int), int 
 // `rounds` decisions of every loaded game in ONE launch (1 = a decision round; max_turns + 1 = whole games: the extra
 // round turns "still running at the cap" into a result).
 // vs = true: k_play_vs, the kernel that knows the scripted bot (the build's default variant, whatever the handle's is).
+// log (monsoon_rollout_logged): k_play_log, k_play_vs that writes every committed step into *log; never split either.
 // split = true (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below.
-static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false, bool split = false) {
-  if (h->bot_rows && !vs) {   // (a weight row of -1 must never reach k_play)
+static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false, bool split = false,
+                       const PlayLog* log = nullptr) {
+  if (h->bot_rows && !vs && !log) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
   }
-  const VariantOps* v = vs ? monsoon_vs_expert_ops() : h->var;
+  const VariantOps* vp = vs ? monsoon_vs_expert_ops() : h->var;
+  const KernelOps* v = log ? static_cast<const KernelOps*>(monsoon_play_log_ops()) : vp;
   const int lds = v->lds_bytes + g_lds_pad;
-  int& grid_waves = vs ? h->vs_grid_waves : h->grid_waves;
+  int& grid_waves = log ? h->log_grid_waves : vs ? h->vs_grid_waves : h->grid_waves;
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
     const int rc = resident_waves(h, v->occupancy, lds, 4096, &grid_waves);
     if (rc) return rc;
@@ -1721,7 +1728,7 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   // captured (a graph holds one stream's work), and only where every sub-batch is still persistent.  MONSOON_SPLIT = 0 / 1:
   // one launch; read per call, like MONSOON_GRID.
   int parts = 1;
-  if (split && !vs && pers) {
+  if (split && !vs && !log && pers) {
     parts = 2;
     if (const char* e = getenv("MONSOON_SPLIT")) parts = std::min(std::max(atoi(e), 1), (int)SPLIT_MAX);
     if (n / parts <= grid) parts = 1;
@@ -1753,7 +1760,10 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   }
   for (int s = 0; s < parts; s++) {
     const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
-    v->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, max_turns, rounds, write_scores, pers, h->parity[s], g0, s);
+    if (log)   // (parts == 1)
+      monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, max_turns, rounds, pers, h->parity[0], *log);
+    else
+      vp->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, max_turns, rounds, write_scores, pers, h->parity[s], g0, s);
     // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
     // must leave the parity alone, or the next persistent launch would start from the stale counts of the one before.
     if (pers) h->parity[s] ^= 1;
@@ -1833,10 +1843,15 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
   return MONSOON_OK;
 }
 
-// monsoon_rollout (min_row = 0) and monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot)
+// A logged call's batch is cut so that its device log stays within LOG_BUDGET whatever max_turns is: 11 bytes per entry
+// (action + score + legal count), max_turns entries per game.
+constexpr size_t LOG_BUDGET = (size_t)256 << 20;
+
+// monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and
+// monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                         int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
-                        int8_t* out_results, int32_t* out_steps) {
+                        int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
@@ -1878,6 +1893,23 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
   h->rollout_matches = 0;
   uint8_t* d_faults = (uint8_t*)h->d_results + h->matches_cap;
   int cap = h->cfg.max_games;
+  PlayLog dlog = {nullptr, nullptr, nullptr, max_turns};
+  if (log) {
+    cap = (int)std::min((size_t)cap, std::max((size_t)1, LOG_BUDGET / ((size_t)11 * max_turns)));
+    const size_t log_rows = (size_t)std::min(cap, n_matches) * max_turns;   // entries of one device array
+    const size_t need = log_rows * ((log->score ? 8 : 0) + (log->n_legal ? 2 : 0) + 1);
+    if (need > h->log_cap) {
+      if (h->d_log) HIP_TRY(h, hipFree(h->d_log));
+      h->d_log = nullptr;
+      h->log_cap = 0;
+      HIP_TRY(h, hipMalloc(&h->d_log, need));
+      h->log_cap = need;
+    }
+    uint8_t* at = h->d_log;
+    if (log->score) dlog.score = (double*)at, at += log_rows * 8;
+    if (log->n_legal) dlog.n_legal = (int16_t*)at, at += log_rows * 2;
+    dlog.action = at;
+  }
   std::vector<uint32_t> seeds;
   std::vector<uint8_t> decks;
   std::vector<int32_t> p1, p2;
@@ -1899,11 +1931,23 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
     if (rc) return rc;
     // one launch plays the whole batch to the end; a batch without a bot is k_play's, counted by k_collect, as ever
     const bool vs = h->bot_rows;
-    rc = launch_play(h, n, max_turns, max_turns + 1, 0, true, vs);
+    if (log) {   // the padding behind a game's last step: action 255, score NaN (all ones), legal count 0
+      const size_t cnt = (size_t)n * max_turns;
+      HIP_TRY(h, hipMemsetAsync(dlog.action, 0xFF, cnt, h->stream));
+      if (dlog.score) HIP_TRY(h, hipMemsetAsync(dlog.score, 0xFF, cnt * 8, h->stream));
+      if (dlog.n_legal) HIP_TRY(h, hipMemsetAsync(dlog.n_legal, 0, cnt * 2, h->stream));
+    }
+    rc = launch_play(h, n, max_turns, max_turns + 1, 0, true, vs, false, log ? &dlog : nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
                        h->d_steps, d_faults);
     HIP_TRY(h, hipGetLastError());
+    if (log) {
+      const size_t cnt = (size_t)n * max_turns, row = (size_t)base * max_turns;
+      HIP_TRY(h, hipMemcpyAsync(log->action + row, dlog.action, cnt, hipMemcpyDeviceToHost, h->stream));
+      if (dlog.score) HIP_TRY(h, hipMemcpyAsync(log->score + row, dlog.score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+      if (dlog.n_legal) HIP_TRY(h, hipMemcpyAsync(log->n_legal + row, dlog.n_legal, cnt * 2, hipMemcpyDeviceToHost, h->stream));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     rc = drain_timing(h);
     if (rc) return rc;
@@ -1929,6 +1973,18 @@ int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_ind
                               int32_t* out_steps) {
   return rollout_impl(h, "monsoon_rollout_vs_expert", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
                       max_turns, out_counts, out_results, out_steps);
+}
+
+int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                           const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                           int32_t* out_steps, const monsoon_rollout_log* log) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!log || !log->action) {
+    h->err = "monsoon_rollout_logged: log and log->action are required";
+    return MONSOON_ERR_ARG;
+  }
+  return rollout_impl(h, "monsoon_rollout_logged", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
+                      max_turns, out_counts, out_results, out_steps, log);
 }
 
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches) {

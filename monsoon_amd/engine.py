@@ -6,9 +6,36 @@ import numpy as np
 from . import _lib
 from ._lib import Config, Match, MonsoonError, Stats
 
+MATCH_DTYPE = np.dtype([("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", "<u4")])   # monsoon_match
+LOG_BUDGET = 256 << 20   # bytes of device log a batch of monsoon_rollout_logged may take (include/monsoon.h)
+
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+class RolloutLog:
+    """What a logged rollout played (monsoon_rollout_logged): entry k of row i is game i's k-th committed step.
+    action uint8[n][max_turns] (255 behind the last step), score float64[n][max_turns] or None (the decision's best score;
+    NaN for a step of the scripted bot and behind the last step), n_legal int16[n][max_turns] or None (legal actions of
+    the decision; 0 for a bot step and behind), steps int32[n] = the entries of each row."""
+
+    def __init__(self, action, score, n_legal, steps):
+        self.action, self.score, self.n_legal, self.steps = action, score, n_legal, steps
+
+    @classmethod
+    def empty(cls, n, max_turns, scores=True, n_legal=True):
+        """n rows of padding."""
+        return cls(np.full((n, max_turns), 255, dtype=np.uint8), np.full((n, max_turns), np.nan) if scores else None,
+                   np.zeros((n, max_turns), dtype=np.int16) if n_legal else None, np.zeros(n, dtype=np.int32))
+
+    def put(self, rows, other):
+        """Rows `rows` become the rows of `other` (a log of len(rows) games with the same arrays)."""
+        self.action[rows], self.steps[rows] = other.action, other.steps
+        if self.score is not None:
+            self.score[rows] = other.score
+        if self.n_legal is not None:
+            self.n_legal[rows] = other.n_legal
 
 
 class BatchEngine:
@@ -287,16 +314,37 @@ class BatchEngine:
         won), else p2 (a win = SECOND won); results stay FIRST / SECOND, steps count both sides' committed steps."""
         return self._rollout("monsoon_rollout_vs_expert", weights, matches, deck_pairs, max_turns, want_results)
 
-    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results):
+    def rollout_logged(self, weights, matches, deck_pairs, max_turns, scores=True, n_legal=True):
+        """monsoon_rollout_logged: rollout_vs_expert (the bot's rows included) that also writes down every committed step.
+        Returns (counts, results, steps, log), log a RolloutLog whose score / n_legal are None where not asked for."""
+        weights, m, deck_pairs = self._rollout_args(weights, matches, deck_pairs)
+        counts = np.zeros((len(weights), 3), dtype=np.int32)
+        results = np.zeros(len(m), dtype=np.int8)
+        log = RolloutLog.empty(len(m), max_turns, scores, n_legal)
+        c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
+        self._ck(self.lib.monsoon_rollout_logged(self.h, _ptr(weights), len(weights), _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
+                                                 max_turns, _ptr(counts), _ptr(results), _ptr(log.steps), ctypes.byref(c_log)),
+                 "monsoon_rollout_logged")
+        # the handle now holds the last batch of the schedule; a logged call's batches are cut by the log's budget too
+        batch = min(self.max_games, max(1, LOG_BUDGET // (11 * max_turns)))
+        self.n = len(m) - ((len(m) - 1) // batch) * batch
+        return counts, results, log.steps, log
+
+    @staticmethod
+    def _rollout_args(weights, matches, deck_pairs):
         weights = np.ascontiguousarray(weights, dtype=np.float64)
-        n_ind = weights.shape[0]
         deck_pairs = np.ascontiguousarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12)
         m = np.ascontiguousarray(matches)
-        if m.dtype != np.dtype([("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", "<u4")]):
-            arr = np.zeros(len(matches), dtype=[("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", "<u4")])
+        if m.dtype != MATCH_DTYPE:
+            arr = np.zeros(len(matches), dtype=MATCH_DTYPE)
             mm = np.asarray(matches)
             arr["p1"], arr["p2"], arr["seed"], arr["deck"] = mm[:, 0], mm[:, 1], mm[:, 2], mm[:, 3]
             m = arr
+        return weights, m, deck_pairs
+
+    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results):
+        weights, m, deck_pairs = self._rollout_args(weights, matches, deck_pairs)
+        n_ind = weights.shape[0]
         counts = np.zeros((n_ind, 3), dtype=np.int32)
         results = np.zeros(len(m), dtype=np.int8) if want_results else None
         steps = np.zeros(len(m), dtype=np.int32) if want_results else None

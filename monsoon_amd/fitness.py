@@ -287,6 +287,18 @@ class FitnessEvaluator:
         self.last_rollout = (results, steps, faults)
         return counts
 
+    def logged_games(self, weights, matches, deck_pairs=None):
+        """The games of a schedule with their logs, on this evaluator's engines (game_log.logged_rollout): what a
+        champion played, step by step.  deck_pairs None: config.deck on both sides.  Returns (counts, results, steps,
+        faults, log); the evaluator's statistics are left alone."""
+        from .game_log import logged_rollout
+        matches = np.asarray(matches)
+        if deck_pairs is None:
+            from .cards import deck_indices
+            deck = deck_indices(self.config.deck)
+            deck_pairs = np.stack([deck, deck])[None]
+        return logged_rollout(self._engine, np.asarray(weights, dtype=np.float64), matches, deck_pairs, self.config.max_turns)
+
     def _decks_for(self, matches, generation, tag=1):
         """Deck pairs [n_decks][2][12] for a schedule; fills matches["deck"].  Without a deck_config: config.deck both
         sides.  With one: utils.py:155-219 per GAME, as games/evolutionary_stormbound.py:52 draws them (one pair for
