@@ -20,6 +20,8 @@
 #include "deck_schedule.h"
 #include "env_after.h"
 #include "env_snap.h"
+#include "host_layout.h"
+#include "host_mem.h"
 #include "kernels.h"
 
 using namespace msb;
@@ -666,10 +668,22 @@ __global__ void k_ga_select(const double* fitness, int n, int* out_order) {
 // ================================================================================================
 // Host side
 // ================================================================================================
+// What launch_play launches: k_play of the handle's variant, k_play_vs (the kernel that knows the scripted bot, the
+// build's default variant) or k_play_log (k_play_vs that writes every committed step into a log).
+enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_KINDS = 3 };
+
+// Device memory: everything the handle allocates is recorded in `mem` when it is allocated and freed from that record by
+// monsoon_destroy; the pointers below and in `b`, `env` and `env_sched` only refer to it.  Events and the split streams
+// are created on first use through `events` / `streams` and destroyed once, likewise.  How the workspaces (d_env, d_opp,
+// d_bytes, d_results, d_log) are cut into fields is host_layout.h's business.
 struct monsoon {
+  __attribute__((visibility("hidden"))) ~monsoon() = default;   // (`mem` gives the handle a destructor: not an exported symbol)
   monsoon_config cfg;
   int device = 0;
   hipStream_t stream = nullptr;
+  DevOwner mem;
+  LazyObjects<hipEvent_t> events;
+  LazyObjects<hipStream_t> streams;
   DevBuffers b;
   const VariantOps* var = nullptr;   // hot-kernel variant: candidate lanes per game, waves per SIMD
   int parity[SPLIT_MAX] = {};   // which of its two sets of b.pop the next persistent launch of sub-batch s uses (s = 0: every unsplit launch)
@@ -679,19 +693,16 @@ struct monsoon {
   hipEvent_t split_fork = nullptr;         // recorded on `stream` before the first split call after other work
   int split_live = 0;   // sub-batches of split calls that `stream` has not waited for yet (bind_device joins them), 0 = none
   int split_grid = 0;   // ... and their grid
-  size_t ovf_lanes = 0;   // stepping lanes b.wk_ovf has room for (OVF_WORDS words each)
-  std::vector<uint32_t*> ovf_retired;   // earlier, smaller b.wk_ovf blocks: a captured launch may still point to one (grow_ovf)
+  size_t ovf_lanes = 0;   // stepping lanes b.wk_ovf has room for (OVF_WORDS words each); earlier, smaller blocks stay in `mem` (grow_ovf)
   unsigned long long st_acc[ST_N], st_base[ST_N];   // statistics: totals of earlier batches, baseline of the loaded one
-  int grid_waves = 0; // persistent grid size of k_decide (resident wavefronts), 0 = not yet queried
-  int vs_grid_waves = 0;   // ... of k_play_vs (monsoon_rollout_vs_expert), 0 = not yet queried
-  int log_grid_waves = 0;  // ... of k_play_log (monsoon_rollout_logged), 0 = not yet queried
+  int grid_waves[PLAY_KINDS] = {};   // persistent grid size of each kind's kernel (resident wavefronts), 0 = not yet queried
   bool bot_rows = false;   // the loaded games' p1 / p2 may be MONSOON_PLAYER_EXPERT: only k_play_vs may play them
   int n = 0;          // games loaded by the last reset
   int n_individuals = 0;   // rows of the uploaded weight table
   int weights_cap = 0;     // rows allocated
   std::string err;
   // scratch device buffers for API calls
-  uint8_t* d_bytes = nullptr;   // max(cap * 8, 16 KiB)
+  uint8_t* d_bytes = nullptr;   // layout::bytes_total(cap), cut by the call that uses it
   uint8_t* d_decks = nullptr;   // [cap][24]
   uint8_t* d_factions = nullptr;
   uint32_t* d_seeds = nullptr;
@@ -704,12 +715,13 @@ struct monsoon {
   // rollout result buffers, grown on demand and kept for the life of the handle
   int32_t* d_counts = nullptr;
   size_t counts_cap = 0;
-  int8_t* d_results = nullptr;    // [matches_cap] results, then [matches_cap] fault codes (monsoon_rollout_faults)
+  int8_t* d_results = nullptr;    // layout::results(results_cap)
+  size_t results_cap = 0;
   size_t rollout_matches = 0;     // matches of the last monsoon_rollout
   bool own_stream = false;
   int32_t* d_steps = nullptr;
-  size_t matches_cap = 0;
-  // monsoon_rollout_logged: the log of one batch, grown on demand: scores f64 | legal counts i16 | actions u8, [rows][max_turns] each
+  size_t steps_cap = 0;
+  // monsoon_rollout_logged: the log of one batch (layout::rollout_log), grown on demand
   uint8_t* d_log = nullptr;
   size_t log_cap = 0;   // bytes
   // kernel timing: event pairs are created once and reused
@@ -719,14 +731,14 @@ struct monsoon {
   double kernel_ms = 0;
   long long kernel_launches = 0;
   // vector env (monsoon_env_reset): workspace of max_games slots, allocated once; env_on until monsoon_reset / rollout
-  uint8_t* d_env = nullptr;   // seed0 u32 | episode i32 | agent steps u32 | bot steps u32 | decks [24] | factions [2] | mark | pool [128] | loaded flags [cap]
+  uint8_t* d_env = nullptr;   // layout::env(cap)
   EnvDev env;
   int env_n = 0;
   bool env_on = false;
   EnvSched env_sched = {};   // sched non-null: the loaded env is in schedule mode (k_env_reseed_schedule)
   // the env's heuristic opponent (monsoon_env_set_opponents): d_opp is sized by max_games and allocated once; the weight
   // table is never moved while an opponent-2 env is loaded (a captured step points to it)
-  uint8_t* d_opp = nullptr;   // rows i32 [cap] | slot lists i32 [2][cap] | look-ahead transitions u32 [cap] | list counts i32 [2 * ENV_COUNT_STRIDE] | pop counters i32 [2][POP_PARTS * POP_STRIDE]
+  uint8_t* d_opp = nullptr;   // layout::opp(cap, ...)
   double* d_opp_w = nullptr;  // [opp_w_cap][10]
   int opp_w_cap = 0;          // rows allocated
   int opp_n = 0;              // slots the last monsoon_env_set_opponents gave rows for (0 = never called)
@@ -734,7 +746,7 @@ struct monsoon {
   int after_grid = 0;         // k_env_after's grid (monsoon_env_afterstates_dev), likewise
   int after_waves = 0;        // resident wavefronts of k_env_after (queried once per handle)
   int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
-  uint8_t* d_snap_flag = nullptr;   // [cap], inside d_env: the loaded flags of monsoon_env_load_dev when the caller keeps none
+  uint8_t* d_snap_flag = nullptr;   // inside d_env: the loaded flags of monsoon_env_load_dev when the caller keeps none
   int cu_count = 0;           // compute units of the device (queried once per handle)
   // monsoon_draw_schedule and the env's schedule mode: init_genrand(19650218), uploaded by the first call that needs it
   // (ensure_mt_init); the draw kernel's time in the last monsoon_draw_schedule call
@@ -751,16 +763,45 @@ struct monsoon {
   double draw_ms = 0;
 };
 
+// The workspace layouts of this build and handle (host_layout.h).
+static_assert(BLOB_BYTES == layout::blob_bytes(sizeof(GameMeta), STATE_BYTES, MT_N), "k_blob and host_layout.h agree");
+static_assert(BLOB_BYTES <= layout::BYTES_MIN && layout::DEBUG_STREAM_MAX * 4 + (2 + 2 * DBG_TRACE_CAP) * 4 <= layout::BYTES_MIN &&
+                  layout::state_export().total <= layout::BYTES_MIN, "d_bytes holds every fixed-size use of it at any cap");
+static layout::Opp opp_layout(const monsoon* h) { return layout::opp((size_t)h->cfg.max_games, ENV_COUNT_STRIDE, POP_PARTS, POP_STRIDE); }
+
 static std::string g_create_error;
 
+// The one error path of the host side: whatever a call holds in a DevOwner of its own is freed as it returns.
 #define HIP_TRY(h, call)                                                                  \
   do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
+    hipError_t e_ = (hipError_t)(call);                                                   \
     if (e_ != hipSuccess) {                                                               \
       (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
       return MONSOON_ERR_DEVICE;                                                          \
     }                                                                                     \
   } while (0)
+
+// The refusals every entry point shares: "<who>: <text>" with MONSOON_ERR_ARG, and the one of the calls that need a
+// loaded env.
+static int bad_arg(monsoon_t* h, const char* who, const std::string& text) {
+  if (h) h->err = std::string(who) + ": " + text;
+  return MONSOON_ERR_ARG;
+}
+static int require_env(monsoon_t* h, const char* who) {
+  if (h->env_on) return MONSOON_OK;
+  h->err = std::string(who) + ": no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
+  return MONSOON_ERR_STATE;
+}
+
+// The launch of a lane-per-game API kernel for n games on the handle's stream: API_LANES games per 64-thread workgroup,
+// their records in dynamic LDS.  A macro, like hipLaunchKernelGGL itself: the kernel is named at the launch.
+#define LAUNCH_LANES(h, kernel, n, ...) \
+  hipLaunchKernelGGL(kernel, dim3(((n) + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, (h)->stream, __VA_ARGS__)
+
+// An event of the handle, created on first use and destroyed with the handle.
+static hipError_t lazy_event(monsoon_t* h, hipEvent_t& e, unsigned flags = hipEventDefault) {
+  return (hipError_t)h->events.get(e, [flags](hipEvent_t* p) { return flags ? hipEventCreateWithFlags(p, flags) : hipEventCreate(p); });
+}
 
 static const char* kCardIds[NUM_CARDS] = {
 #define X(id) #id,
@@ -825,28 +866,12 @@ void monsoon_destroy(monsoon_t* h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  for (int s = 1; s < SPLIT_MAX; s++) {   // (a split call may still be in flight on these: not joined, the handle goes away)
-    if (h->split_stream[s]) {
-      hipStreamSynchronize(h->split_stream[s]);
-      hipStreamDestroy(h->split_stream[s]);
-    }
-    if (h->split_done[s]) hipEventDestroy(h->split_done[s]);
-  }
-  if (h->split_fork) hipEventDestroy(h->split_fork);
-  void* ptrs[] = {h->b.state, h->b.rng_out, h->b.rng_mt, h->b.meta, h->b.weights, h->b.stats, h->b.scores, h->b.best, h->b.prof, h->b.pop, h->b.wk_ovf,
-                  h->d_bytes, h->d_decks, h->d_factions, h->d_seeds, h->d_masks, h->d_i32, h->d_f64, h->d_p1, h->d_p2, h->d_int,
-                  h->d_counts, h->d_results, h->d_steps, h->d_log, h->d_env, h->d_opp, h->d_opp_w, h->d_mt_init, h->d_sched};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  for (hipEvent_t e : h->draw_ev)
-    if (e) hipEventDestroy(e);
-  for (hipEvent_t e : h->reseed_ev)
-    if (e) hipEventDestroy(e);
-  for (uint32_t* p : h->ovf_retired) hipFree(p);
-  for (auto& pr : h->ev_pool) {
-    hipEventDestroy(pr.first);
-    hipEventDestroy(pr.second);
-  }
+  h->streams.destroy_all([](hipStream_t s) {   // (a split call may still be in flight on these: not joined, the handle goes away)
+    hipStreamSynchronize(s);
+    hipStreamDestroy(s);
+  });
+  h->events.destroy_all([](hipEvent_t e) { hipEventDestroy(e); });
+  h->mem.free_all();
   if (h->stream && h->own_stream) hipStreamDestroy(h->stream);
   delete h;
 }
@@ -869,32 +894,32 @@ static int create_impl(monsoon* h) {
     h->stream = nullptr;
     h->own_stream = false;
   }
-  HIP_TRY(h, hipMalloc(&h->b.state, cap * SW * 4));
-  HIP_TRY(h, hipMalloc(&h->b.rng_out, cap * RNG_WORDS * 4));
-  HIP_TRY(h, hipMalloc(&h->b.rng_mt, cap * MT_N * 4));
-  HIP_TRY(h, hipMalloc(&h->b.meta, cap * sizeof(GameMeta)));
+  HIP_TRY(h, h->mem.alloc(&h->b.state, cap * SW * 4));
+  HIP_TRY(h, h->mem.alloc(&h->b.rng_out, cap * RNG_WORDS * 4));
+  HIP_TRY(h, h->mem.alloc(&h->b.rng_mt, cap * MT_N * 4));
+  HIP_TRY(h, h->mem.alloc(&h->b.meta, cap * sizeof(GameMeta)));
   HIP_TRY(h, hipMemset(h->b.meta, 0, cap * sizeof(GameMeta)));
-  HIP_TRY(h, hipMalloc(&h->b.stats, ST_WORDS * sizeof(unsigned long long)));
+  HIP_TRY(h, h->mem.alloc(&h->b.stats, ST_WORDS * sizeof(unsigned long long)));
   HIP_TRY(h, hipMemset(h->b.stats, 0, ST_WORDS * sizeof(unsigned long long)));
-  HIP_TRY(h, hipMalloc(&h->b.best, cap * sizeof(double)));
+  HIP_TRY(h, h->mem.alloc(&h->b.best, cap * sizeof(double)));
   // overflow blocks of the work stack (kernels.h): the lane-per-game API kernels step up to `cap` games at once (rounded
   // up to whole workgroups); launch_play grows the buffer once it knows its grid
   h->ovf_lanes = ((cap + API_LANES - 1) / API_LANES) * (size_t)API_LANES;
-  HIP_TRY(h, hipMalloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
-  HIP_TRY(h, hipMalloc(&h->b.pop, SPLIT_MAX * 2 * POP_PARTS * POP_STRIDE * sizeof(int)));
+  HIP_TRY(h, h->mem.alloc(&h->b.wk_ovf, h->ovf_lanes * OVF_WORDS * 4));
+  HIP_TRY(h, h->mem.alloc(&h->b.pop, SPLIT_MAX * 2 * POP_PARTS * POP_STRIDE * sizeof(int)));
   HIP_TRY(h, hipMemset(h->b.pop, 0, SPLIT_MAX * 2 * POP_PARTS * POP_STRIDE * sizeof(int)));
 #if defined(MSB_PROF) && MSB_PROF
-  HIP_TRY(h, hipMalloc(&h->b.prof, cap * PROF_WORDS * sizeof(unsigned long long)));
+  HIP_TRY(h, h->mem.alloc(&h->b.prof, cap * PROF_WORDS * sizeof(unsigned long long)));
   HIP_TRY(h, hipMemset(h->b.prof, 0, cap * PROF_WORDS * sizeof(unsigned long long)));
 #endif
-  HIP_TRY(h, hipMalloc(&h->d_decks, cap * 24));
-  HIP_TRY(h, hipMalloc(&h->d_factions, cap * 2));
-  HIP_TRY(h, hipMalloc(&h->d_seeds, cap * 4));
-  HIP_TRY(h, hipMalloc(&h->d_masks, cap * 24));
-  HIP_TRY(h, hipMalloc(&h->d_bytes, cap * 8 > 16384 ? cap * 8 : 16384));
-  HIP_TRY(h, hipMalloc(&h->d_p1, cap * 4));
-  HIP_TRY(h, hipMalloc(&h->d_p2, cap * 4));
-  HIP_TRY(h, hipMalloc(&h->d_int, 64));
+  HIP_TRY(h, h->mem.alloc(&h->d_decks, cap * 24));
+  HIP_TRY(h, h->mem.alloc(&h->d_factions, cap * 2));
+  HIP_TRY(h, h->mem.alloc(&h->d_seeds, cap * 4));
+  HIP_TRY(h, h->mem.alloc(&h->d_masks, cap * 24));
+  HIP_TRY(h, h->mem.alloc(&h->d_bytes, layout::bytes_total(cap)));
+  HIP_TRY(h, h->mem.alloc(&h->d_p1, cap * 4));
+  HIP_TRY(h, h->mem.alloc(&h->d_p2, cap * 4));
+  HIP_TRY(h, h->mem.alloc(&h->d_int, 64));
   return MONSOON_OK;
 }
 
@@ -990,7 +1015,7 @@ static int check_ready(monsoon_t* h, bool join = true) {
 
 static int launch_reset(monsoon_t* h, int n) {
   hipLaunchKernelGGL(k_seed, dim3(n), dim3(64), 0, h->stream, h->b, 0, n, h->d_seeds);
-  hipLaunchKernelGGL(k_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, h->d_decks, h->d_factions, h->d_seeds);
+  LAUNCH_LANES(h, k_init, n, h->b, n, h->d_decks, h->d_factions, h->d_seeds);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
 }
@@ -999,19 +1024,14 @@ static int fold_stats(monsoon_t* h);
 
 static int check_decks(monsoon_t* h, const uint8_t* decks, size_t n_cards, const char* who) {
   for (size_t i = 0; i < n_cards; i++) {
-    if (decks[i] >= NUM_CARDS || card_unsupported(decks[i])) {
-      h->err = std::string(who) + ": card not supported by this build: " + (decks[i] < NUM_CARDS ? kCardIds[decks[i]] : "index out of range");
-      return MONSOON_ERR_ARG;
-    }
+    if (decks[i] >= NUM_CARDS || card_unsupported(decks[i]))
+      return bad_arg(h, who, std::string("card not supported by this build: ") + (decks[i] < NUM_CARDS ? kCardIds[decks[i]] : "index out of range"));
   }
   return MONSOON_OK;
 }
 
 int monsoon_reset(monsoon_t* h, int32_t n, const uint32_t* seeds, const uint8_t* decks, const uint8_t* factions) {
-  if (!h || !seeds || !decks || n <= 0 || n > h->cfg.max_games) {
-    if (h) h->err = "monsoon_reset: bad argument";
-    return MONSOON_ERR_ARG;
-  }
+  if (!h || !seeds || !decks || n <= 0 || n > h->cfg.max_games) return bad_arg(h, "monsoon_reset", "bad argument");
   h->env_on = false;   // the env's slots are about to be replaced
   int rc = check_decks(h, decks, (size_t)n * 24, "monsoon_reset");
   if (rc) return rc;
@@ -1033,53 +1053,33 @@ int monsoon_reset(monsoon_t* h, int32_t n, const uint32_t* seeds, const uint8_t*
 }
 
 int monsoon_draw_decks(monsoon_t* h, const uint32_t* seeds, int32_t n, const uint8_t* pool, int32_t pool_n, uint8_t* out_pairs) {
-  if (!h || !seeds || !pool || !out_pairs || n <= 0 || pool_n < 12 || pool_n > 128) {
-    if (h) h->err = "monsoon_draw_decks: bad argument (12 <= pool_n <= 128)";
-    return MONSOON_ERR_ARG;
-  }
+  const char* who = "monsoon_draw_decks";
+  if (!h || !seeds || !pool || !out_pairs || n <= 0 || pool_n < 12 || pool_n > 128) return bad_arg(h, who, "bad argument (12 <= pool_n <= 128)");
   for (int i = 0; i < pool_n; i++)
-    if (pool[i] >= NUM_CARDS) {
-      h->err = "monsoon_draw_decks: pool entry " + std::to_string(i) + " is not a card index";
-      return MONSOON_ERR_ARG;
-    }
+    if (pool[i] >= NUM_CARDS) return bad_arg(h, who, "pool entry " + std::to_string(i) + " is not a card index");
   HIP_TRY(h, bind_device(h));
+  DevOwner tmp;   // freed on return
   uint32_t* d_seeds = nullptr;
   uint8_t *d_pool = nullptr, *d_out = nullptr;
   int* d_over = nullptr;
-  auto done = [&](int rc) {
-    hipFree(d_seeds);
-    hipFree(d_pool);
-    hipFree(d_out);
-    hipFree(d_over);
-    return rc;
-  };
-#define DD_TRY(call)                                                  \
-  do {                                                                \
-    hipError_t e_ = (call);                                           \
-    if (e_ != hipSuccess) {                                           \
-      h->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
-      return done(MONSOON_ERR_DEVICE);                                \
-    }                                                                 \
-  } while (0)
-  DD_TRY(hipMalloc(&d_seeds, (size_t)n * 4));
-  DD_TRY(hipMalloc(&d_pool, 128));
-  DD_TRY(hipMalloc(&d_out, (size_t)n * 24));
-  DD_TRY(hipMalloc(&d_over, 4));
-  DD_TRY(hipMemcpyAsync(d_seeds, seeds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-  DD_TRY(hipMemcpyAsync(d_pool, pool, (size_t)pool_n, hipMemcpyHostToDevice, h->stream));
-  DD_TRY(hipMemsetAsync(d_over, 0, 4, h->stream));
+  HIP_TRY(h, tmp.alloc(&d_seeds, (size_t)n * 4));
+  HIP_TRY(h, tmp.alloc(&d_pool, 128));
+  HIP_TRY(h, tmp.alloc(&d_out, (size_t)n * 24));
+  HIP_TRY(h, tmp.alloc(&d_over, 4));
+  HIP_TRY(h, hipMemcpyAsync(d_seeds, seeds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d_pool, pool, (size_t)pool_n, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(d_over, 0, 4, h->stream));
   hipLaunchKernelGGL(k_draw_decks, dim3(n), dim3(64), 0, h->stream, n, d_seeds, d_pool, pool_n, d_out, d_over);
-  DD_TRY(hipGetLastError());
+  HIP_TRY(h, hipGetLastError());
   int over = 0;
-  DD_TRY(hipMemcpyAsync(out_pairs, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
-  DD_TRY(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, h->stream));
-  DD_TRY(hipStreamSynchronize(h->stream));
-#undef DD_TRY
+  HIP_TRY(h, hipMemcpyAsync(out_pairs, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (over) {
     h->err = "monsoon_draw_decks: " + std::to_string(over) + " seed(s) needed more than 1248 outputs of their stream";
-    return done(MONSOON_ERR_STATE);
+    return MONSOON_ERR_STATE;
   }
-  return done(MONSOON_OK);
+  return MONSOON_OK;
 }
 
 // init_genrand(19650218) on the device, once per handle: where the key mixing of every schedule stream starts
@@ -1089,83 +1089,58 @@ static int ensure_mt_init(monsoon_t* h) {
   std::vector<uint32_t> mt(MT_N);   // (mt19937.h: mt_seed)
   mt[0] = DS_INIT_SEED;
   for (int i = 1; i < MT_N; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+  DevOwner tmp;   // the handle's only once the table is in it
   uint32_t* d = nullptr;
-  HIP_TRY(h, hipMalloc(&d, MT_N * 4));
-  hipError_t e = hipMemcpy(d, mt.data(), MT_N * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(d);
-    h->err = std::string("hipMemcpy: ") + hipGetErrorString(e);
-    return MONSOON_ERR_DEVICE;
-  }
+  HIP_TRY(h, tmp.alloc(&d, MT_N * 4));
+  HIP_TRY(h, hipMemcpy(d, mt.data(), MT_N * 4, hipMemcpyHostToDevice));
+  h->mem.adopt(tmp);
   h->d_mt_init = d;
   return MONSOON_OK;
 }
 
 int monsoon_draw_schedule(monsoon_t* h, const monsoon_deck_schedule* sc, const uint32_t* game_seeds, int32_t n, uint8_t* out_pairs) {
+  const char* who = "monsoon_draw_schedule";
   if (!h || !sc || !game_seeds || !out_pairs || n <= 0 || sc->tag == 0 || (sc->phase != DS_EXPLORE && sc->phase != DS_BALANCE) ||
-      sc->n_preserve < 0 || sc->n_preserve > 12) {
-    if (h) h->err = "monsoon_draw_schedule: bad argument (n > 0, tag != 0, phase 1 or 2, 0 <= n_preserve <= 12)";
-    return MONSOON_ERR_ARG;
-  }
+      sc->n_preserve < 0 || sc->n_preserve > 12)
+    return bad_arg(h, who, "bad argument (n > 0, tag != 0, phase 1 or 2, 0 <= n_preserve <= 12)");
   for (int side = 0; side < 2; side++) {
-    if (sc->pool_n[side] < 12 || sc->pool_n[side] > DS_POOL_MAX) {
-      h->err = "monsoon_draw_schedule: bad argument (12 <= pool_n <= 128)";
-      return MONSOON_ERR_ARG;
-    }
+    if (sc->pool_n[side] < 12 || sc->pool_n[side] > DS_POOL_MAX) return bad_arg(h, who, "bad argument (12 <= pool_n <= 128)");
     for (int i = 0; i < 12 + sc->pool_n[side]; i++)
-      if ((i < 12 ? sc->archetype[side][i] : sc->pool[side][i - 12]) >= NUM_CARDS) {
-        h->err = std::string("monsoon_draw_schedule: ") + (i < 12 ? "archetype" : "pool") + " entry " + std::to_string(i < 12 ? i : i - 12) + " of side " +
-                 std::to_string(side) + " is not a card index";
-        return MONSOON_ERR_ARG;
-      }
+      if ((i < 12 ? sc->archetype[side][i] : sc->pool[side][i - 12]) >= NUM_CARDS)
+        return bad_arg(h, who, std::string(i < 12 ? "archetype" : "pool") + " entry " + std::to_string(i < 12 ? i : i - 12) + " of side " +
+                                   std::to_string(side) + " is not a card index");
   }
   HIP_TRY(h, bind_device(h));
   int rc_mt = ensure_mt_init(h);
   if (rc_mt) return rc_mt;
-  for (hipEvent_t& e : h->draw_ev)
-    if (!e) HIP_TRY(h, hipEventCreate(&e));
+  for (hipEvent_t& e : h->draw_ev) HIP_TRY(h, lazy_event(h, e));
+  DevOwner tmp;   // freed on return
   uint32_t *d_seeds = nullptr, *d_out = nullptr;
   monsoon_deck_schedule* d_sc = nullptr;
   int* d_over = nullptr;
-  auto done = [&](int rc) {
-    hipFree(d_seeds);
-    hipFree(d_sc);
-    hipFree(d_out);
-    hipFree(d_over);
-    return rc;
-  };
-#define DS_TRY(call)                                                  \
-  do {                                                                \
-    hipError_t e_ = (call);                                           \
-    if (e_ != hipSuccess) {                                           \
-      h->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
-      return done(MONSOON_ERR_DEVICE);                                \
-    }                                                                 \
-  } while (0)
-  DS_TRY(hipMalloc(&d_seeds, (size_t)n * 4));
-  DS_TRY(hipMalloc(&d_sc, sizeof(monsoon_deck_schedule)));
-  DS_TRY(hipMalloc(&d_out, (size_t)n * 24));
-  DS_TRY(hipMalloc(&d_over, 4));
-  DS_TRY(hipMemcpyAsync(d_seeds, game_seeds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-  DS_TRY(hipMemcpyAsync(d_sc, sc, sizeof(monsoon_deck_schedule), hipMemcpyHostToDevice, h->stream));
-  DS_TRY(hipMemsetAsync(d_over, 0, 4, h->stream));
-  DS_TRY(hipEventRecord(h->draw_ev[0], h->stream));
+  HIP_TRY(h, tmp.alloc(&d_seeds, (size_t)n * 4));
+  HIP_TRY(h, tmp.alloc(&d_sc, sizeof(monsoon_deck_schedule)));
+  HIP_TRY(h, tmp.alloc(&d_out, (size_t)n * 24));
+  HIP_TRY(h, tmp.alloc(&d_over, 4));
+  HIP_TRY(h, hipMemcpyAsync(d_seeds, game_seeds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d_sc, sc, sizeof(monsoon_deck_schedule), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemsetAsync(d_over, 0, 4, h->stream));
+  HIP_TRY(h, hipEventRecord(h->draw_ev[0], h->stream));
   hipLaunchKernelGGL(k_draw_schedule, dim3(n), dim3(64), 0, h->stream, n, d_sc, h->d_mt_init, d_seeds, d_out, d_over);
-  DS_TRY(hipGetLastError());
-  DS_TRY(hipEventRecord(h->draw_ev[1], h->stream));
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(h->draw_ev[1], h->stream));
   int over = 0;
   float ms = 0;
-  DS_TRY(hipMemcpyAsync(out_pairs, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
-  DS_TRY(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, h->stream));
-  DS_TRY(hipStreamSynchronize(h->stream));
-  DS_TRY(hipEventElapsedTime(&ms, h->draw_ev[0], h->draw_ev[1]));
-#undef DS_TRY
+  HIP_TRY(h, hipMemcpyAsync(out_pairs, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipEventElapsedTime(&ms, h->draw_ev[0], h->draw_ev[1]));
   h->draw_ms = ms;
   if (over) {
     h->err = "monsoon_draw_schedule: " + std::to_string(over) + " game(s) needed more than 624 outputs of their stream";
-    return done(MONSOON_ERR_STATE);
+    return MONSOON_ERR_STATE;
   }
-  return done(MONSOON_OK);
+  return MONSOON_OK;
 }
 
 int monsoon_draw_schedule_time(monsoon_t* h, double* kernel_ms) {
@@ -1177,75 +1152,50 @@ int monsoon_draw_schedule_time(monsoon_t* h, double* kernel_ms) {
 int monsoon_ga_offspring(monsoon_t* h, monsoon_np_state* st, const double* parents_w, const double* parents_s, int32_t mu, int32_t dim,
                          int32_t lambda, double tau, double tau_prime, double min_sigma, double* out_w, double* out_s, int32_t* out_parent,
                          int64_t* out_tries) {
-  if (!h || !st || !parents_w || !parents_s || !out_w || !out_s || mu <= 0 || lambda <= 0 || dim <= 0 || dim > 16 || st->pos < 0 || st->pos > MT_N) {
-    if (h) h->err = "monsoon_ga_offspring: bad argument (1 <= dim <= 16, 0 <= state position <= 624)";
-    return MONSOON_ERR_ARG;
-  }
+  if (!h || !st || !parents_w || !parents_s || !out_w || !out_s || mu <= 0 || lambda <= 0 || dim <= 0 || dim > 16 || st->pos < 0 || st->pos > MT_N)
+    return bad_arg(h, "monsoon_ga_offspring", "bad argument (1 <= dim <= 16, 0 <= state position <= 624)");
   HIP_TRY(h, bind_device(h));
-  const size_t pb = (size_t)mu * dim * 8, ob = (size_t)lambda * dim * 8;
-  uint8_t* d = nullptr;   // one allocation: key | pos, has_gauss | gauss | parents w, s | out w, s | parent | tries
-  const size_t o_key = 0, o_pg = MT_N * 4, o_g = o_pg + 8, o_pw = o_g + 8, o_ps = o_pw + pb, o_ow = o_ps + pb, o_os = o_ow + ob, o_par = o_os + ob,
-               o_tr = (o_par + (size_t)lambda * 4 + 7) & ~(size_t)7, total = o_tr + (size_t)lambda * 8;
-  HIP_TRY(h, hipMalloc(&d, total));
-  auto done = [&](int rc) {
-    hipFree(d);
-    return rc;
-  };
-#define GA_TRY(call)                                                  \
-  do {                                                                \
-    hipError_t e_ = (call);                                           \
-    if (e_ != hipSuccess) {                                           \
-      h->err = std::string(#call) + ": " + hipGetErrorString(e_);     \
-      return done(MONSOON_ERR_DEVICE);                                \
-    }                                                                 \
-  } while (0)
+  const layout::GaOffspring l = layout::ga_offspring((size_t)mu, (size_t)dim, (size_t)lambda, MT_N);
+  DevOwner tmp;   // freed on return
+  uint8_t* d = nullptr;
+  HIP_TRY(h, tmp.alloc(&d, l.total));
   int pg[2] = {st->pos, st->has_gauss};
-  GA_TRY(hipMemcpyAsync(d + o_key, st->key, MT_N * 4, hipMemcpyHostToDevice, h->stream));
-  GA_TRY(hipMemcpyAsync(d + o_pg, pg, 8, hipMemcpyHostToDevice, h->stream));
-  GA_TRY(hipMemcpyAsync(d + o_g, &st->gauss, 8, hipMemcpyHostToDevice, h->stream));
-  GA_TRY(hipMemcpyAsync(d + o_pw, parents_w, pb, hipMemcpyHostToDevice, h->stream));
-  GA_TRY(hipMemcpyAsync(d + o_ps, parents_s, pb, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_ga_offspring, dim3(1), dim3(64), 0, h->stream, (uint32_t*)(d + o_key), (int*)(d + o_pg), (double*)(d + o_g),
-                     (const double*)(d + o_pw), (const double*)(d + o_ps), mu, dim, lambda, tau, tau_prime, min_sigma, (double*)(d + o_ow),
-                     (double*)(d + o_os), (int*)(d + o_par), (long long*)(d + o_tr));
-  GA_TRY(hipGetLastError());
-  GA_TRY(hipMemcpyAsync(st->key, d + o_key, MT_N * 4, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipMemcpyAsync(pg, d + o_pg, 8, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipMemcpyAsync(&st->gauss, d + o_g, 8, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipMemcpyAsync(out_w, d + o_ow, ob, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipMemcpyAsync(out_s, d + o_os, ob, hipMemcpyDeviceToHost, h->stream));
-  if (out_parent) GA_TRY(hipMemcpyAsync(out_parent, d + o_par, (size_t)lambda * 4, hipMemcpyDeviceToHost, h->stream));
-  if (out_tries) GA_TRY(hipMemcpyAsync(out_tries, d + o_tr, (size_t)lambda * 8, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.key, st->key, MT_N * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.pos_gauss, pg, 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.gauss, &st->gauss, 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.parents_w, parents_w, l.parents_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.parents_s, parents_s, l.parents_bytes, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_ga_offspring, dim3(1), dim3(64), 0, h->stream, (uint32_t*)(d + l.key), (int*)(d + l.pos_gauss), (double*)(d + l.gauss),
+                     (const double*)(d + l.parents_w), (const double*)(d + l.parents_s), mu, dim, lambda, tau, tau_prime, min_sigma,
+                     (double*)(d + l.out_w), (double*)(d + l.out_s), (int*)(d + l.parent), (long long*)(d + l.tries));
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(st->key, d + l.key, MT_N * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(pg, d + l.pos_gauss, 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(&st->gauss, d + l.gauss, 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(out_w, d + l.out_w, l.out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(out_s, d + l.out_s, l.out_bytes, hipMemcpyDeviceToHost, h->stream));
+  if (out_parent) HIP_TRY(h, hipMemcpyAsync(out_parent, d + l.parent, (size_t)lambda * 4, hipMemcpyDeviceToHost, h->stream));
+  if (out_tries) HIP_TRY(h, hipMemcpyAsync(out_tries, d + l.tries, (size_t)lambda * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   st->pos = pg[0];
   st->has_gauss = pg[1];
-  return done(MONSOON_OK);
+  return MONSOON_OK;
 }
 
 int monsoon_ga_select(monsoon_t* h, const double* fitness, int32_t n, int32_t* out_order) {
-  if (!h || !fitness || !out_order || n <= 0) {
-    if (h) h->err = "monsoon_ga_select: bad argument";
-    return MONSOON_ERR_ARG;
-  }
+  if (!h || !fitness || !out_order || n <= 0) return bad_arg(h, "monsoon_ga_select", "bad argument");
   for (int i = 0; i < n; i++)
-    if (fitness[i] != fitness[i]) {
-      h->err = "monsoon_ga_select: NaN fitness (Python's sort order would be undefined)";
-      return MONSOON_ERR_ARG;
-    }
+    if (fitness[i] != fitness[i]) return bad_arg(h, "monsoon_ga_select", "NaN fitness (Python's sort order would be undefined)");
   HIP_TRY(h, bind_device(h));
+  DevOwner tmp;   // freed on return
   uint8_t* d = nullptr;
-  HIP_TRY(h, hipMalloc(&d, (size_t)n * 12));
-  auto done = [&](int rc) {
-    hipFree(d);
-    return rc;
-  };
-  GA_TRY(hipMemcpyAsync(d, fitness, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, tmp.alloc(&d, (size_t)n * 12));   // fitness f64 [n] | order i32 [n]
+  HIP_TRY(h, hipMemcpyAsync(d, fitness, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_ga_select, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const double*)d, n, (int*)(d + (size_t)n * 8));
-  GA_TRY(hipGetLastError());
-  GA_TRY(hipMemcpyAsync(out_order, d + (size_t)n * 8, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-  GA_TRY(hipStreamSynchronize(h->stream));
-#undef GA_TRY
-  return done(MONSOON_OK);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(out_order, d + (size_t)n * 8, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MONSOON_OK;
 }
 
 int monsoon_legal_mask(monsoon_t* h, uint64_t* out) {
@@ -1253,7 +1203,7 @@ int monsoon_legal_mask(monsoon_t* h, uint64_t* out) {
   if (rc) return rc;
   if (!out) return MONSOON_ERR_ARG;
   int n = h->n;
-  hipLaunchKernelGGL(k_legal, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, h->d_masks);
+  LAUNCH_LANES(h, k_legal, n, h->b, n, h->d_masks);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, h->d_masks, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1274,23 +1224,21 @@ int monsoon_step(monsoon_t* h, const uint8_t* actions, int8_t* reward, uint8_t* 
     for (int i = 0; i < n; i++) {
       int a = actions[i];
       if (a == 255 || a == 155) continue;   // skip / PASS (always accepted, see k_step)
-      if (a >= MONSOON_NUM_ACTIONS || !((masks[(size_t)i * 3 + (a >> 6)] >> (a & 63)) & 1)) {
-        h->err = "monsoon_step: illegal action " + std::to_string(a) + " for game " + std::to_string(i);
-        return MONSOON_ERR_ARG;
-      }
+      if (a >= MONSOON_NUM_ACTIONS || !((masks[(size_t)i * 3 + (a >> 6)] >> (a & 63)) & 1))
+        return bad_arg(h, "monsoon_step", "illegal action " + std::to_string(a) + " for game " + std::to_string(i));
     }
   }
-  uint8_t* d = h->d_bytes;   // [actions | reward | done | fault | illegal] x n
-  HIP_TRY(h, hipMemcpyAsync(d, actions, n, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_step, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, d, (int8_t*)(d + n), d + 2 * (size_t)n,
-                     d + 3 * (size_t)n, d + 4 * (size_t)n);
+  const layout::Step l = layout::step((size_t)n);
+  uint8_t* d = h->d_bytes;
+  HIP_TRY(h, hipMemcpyAsync(d + l.actions, actions, n, hipMemcpyHostToDevice, h->stream));
+  LAUNCH_LANES(h, k_step, n, h->b, n, d + l.actions, (int8_t*)(d + l.reward), d + l.done, d + l.fault, d + l.illegal);
   HIP_TRY(h, hipGetLastError());
-  std::vector<uint8_t> host(4 * (size_t)n);
-  HIP_TRY(h, hipMemcpyAsync(host.data(), d + n, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  std::vector<uint8_t> host(l.total - l.reward);   // reward .. illegal in one copy
+  HIP_TRY(h, hipMemcpyAsync(host.data(), d + l.reward, host.size(), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (reward) memcpy(reward, host.data(), n);
-  if (done) memcpy(done, host.data() + n, n);
-  if (fault) memcpy(fault, host.data() + 2 * (size_t)n, n);
+  if (done) memcpy(done, host.data() + (l.done - l.reward), n);
+  if (fault) memcpy(fault, host.data() + (l.fault - l.reward), n);
   return MONSOON_OK;
 }
 
@@ -1299,14 +1247,15 @@ int monsoon_expert_action(monsoon_t* h, uint8_t* out_action, uint8_t* fault) {
   if (rc) return rc;
   if (!out_action) return MONSOON_ERR_ARG;
   int n = h->n;
+  const layout::Expert l = layout::expert((size_t)n);
   uint8_t* d = h->d_bytes;
-  hipLaunchKernelGGL(k_expert, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, d, d + n);
+  LAUNCH_LANES(h, k_expert, n, h->b, n, d + l.action, d + l.fault);
   HIP_TRY(h, hipGetLastError());
-  std::vector<uint8_t> host(2 * (size_t)n);
-  HIP_TRY(h, hipMemcpyAsync(host.data(), d, 2 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  std::vector<uint8_t> host(l.total);
+  HIP_TRY(h, hipMemcpyAsync(host.data(), d, l.total, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  memcpy(out_action, host.data(), n);
-  if (fault) memcpy(fault, host.data() + n, n);
+  memcpy(out_action, host.data() + l.action, n);
+  if (fault) memcpy(fault, host.data() + l.fault, n);
   return MONSOON_OK;
 }
 
@@ -1315,8 +1264,8 @@ int monsoon_observe(monsoon_t* h, int32_t* out, uint8_t* raises) {
   if (rc) return rc;
   if (!out) return MONSOON_ERR_ARG;
   int n = h->n;
-  if (!h->d_i32) HIP_TRY(h, hipMalloc(&h->d_i32, (size_t)h->cfg.max_games * MONSOON_OBS_INTS * 4));
-  hipLaunchKernelGGL(k_observe, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, h->d_i32, h->d_bytes);
+  if (!h->d_i32) HIP_TRY(h, h->mem.alloc(&h->d_i32, (size_t)h->cfg.max_games * MONSOON_OBS_INTS * 4));
+  LAUNCH_LANES(h, k_observe, n, h->b, n, h->d_i32, h->d_bytes);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, h->d_i32, (size_t)n * MONSOON_OBS_INTS * 4, hipMemcpyDeviceToHost, h->stream));
   std::vector<uint8_t> r(n);
@@ -1334,7 +1283,7 @@ int monsoon_observe_dev(monsoon_t* h, void* out_dev, void* raises_dev) {
   if (!out_dev) return MONSOON_ERR_ARG;
   int n = h->n;
   uint8_t* r = raises_dev ? (uint8_t*)raises_dev : h->d_bytes;
-  hipLaunchKernelGGL(k_observe, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, (int32_t*)out_dev, r);
+  LAUNCH_LANES(h, k_observe, n, h->b, n, (int32_t*)out_dev, r);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return MONSOON_OK;
@@ -1345,8 +1294,8 @@ int monsoon_features(monsoon_t* h, double* out) {
   if (rc) return rc;
   if (!out) return MONSOON_ERR_ARG;
   int n = h->n;
-  if (!h->d_f64) HIP_TRY(h, hipMalloc(&h->d_f64, (size_t)h->cfg.max_games * 10 * 8));
-  hipLaunchKernelGGL(k_features, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, h->d_f64);
+  if (!h->d_f64) HIP_TRY(h, h->mem.alloc(&h->d_f64, (size_t)h->cfg.max_games * 10 * 8));
+  LAUNCH_LANES(h, k_features, n, h->b, n, h->d_f64);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, h->d_f64, (size_t)n * 80, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1358,7 +1307,7 @@ int monsoon_status(monsoon_t* h, int32_t* out) {
   if (rc) return rc;
   if (!out) return MONSOON_ERR_ARG;
   int n = h->n;
-  if (!h->d_i32) HIP_TRY(h, hipMalloc(&h->d_i32, (size_t)h->cfg.max_games * MONSOON_OBS_INTS * 4));
+  if (!h->d_i32) HIP_TRY(h, h->mem.alloc(&h->d_i32, (size_t)h->cfg.max_games * MONSOON_OBS_INTS * 4));
   hipLaunchKernelGGL(k_status, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->b, n, h->d_i32);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, h->d_i32, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
@@ -1370,14 +1319,15 @@ int monsoon_state_export(monsoon_t* h, int32_t idx, uint8_t* buf, int32_t* len) 
   int rc = check_ready(h);
   if (rc) return rc;
   if (!buf || !len || idx < 0 || idx >= h->n) return MONSOON_ERR_ARG;
-  hipLaunchKernelGGL(k_export, dim3(1), dim3(64), API_LDS_BYTES, h->stream, h->b, idx, h->d_bytes, (int32_t*)(h->d_bytes + 2048));
+  constexpr layout::Export l = layout::state_export();
+  hipLaunchKernelGGL(k_export, dim3(1), dim3(64), API_LDS_BYTES, h->stream, h->b, idx, h->d_bytes + l.buf, (int32_t*)(h->d_bytes + l.len));
   HIP_TRY(h, hipGetLastError());
-  uint8_t host[2048 + 4];
-  HIP_TRY(h, hipMemcpyAsync(host, h->d_bytes, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+  uint8_t host[l.total];
+  HIP_TRY(h, hipMemcpyAsync(host, h->d_bytes, l.total, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   int32_t n;
-  memcpy(&n, host + 2048, 4);
-  memcpy(buf, host, n);
+  memcpy(&n, host + l.len, 4);
+  memcpy(buf, host + l.buf, n);
   *len = n;
   return MONSOON_OK;
 }
@@ -1400,11 +1350,8 @@ int32_t monsoon_state_blob_bytes(void) { return BLOB_BYTES; }
 int monsoon_state_save(monsoon_t* h, int32_t idx, uint8_t* buf, int32_t buf_bytes) {
   int rc = check_ready(h);
   if (rc) return rc;
-  if (!buf || buf_bytes < BLOB_BYTES || idx < 0 || idx >= h->n) {
-    h->err = "monsoon_state_save: bad argument (buffer must hold monsoon_state_blob_bytes())";
-    return MONSOON_ERR_ARG;
-  }
-  static_assert(BLOB_BYTES <= 16384, "blob staging buffer");
+  if (!buf || buf_bytes < BLOB_BYTES || idx < 0 || idx >= h->n)
+    return bad_arg(h, "monsoon_state_save", "bad argument (buffer must hold monsoon_state_blob_bytes())");
   hipLaunchKernelGGL(k_blob, dim3(1), dim3(256), 0, h->stream, h->b, idx, (uint32_t*)h->d_bytes, 0);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(buf, h->d_bytes, BLOB_BYTES, hipMemcpyDeviceToHost, h->stream));
@@ -1417,20 +1364,16 @@ int monsoon_state_load(monsoon_t* h, int32_t idx, const uint8_t* buf, int32_t bu
   if (!h || !buf) return MONSOON_ERR_ARG;
   uint32_t head[2];
   if (buf_bytes >= 8) memcpy(head, buf, 8);
-  if (buf_bytes < BLOB_BYTES || head[0] != BLOB_MAGIC || head[1] != (uint32_t)STATE_BYTES || idx < 0 || idx > h->n || idx >= h->cfg.max_games) {
-    h->err = "monsoon_state_load: not a state blob of this build, or slot out of range";
-    return MONSOON_ERR_ARG;
-  }
+  if (buf_bytes < BLOB_BYTES || head[0] != BLOB_MAGIC || head[1] != (uint32_t)STATE_BYTES || idx < 0 || idx > h->n || idx >= h->cfg.max_games)
+    return bad_arg(h, "monsoon_state_load", "not a state blob of this build, or slot out of range");
   // The blob carries the game's bookkeeping row as it was in the handle that saved it.  What refers to THAT handle is
   // checked here: a stream cursor outside its two resident blocks is refused; the players' weight rows are kept only if
   // this handle's weight table has them (else both become row 0 -- assign players again before deciding).  The schedule
   // index travels along untouched: only monsoon_rollout reads it, after it has reset every game and set it anew.
   GameMeta gm;
   memcpy(&gm, buf + 8, sizeof(gm));
-  if ((gm.rng & 0xffffu) >= (uint32_t)(2 * MT_N) || (gm.rng >> 17) != 0) {
-    h->err = "monsoon_state_load: the blob's stream cursor is out of range";
-    return MONSOON_ERR_ARG;
-  }
+  if ((gm.rng & 0xffffu) >= (uint32_t)(2 * MT_N) || (gm.rng >> 17) != 0)
+    return bad_arg(h, "monsoon_state_load", "the blob's stream cursor is out of range");
   if (gm.p1 < 0 || gm.p2 < 0 || (h->b.weights && (gm.p1 >= h->n_individuals || gm.p2 >= h->n_individuals))) gm.p1 = gm.p2 = 0;
   std::vector<uint8_t> staged(buf, buf + BLOB_BYTES);
   memcpy(staged.data() + 8, &gm, sizeof(gm));
@@ -1446,14 +1389,12 @@ int monsoon_state_load(monsoon_t* h, int32_t idx, const uint8_t* buf, int32_t bu
 // Diagnostics for the scenario tests (tests/scenario_lib.py): build game idx from a state stream / make one engine call.
 static int debug_call(monsoon_t* h, int32_t idx, int build, uint32_t seed, uint32_t stream_pos, const int32_t* stream, int32_t n_stream,
                       int32_t* fault, int32_t* log, int32_t log_cap, int32_t* n_log) {
-  if (!h || !stream || n_stream <= 0 || n_stream > 3000 || idx < 0 || idx >= h->cfg.max_games || idx > h->n) {
-    if (h) h->err = "monsoon_debug_*: bad argument";
-    return MONSOON_ERR_ARG;
-  }
+  if (!h || !stream || n_stream <= 0 || n_stream > (int)layout::DEBUG_STREAM_MAX || idx < 0 || idx >= h->cfg.max_games || idx > h->n)
+    return bad_arg(h, "monsoon_debug_*", "bad argument");
   HIP_TRY(h, bind_device(h));
-  static_assert(3000 * 4 + (2 + 2 * DBG_TRACE_CAP) * 4 <= 16384, "staging buffer");
-  int32_t* d_stream = (int32_t*)h->d_bytes;
-  int32_t* d_out = d_stream + 3000;
+  const layout::Debug l = layout::debug(DBG_TRACE_CAP);
+  int32_t* d_stream = (int32_t*)(h->d_bytes + l.stream);
+  int32_t* d_out = (int32_t*)(h->d_bytes + l.out);
   HIP_TRY(h, hipMemcpyAsync(d_stream, stream, (size_t)n_stream * 4, hipMemcpyHostToDevice, h->stream));
   if (build) {
     HIP_TRY(h, hipMemcpyAsync(h->d_seeds + idx, &seed, 4, hipMemcpyHostToDevice, h->stream));
@@ -1461,7 +1402,7 @@ static int debug_call(monsoon_t* h, int32_t idx, int build, uint32_t seed, uint3
   }
   hipLaunchKernelGGL(k_debug, dim3(1), dim3(64), DBG_LDS_BYTES, h->stream, h->b, idx, build, seed, stream_pos, d_stream, d_out);
   HIP_TRY(h, hipGetLastError());
-  std::vector<int32_t> out(2 + 2 * DBG_TRACE_CAP);
+  std::vector<int32_t> out(l.out_words);
   HIP_TRY(h, hipMemcpyAsync(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (fault) *fault = out[0];
@@ -1475,10 +1416,7 @@ int monsoon_debug_build(monsoon_t* h, int32_t idx, uint32_t seed, uint32_t strea
   return debug_call(h, idx, 1, seed, stream_pos, state, n_state, fault, nullptr, 0, nullptr);
 }
 int monsoon_debug_op(monsoon_t* h, int32_t idx, const int32_t* op, int32_t n_op, int32_t* fault, int32_t* log, int32_t log_cap, int32_t* n_log) {
-  if (h && idx >= h->n) {
-    h->err = "monsoon_debug_op: no such game";
-    return MONSOON_ERR_ARG;
-  }
+  if (h && idx >= h->n) return bad_arg(h, "monsoon_debug_op", "no such game");
   return debug_call(h, idx, 0, 0, 0, op, n_op, fault, log, log_cap, n_log);
 }
 
@@ -1486,37 +1424,23 @@ int monsoon_debug_op(monsoon_t* h, int32_t idx, const int32_t* op, int32_t n_op,
 // shuffle(list(range(12))) on one stream (out int32[n][12]); 4: n scores of in = double[n][30] {weights, before, after}.
 // Uses (and re-seeds) the stream buffers of game slot 0.
 int monsoon_debug_kat(monsoon_t* h, int32_t kind, uint32_t seed, int32_t n, const void* in, void* out) {
-  if (!h || !out || n <= 0 || n > 4096 || kind < 0 || kind > 4 || ((kind == 2 || kind == 4) && !in)) {
-    if (h) h->err = "monsoon_debug_kat: bad argument";
-    return MONSOON_ERR_ARG;
-  }
+  if (!h || !out || n <= 0 || n > 4096 || kind < 0 || kind > 4 || ((kind == 2 || kind == 4) && !in)) return bad_arg(h, "monsoon_debug_kat", "bad argument");
   HIP_TRY(h, bind_device(h));
   const size_t in_bytes = kind == 2 ? (size_t)n * 4 : (kind == 4 ? (size_t)n * 240 : 0);
   const size_t out_bytes = kind == 3 ? (size_t)n * 48 : (kind == 1 || kind == 4 ? (size_t)n * 8 : (size_t)n * 4);
+  DevOwner tmp;   // freed on return
   void *d_in = nullptr, *d_out = nullptr;
-  HIP_TRY(h, hipMalloc(&d_out, out_bytes));
+  HIP_TRY(h, tmp.alloc(&d_out, out_bytes));
   if (in_bytes) {
-    hipError_t e = hipMalloc(&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      hipFree(d_out);
-      if (d_in) hipFree(d_in);
-      h->err = std::string("monsoon_debug_kat: ") + hipGetErrorString(e);
-      return MONSOON_ERR_DEVICE;
-    }
+    HIP_TRY(h, tmp.alloc(&d_in, in_bytes));
+    HIP_TRY(h, hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
   }
-  hipMemcpyAsync(h->d_seeds, &seed, 4, hipMemcpyHostToDevice, h->stream);
+  HIP_TRY(h, hipMemcpyAsync(h->d_seeds, &seed, 4, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_seed, dim3(1), dim3(64), 0, h->stream, h->b, 0, 1, h->d_seeds);
   hipLaunchKernelGGL(k_kat, dim3(1), dim3(64), DBG_LDS_BYTES, h->stream, h->b, kind, n, (const void*)d_in, d_out);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  hipFree(d_out);
-  if (d_in) hipFree(d_in);
-  if (e != hipSuccess) {
-    h->err = std::string("monsoon_debug_kat: ") + hipGetErrorString(e);
-    return MONSOON_ERR_DEVICE;
-  }
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return MONSOON_OK;
 }
 
@@ -1537,7 +1461,7 @@ int monsoon_state_hash(monsoon_t* h, uint64_t* out) {
   if (rc) return rc;
   if (!out) return MONSOON_ERR_ARG;
   int n = h->n;
-  hipLaunchKernelGGL(k_hash, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, n, h->d_masks);
+  LAUNCH_LANES(h, k_hash, n, h->b, n, h->d_masks);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, h->d_masks, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1548,13 +1472,9 @@ int monsoon_upload_weights(monsoon_t* h, const double* weights, int32_t n_indivi
   if (!h || !weights || n_individuals <= 0) return MONSOON_ERR_ARG;
   HIP_TRY(h, bind_device(h));
   if (n_individuals > h->weights_cap) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->b.weights) HIP_TRY(h, hipFree(h->b.weights));
-    h->b.weights = nullptr;
-    h->weights_cap = 0;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // a launch in flight may still read the table that is freed
     h->n_individuals = 0;
-    HIP_TRY(h, hipMalloc(&h->b.weights, (size_t)n_individuals * 80));
-    h->weights_cap = n_individuals;
+    HIP_TRY(h, h->mem.grow(h->b.weights, h->weights_cap, n_individuals, (size_t)n_individuals * 80, Grow::Replace));
   }
   HIP_TRY(h, hipMemcpyAsync(h->b.weights, weights, (size_t)n_individuals * 80, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1567,10 +1487,8 @@ static int assign_players(monsoon_t* h, const int32_t* p1, const int32_t* p2, in
   int n = h->n;
   bool bot_rows = false;
   for (int i = 0; i < n; i++) {
-    if (p1[i] < min_row || p2[i] < min_row || p1[i] >= h->n_individuals || p2[i] >= h->n_individuals) {
-      h->err = "monsoon_assign_players: index outside the uploaded weight table";
-      return MONSOON_ERR_ARG;
-    }
+    if (p1[i] < min_row || p2[i] < min_row || p1[i] >= h->n_individuals || p2[i] >= h->n_individuals)
+      return bad_arg(h, "monsoon_assign_players", "index outside the uploaded weight table");
     bot_rows |= p1[i] < 0 || p2[i] < 0;
   }
   h->bot_rows = bot_rows;
@@ -1593,13 +1511,8 @@ int monsoon_assign_players(monsoon_t* h, const int32_t* p1, const int32_t* p2) {
 static int timing_begin(monsoon_t* h, size_t* slot) {
   if (h->ev_used == h->ev_pool.size()) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(h, hipEventCreate(&e0));
-    hipError_t e = hipEventCreate(&e1);
-    if (e != hipSuccess) {
-      hipEventDestroy(e0);
-      h->err = std::string("hipEventCreate: ") + hipGetErrorString(e);
-      return MONSOON_ERR_DEVICE;
-    }
+    HIP_TRY(h, lazy_event(h, e0));
+    HIP_TRY(h, lazy_event(h, e1));
     h->ev_pool.emplace_back(e0, e1);
     h->ev_split.push_back(0);
   }
@@ -1646,18 +1559,14 @@ static int drain_timing(monsoon_t* h) {
 static int grow_ovf(monsoon_t* h, size_t lanes) {
   if (lanes <= h->ovf_lanes) return MONSOON_OK;
   lanes = std::max(lanes, 2 * h->ovf_lanes);
-  uint32_t* grown = nullptr;
   hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
   HIP_TRY(h, hipThreadExchangeStreamCaptureMode(&mode));
-  const hipError_t e = hipMalloc(&grown, lanes * OVF_WORDS * 4);
+  const hipError_t e = (hipError_t)h->mem.grow(h->b.wk_ovf, h->ovf_lanes, lanes, lanes * OVF_WORDS * 4, Grow::Retire);
   HIP_TRY(h, hipThreadExchangeStreamCaptureMode(&mode));
   if (e != hipSuccess) {
     h->err = std::string("hipMalloc of the work-stack overflow blocks: ") + hipGetErrorString(e);
     return MONSOON_ERR_DEVICE;
   }
-  if (h->b.wk_ovf) h->ovf_retired.push_back(h->b.wk_ovf);
-  h->b.wk_ovf = grown;
-  h->ovf_lanes = lanes;
   return MONSOON_OK;
 }
 
@@ -1686,27 +1595,36 @@ static int resident_waves(monsoon_t* h, hipError_t (*occupancy)(int*, int), int 
   return MONSOON_OK;
 }
 
-// `rounds` decisions of every loaded game in ONE launch (1 = a decision round; max_turns + 1 = whole games: the extra
-// round turns "still running at the cap" into a result).
-// vs = true: k_play_vs, the kernel that knows the scripted bot (the build's default variant, whatever the handle's is).
-// log (monsoon_rollout_logged): k_play_log, k_play_vs that writes every committed step into *log; never split either.
-// split = true (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below.
-static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write_scores, bool timed, bool vs = false, bool split = false,
-                       const PlayLog* log = nullptr) {
-  if (h->bot_rows && !vs && !log) {   // (a weight row of -1 must never reach k_play)
+// What one launch_play call plays.
+struct PlayCall {
+  PlayKind kind = PLAY;
+  int max_turns = 0x7fff;        // a game ends undecided once it has lasted this long
+  int rounds = 1;                // decisions per game (1 = a decision round; max_turns + 1 = whole games: the extra round
+                                 // turns "still running at the cap" into a result)
+  bool write_scores = false;     // every candidate's score goes to b.scores
+  bool timed = false;            // an event pair of the handle round the call (kernel_ms)
+  bool split = false;            // PLAY only (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below
+  const PlayLog* log = nullptr;  // PLAY_LOG only (monsoon_rollout_logged): where every committed step is written
+};
+
+// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS and PLAY_LOG are never split.
+static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
+  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG;
+  bool timed = call.timed;
+  if (h->bot_rows && call.kind == PLAY) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
   }
   const VariantOps* vp = vs ? monsoon_vs_expert_ops() : h->var;
   const KernelOps* v = log ? static_cast<const KernelOps*>(monsoon_play_log_ops()) : vp;
   const int lds = v->lds_bytes + g_lds_pad;
-  int& grid_waves = log ? h->log_grid_waves : vs ? h->vs_grid_waves : h->grid_waves;
+  int& grid_waves = h->grid_waves[call.kind];
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
     const int rc = resident_waves(h, v->occupancy, lds, 4096, &grid_waves);
     if (rc) return rc;
   }
   // one decision per game and launch: two waves per slot measured best; many decisions per game: exactly the resident waves
-  int grid = rounds > 1 ? grid_waves : 2 * grid_waves;
+  int grid = call.rounds > 1 ? grid_waves : 2 * grid_waves;
   if (const char* e = getenv("MONSOON_GRID")) grid = atoi(e);
   // A call recorded into a graph is replayed as it stands, any number of times in a row.  The persistent form cannot be:
   // `parity` is a kernel argument, a launch counts its own counter set up and clears only the other one, so the second
@@ -1728,7 +1646,7 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   // captured (a graph holds one stream's work), and only where every sub-batch is still persistent.  MONSOON_SPLIT = 0 / 1:
   // one launch; read per call, like MONSOON_GRID.
   int parts = 1;
-  if (split && !vs && !log && pers) {
+  if (call.split && call.kind == PLAY && pers) {
     parts = 2;
     if (const char* e = getenv("MONSOON_SPLIT")) parts = std::min(std::max(atoi(e), 1), (int)SPLIT_MAX);
     if (n / parts <= grid) parts = 1;
@@ -1743,10 +1661,10 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
     if (rc) return rc;
   }
   for (int s = 1; s < parts; s++) {
-    if (!h->split_stream[s]) HIP_TRY(h, hipStreamCreateWithFlags(&h->split_stream[s], hipStreamNonBlocking));
-    if (!h->split_done[s]) HIP_TRY(h, hipEventCreateWithFlags(&h->split_done[s], hipEventDisableTiming));
+    HIP_TRY(h, h->streams.get(h->split_stream[s], [](hipStream_t* p) { return hipStreamCreateWithFlags(p, hipStreamNonBlocking); }));
+    HIP_TRY(h, lazy_event(h, h->split_done[s], hipEventDisableTiming));
   }
-  if (parts > 1 && !h->split_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->split_fork, hipEventDisableTiming));
+  if (parts > 1) HIP_TRY(h, lazy_event(h, h->split_fork, hipEventDisableTiming));
   size_t slot = 0;
   if (timed) {
     int rc = timing_begin(h, &slot);
@@ -1761,9 +1679,9 @@ static int launch_play(monsoon_t* h, int n, int max_turns, int rounds, int write
   for (int s = 0; s < parts; s++) {
     const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
     if (log)   // (parts == 1)
-      monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, max_turns, rounds, pers, h->parity[0], *log);
+      monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log);
     else
-      vp->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, max_turns, rounds, write_scores, pers, h->parity[s], g0, s);
+      vp->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, call.max_turns, call.rounds, call.write_scores, pers, h->parity[s], g0, s);
     // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
     // must leave the parity alone, or the next persistent launch would start from the stale counts of the one before.
     if (pers) h->parity[s] ^= 1;
@@ -1788,7 +1706,9 @@ int monsoon_decide_round_dev(monsoon_t* h) {
     h->err = "monsoon_decide_round_dev: upload weights and assign players first";
     return MONSOON_ERR_STATE;
   }
-  return launch_play(h, h->n, 0x7fff, 1, 0, true, false, true);
+  PlayCall call;
+  call.timed = call.split = true;
+  return launch_play(h, h->n, call);
 }
 
 // `rounds` decisions of every loaded game in one launch: a game's record stays in LDS from its first to its last decision
@@ -1800,7 +1720,10 @@ int monsoon_play_rounds_dev(monsoon_t* h, int32_t rounds) {
     h->err = "monsoon_play_rounds_dev: rounds must be positive; upload weights and assign players first";
     return rounds <= 0 ? MONSOON_ERR_ARG : MONSOON_ERR_STATE;
   }
-  return launch_play(h, h->n, 0x7fff, rounds, 0, true, false, true);
+  PlayCall call;
+  call.rounds = rounds;
+  call.timed = call.split = true;
+  return launch_play(h, h->n, call);
 }
 
 int monsoon_sync(monsoon_t* h) {
@@ -1826,11 +1749,13 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
   rc = assign_players(h, p1.data(), p2.data(), 0);
   if (rc) return rc;
   if (out_scores) {
-    if (!h->b.scores) HIP_TRY(h, hipMalloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
+    if (!h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
     size_t cnt = (size_t)n * MONSOON_NUM_ACTIONS;
     hipLaunchKernelGGL(k_clear_scores, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->b.scores, cnt);
   }
-  rc = launch_play(h, n, 0x7fff, 1, out_scores ? 1 : 0, false);
+  PlayCall call;
+  call.write_scores = out_scores != nullptr;
+  rc = launch_play(h, n, call);
   if (rc) return rc;
   std::vector<GameMeta> meta(n);
   HIP_TRY(h, hipMemcpyAsync(meta.data(), h->b.meta, (size_t)n * sizeof(GameMeta), hipMemcpyDeviceToHost, h->stream));
@@ -1847,6 +1772,40 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
 // (action + score + legal count), max_turns entries per game.
 constexpr size_t LOG_BUDGET = (size_t)256 << 20;
 
+// Matches [base, base + n) of a rollout: load them, one launch plays the whole batch to the end, collect.  A batch without
+// a bot is k_play's, counted by k_collect, as ever.
+static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max_turns, const uint32_t* seeds, const uint8_t* decks, const int32_t* p1,
+                         const int32_t* p2, const monsoon_rollout_log* log, const PlayLog& dlog) {
+  int rc = monsoon_reset(h, n, seeds, decks, nullptr);
+  if (!rc) rc = assign_players(h, p1, p2, base, min_row);
+  if (rc) return rc;
+  const bool vs = h->bot_rows;
+  const size_t cnt = (size_t)n * max_turns, row = (size_t)base * max_turns;   // log entries of the batch, and where they go
+  if (log) {   // the padding behind a game's last step: action 255, score NaN (all ones), legal count 0
+    HIP_TRY(h, hipMemsetAsync(dlog.action, 0xFF, cnt, h->stream));
+    if (dlog.score) HIP_TRY(h, hipMemsetAsync(dlog.score, 0xFF, cnt * 8, h->stream));
+    if (dlog.n_legal) HIP_TRY(h, hipMemsetAsync(dlog.n_legal, 0, cnt * 2, h->stream));
+  }
+  PlayCall call;
+  call.kind = log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
+  call.max_turns = max_turns;
+  call.rounds = max_turns + 1;
+  call.timed = true;
+  call.log = log ? &dlog : nullptr;
+  rc = launch_play(h, n, call);
+  if (rc) return rc;
+  hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
+                     h->d_steps, (uint8_t*)h->d_results + layout::results(h->results_cap).fault);
+  HIP_TRY(h, hipGetLastError());
+  if (log) {
+    HIP_TRY(h, hipMemcpyAsync(log->action + row, dlog.action, cnt, hipMemcpyDeviceToHost, h->stream));
+    if (dlog.score) HIP_TRY(h, hipMemcpyAsync(log->score + row, dlog.score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    if (dlog.n_legal) HIP_TRY(h, hipMemcpyAsync(log->n_legal + row, dlog.n_legal, cnt * 2, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return drain_timing(h);
+}
+
 // monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and
 // monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
@@ -1855,60 +1814,37 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
-      max_turns > 30000) {
-    h->err = std::string(who) + ": bad argument";
-    return MONSOON_ERR_ARG;
-  }
+      max_turns > 30000)
+    return bad_arg(h, who, "bad argument");
   // The whole schedule and every deck are checked before anything is loaded or launched.
   for (int i = 0; i < n_matches; i++) {
     const monsoon_match& mm = matches[i];
-    if (mm.p1 < min_row || mm.p1 >= n_individuals || mm.p2 < min_row || mm.p2 >= n_individuals || mm.deck >= (uint32_t)n_decks) {
-      h->err = std::string(who) + ": schedule entry " + std::to_string(i) + " out of range";
-      return MONSOON_ERR_ARG;
-    }
+    if (mm.p1 < min_row || mm.p1 >= n_individuals || mm.p2 < min_row || mm.p2 >= n_individuals || mm.deck >= (uint32_t)n_decks)
+      return bad_arg(h, who, "schedule entry " + std::to_string(i) + " out of range");
   }
   int rc = check_decks(h, deck_pairs, (size_t)n_decks * 24, who);
   if (rc) return rc;
   rc = monsoon_upload_weights(h, weights, n_individuals);
   if (rc) return rc;
-  // result buffers live in the handle: grown when a larger schedule arrives, never freed per call
-  if ((size_t)n_individuals > h->counts_cap) {
-    if (h->d_counts) HIP_TRY(h, hipFree(h->d_counts));
-    h->d_counts = nullptr;
-    h->counts_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_counts, (size_t)n_individuals * 12));
-    h->counts_cap = (size_t)n_individuals;
-  }
-  if ((size_t)n_matches > h->matches_cap) {
-    if (h->d_results) HIP_TRY(h, hipFree(h->d_results));
-    if (h->d_steps) HIP_TRY(h, hipFree(h->d_steps));
-    h->d_results = nullptr;
-    h->d_steps = nullptr;
-    h->matches_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_results, 2 * (size_t)n_matches));
-    HIP_TRY(h, hipMalloc(&h->d_steps, (size_t)n_matches * 4));
-    h->matches_cap = (size_t)n_matches;
+  // result buffers live in the handle: grown when a larger schedule arrives, never freed per call (no synchronisation
+  // before an old one goes: monsoon_upload_weights left the stream idle)
+  if ((size_t)n_individuals > h->counts_cap)
+    HIP_TRY(h, h->mem.grow(h->d_counts, h->counts_cap, (size_t)n_individuals, (size_t)n_individuals * 12, Grow::Replace));
+  if ((size_t)n_matches > std::min(h->results_cap, h->steps_cap)) {   // both follow the schedule's length
+    HIP_TRY(h, h->mem.grow(h->d_results, h->results_cap, (size_t)n_matches, layout::results((size_t)n_matches).total, Grow::Replace));
+    HIP_TRY(h, h->mem.grow(h->d_steps, h->steps_cap, (size_t)n_matches, (size_t)n_matches * 4, Grow::Replace));
   }
   HIP_TRY(h, hipMemsetAsync(h->d_counts, 0, (size_t)n_individuals * 12, h->stream));
   h->rollout_matches = 0;
-  uint8_t* d_faults = (uint8_t*)h->d_results + h->matches_cap;
   int cap = h->cfg.max_games;
   PlayLog dlog = {nullptr, nullptr, nullptr, max_turns};
   if (log) {
     cap = (int)std::min((size_t)cap, std::max((size_t)1, LOG_BUDGET / ((size_t)11 * max_turns)));
-    const size_t log_rows = (size_t)std::min(cap, n_matches) * max_turns;   // entries of one device array
-    const size_t need = log_rows * ((log->score ? 8 : 0) + (log->n_legal ? 2 : 0) + 1);
-    if (need > h->log_cap) {
-      if (h->d_log) HIP_TRY(h, hipFree(h->d_log));
-      h->d_log = nullptr;
-      h->log_cap = 0;
-      HIP_TRY(h, hipMalloc(&h->d_log, need));
-      h->log_cap = need;
-    }
-    uint8_t* at = h->d_log;
-    if (log->score) dlog.score = (double*)at, at += log_rows * 8;
-    if (log->n_legal) dlog.n_legal = (int16_t*)at, at += log_rows * 2;
-    dlog.action = at;
+    const layout::RolloutLog l = layout::rollout_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal);
+    HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
+    if (log->score) dlog.score = (double*)(h->d_log + l.score);
+    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
+    dlog.action = h->d_log + l.action;
   }
   std::vector<uint32_t> seeds;
   std::vector<uint8_t> decks;
@@ -1926,30 +1862,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
       p1[i] = mm.p1;
       p2[i] = mm.p2;
     }
-    rc = monsoon_reset(h, n, seeds.data(), decks.data(), nullptr);
-    if (!rc) rc = assign_players(h, p1.data(), p2.data(), base, min_row);
-    if (rc) return rc;
-    // one launch plays the whole batch to the end; a batch without a bot is k_play's, counted by k_collect, as ever
-    const bool vs = h->bot_rows;
-    if (log) {   // the padding behind a game's last step: action 255, score NaN (all ones), legal count 0
-      const size_t cnt = (size_t)n * max_turns;
-      HIP_TRY(h, hipMemsetAsync(dlog.action, 0xFF, cnt, h->stream));
-      if (dlog.score) HIP_TRY(h, hipMemsetAsync(dlog.score, 0xFF, cnt * 8, h->stream));
-      if (dlog.n_legal) HIP_TRY(h, hipMemsetAsync(dlog.n_legal, 0, cnt * 2, h->stream));
-    }
-    rc = launch_play(h, n, max_turns, max_turns + 1, 0, true, vs, false, log ? &dlog : nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
-                       h->d_steps, d_faults);
-    HIP_TRY(h, hipGetLastError());
-    if (log) {
-      const size_t cnt = (size_t)n * max_turns, row = (size_t)base * max_turns;
-      HIP_TRY(h, hipMemcpyAsync(log->action + row, dlog.action, cnt, hipMemcpyDeviceToHost, h->stream));
-      if (dlog.score) HIP_TRY(h, hipMemcpyAsync(log->score + row, dlog.score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
-      if (dlog.n_legal) HIP_TRY(h, hipMemcpyAsync(log->n_legal + row, dlog.n_legal, cnt * 2, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = drain_timing(h);
+    rc = rollout_batch(h, base, n, min_row, max_turns, seeds.data(), decks.data(), p1.data(), p2.data(), log, dlog);
     if (rc) return rc;
   }
   std::vector<int32_t> counts((size_t)n_individuals * 3);
@@ -1979,22 +1892,17 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
                            const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
                            int32_t* out_steps, const monsoon_rollout_log* log) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!log || !log->action) {
-    h->err = "monsoon_rollout_logged: log and log->action are required";
-    return MONSOON_ERR_ARG;
-  }
+  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_logged", "log and log->action are required");
   return rollout_impl(h, "monsoon_rollout_logged", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
                       max_turns, out_counts, out_results, out_steps, log);
 }
 
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches) {
   if (!h || !out) return MONSOON_ERR_ARG;
-  if (n_matches <= 0 || (size_t)n_matches != h->rollout_matches) {
-    h->err = "monsoon_rollout_faults: n_matches is not the size of the last completed monsoon_rollout";
-    return MONSOON_ERR_ARG;
-  }
+  if (n_matches <= 0 || (size_t)n_matches != h->rollout_matches)
+    return bad_arg(h, "monsoon_rollout_faults", "n_matches is not the size of the last completed monsoon_rollout");
   HIP_TRY(h, bind_device(h));
-  HIP_TRY(h, hipMemcpy(out, (uint8_t*)h->d_results + h->matches_cap, (size_t)n_matches, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(out, (uint8_t*)h->d_results + layout::results(h->results_cap).fault, (size_t)n_matches, hipMemcpyDeviceToHost));
   return MONSOON_OK;
 }
 
@@ -2056,10 +1964,9 @@ int monsoon_debug_counters(monsoon_t* h, unsigned long long* out) {
     if (rc) return rc;
   }
   if (h->d_env && h->env_n > 0) {   // the vector env's committed agent / bot steps since monsoon_env_reset
-    const size_t cap = (size_t)h->cfg.max_games;
     std::vector<uint32_t> st(2 * (size_t)h->env_n);
-    HIP_TRY(h, hipMemcpy(st.data(), h->d_env + 8 * cap, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(st.data() + h->env_n, h->d_env + 12 * cap, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(st.data(), h->env.agent_steps, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(st.data() + h->env_n, h->env.bot_steps, (size_t)h->env_n * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < h->env_n; i++) {
       out[6] += st[i];
       out[7] += st[h->env_n + i];
@@ -2169,12 +2076,10 @@ static int launch_env_opp(monsoon_t* h, int n, int list) {
   ob.scores = nullptr;
   ob.best = nullptr;
   o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list);
-  hipLaunchKernelGGL(k_env_after_opp, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, list);
+  LAUNCH_LANES(h, k_env_after_opp, n, h->b, h->env, list);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
 }
-
-static size_t env_opp_bytes(size_t cap) { return 16 * cap + 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE); }
 
 extern "C" {
 
@@ -2187,24 +2092,17 @@ int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_ind
   else if (live && n_individuals > h->opp_w_cap) bad = "more weight rows than when the env was reset (the table is not reallocated under a loaded env)";
   for (int i = 0; !bad && rows && i < n; i++)
     if (rows[i] < 0 || rows[i] >= n_individuals) bad = "a row outside [0, n_individuals)";
-  if (bad) {
-    h->err = std::string("monsoon_env_set_opponents: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_set_opponents", bad);
   HIP_TRY(h, bind_device(h));
-  const size_t cap = (size_t)h->cfg.max_games;
-  if (!h->d_opp) HIP_TRY(h, hipMalloc(&h->d_opp, env_opp_bytes(cap)));
+  const layout::Opp l = opp_layout(h);
+  if (!h->d_opp) HIP_TRY(h, h->mem.alloc(&h->d_opp, l.total));
   if (n_individuals > h->opp_w_cap) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_opp_w) HIP_TRY(h, hipFree(h->d_opp_w));
-    h->d_opp_w = nullptr;
-    h->opp_w_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_opp_w, (size_t)n_individuals * 80));
-    h->opp_w_cap = n_individuals;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // a step in flight may still read the table that is freed
+    HIP_TRY(h, h->mem.grow(h->d_opp_w, h->opp_w_cap, n_individuals, (size_t)n_individuals * 80, Grow::Replace));
   }
   HIP_TRY(h, hipMemcpyAsync(h->d_opp_w, weights, (size_t)n_individuals * 80, hipMemcpyHostToDevice, h->stream));
-  if (rows) HIP_TRY(h, hipMemcpyAsync(h->d_opp, rows, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-  else HIP_TRY(h, hipMemsetAsync(h->d_opp, 0, (size_t)n * 4, h->stream));
+  if (rows) HIP_TRY(h, hipMemcpyAsync(h->d_opp + l.rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  else HIP_TRY(h, hipMemsetAsync(h->d_opp + l.rows, 0, (size_t)n * 4, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->opp_n = n;
   return MONSOON_OK;
@@ -2233,10 +2131,7 @@ int monsoon_env_set_schedule(monsoon_t* h, const monsoon_deck_schedule* sc) {
   else if (sc->phase != DS_STATIC && sc->phase != DS_EXPLORE && sc->phase != DS_BALANCE) bad = "phase must be 0 (static), 1 (explore) or 2 (balance)";
   else if (sc->n_preserve < 0 || sc->n_preserve > 12) bad = "0 <= n_preserve <= 12";
   else if (draws && (sc->pool_n[0] < 12 || sc->pool_n[0] > DS_POOL_MAX || sc->pool_n[1] < 12 || sc->pool_n[1] > DS_POOL_MAX)) bad = "12 <= pool_n <= 128";
-  if (bad) {
-    h->err = std::string("monsoon_env_set_schedule: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_set_schedule", bad);
   for (int side = 0; side < 2; side++) {
     int rc = check_decks(h, sc->archetype[side], 12, "monsoon_env_set_schedule (archetype)");
     if (!rc && draws) rc = check_decks(h, sc->pool[side], (size_t)sc->pool_n[side], "monsoon_env_set_schedule (pool)");
@@ -2244,7 +2139,7 @@ int monsoon_env_set_schedule(monsoon_t* h, const monsoon_deck_schedule* sc) {
   }
   HIP_TRY(h, bind_device(h));
   if (!h->d_sched) {
-    HIP_TRY(h, hipMalloc(&h->d_sched, sizeof(monsoon_deck_schedule) + 64));
+    HIP_TRY(h, h->mem.alloc(&h->d_sched, sizeof(monsoon_deck_schedule) + 64));
     HIP_TRY(h, hipMemsetAsync(h->d_sched, 0, sizeof(monsoon_deck_schedule) + 64, h->stream));
   }
   // behind every step already enqueued: the episodes they start draw from the schedule of their time
@@ -2266,8 +2161,7 @@ int monsoon_env_reseed_time(monsoon_t* h, int32_t enable, double* kernel_ms) {
     *kernel_ms = ms;
   }
   if (enable)
-    for (hipEvent_t& e : h->reseed_ev)
-      if (!e) HIP_TRY(h, hipEventCreate(&e));
+    for (hipEvent_t& e : h->reseed_ev) HIP_TRY(h, lazy_event(h, e));
   h->reseed_timed = enable != 0;
   if (!enable) h->reseed_have = false;
   return MONSOON_OK;
@@ -2276,14 +2170,8 @@ int monsoon_env_reseed_time(monsoon_t* h, int32_t enable, double* kernel_ms) {
 // One device-to-device copy on the handle's stream: no allocation or synchronisation (graph-capturable).
 int monsoon_env_decks_dev(monsoon_t* h, void* out_dev) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_decks_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
-  if (!out_dev) {
-    h->err = "monsoon_env_decks_dev: out_dev is NULL";
-    return MONSOON_ERR_ARG;
-  }
+  if (int rc = require_env(h, "monsoon_env_decks_dev")) return rc;
+  if (!out_dev) return bad_arg(h, "monsoon_env_decks_dev", "out_dev is NULL");
   HIP_TRY(h, bind_device(h));
   HIP_TRY(h, hipMemcpyAsync(out_dev, h->env.decks, (size_t)h->env_n * 24, hipMemcpyDeviceToDevice, h->stream));
   return MONSOON_OK;
@@ -2303,10 +2191,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
   else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
   else if (cfg->opponent == 2 && h->opp_n && h->opp_n != n) bad = "n differs from the n of monsoon_env_set_opponents";
-  if (bad) {
-    h->err = std::string("monsoon_env_reset: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_reset", bad);
   if (cfg->opponent == 2 && !h->opp_n) {
     h->err = "monsoon_env_reset: opponent 2 needs monsoon_env_set_opponents first";
     return MONSOON_ERR_STATE;
@@ -2324,26 +2209,26 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   rc = fold_stats(h);   // statistics live in the per-game rows that are about to be cleared
   if (rc) return rc;
   h->env_on = false;
-  const size_t cap = (size_t)h->cfg.max_games;
-  if (!h->d_env) HIP_TRY(h, hipMalloc(&h->d_env, 45 * cap + 128));
+  const layout::Env l = layout::env((size_t)h->cfg.max_games);
+  if (!h->d_env) HIP_TRY(h, h->mem.alloc(&h->d_env, l.total));
   EnvDev& v = h->env;
   uint8_t* base = h->d_env;
   v.v = *views;
-  v.seed0 = (const uint32_t*)base;
-  v.episode = (int32_t*)(base + 4 * cap);
-  v.agent_steps = (uint32_t*)(base + 8 * cap);
-  v.bot_steps = (uint32_t*)(base + 12 * cap);
-  v.decks = base + 16 * cap;
-  v.factions = base + 40 * cap;
-  v.mark = base + 42 * cap;
-  v.pool = base + 43 * cap;
-  h->d_snap_flag = base + 43 * cap + 128;
+  v.seed0 = (const uint32_t*)(base + l.seed0);
+  v.episode = (int32_t*)(base + l.episode);
+  v.agent_steps = (uint32_t*)(base + l.agent_steps);
+  v.bot_steps = (uint32_t*)(base + l.bot_steps);
+  v.decks = base + l.decks;
+  v.factions = base + l.factions;
+  v.mark = base + l.mark;
+  v.pool = base + l.pool;
+  h->d_snap_flag = base + l.snap_flag;
   v.pool_n = cfg->pool_n;
   v.opponent = cfg->opponent;
   v.agent_side = cfg->agent_side;
   v.max_steps = cfg->max_steps;
   v.stride = cfg->seed_stride ? cfg->seed_stride : (uint32_t)n;
-  v.cap = (int)cap;
+  v.cap = h->cfg.max_games;
   v.opp_rows = nullptr;
   v.opp_list = nullptr;
   v.opp_count = nullptr;
@@ -2355,11 +2240,12 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     HIP_TRY(h, hipMemsetAsync(h->env_sched.over, 0, 4, h->stream));
   }
   if (cfg->opponent == 2) {
-    v.opp_rows = (const int32_t*)h->d_opp;
-    v.opp_list = (int32_t*)(h->d_opp + 4 * cap);
-    v.opp_lookahead = (uint32_t*)(h->d_opp + 12 * cap);
-    v.opp_count = (int32_t*)(h->d_opp + 16 * cap);
-    v.opp_pop = (int*)(h->d_opp + 16 * cap + 4 * 2 * ENV_COUNT_STRIDE);
+    const layout::Opp ol = opp_layout(h);
+    v.opp_rows = (const int32_t*)(h->d_opp + ol.rows);
+    v.opp_list = (int32_t*)(h->d_opp + ol.list);
+    v.opp_lookahead = (uint32_t*)(h->d_opp + ol.lookahead);
+    v.opp_count = (int32_t*)(h->d_opp + ol.count);
+    v.opp_pop = (int*)(h->d_opp + ol.pop);
     const EnvOppOps* o = monsoon_env_opp_ops();
     int waves = 0;
     rc = resident_waves(h, o->occupancy, o->lds_bytes, 4096, &waves);
@@ -2368,7 +2254,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     h->opp_grid = std::max(POP_PARTS, std::min(waves, n));
     rc = grow_ovf(h, (size_t)h->opp_grid * o->lanes);   // work-stack overflow blocks for every workgroup of k_env_opp
     if (rc) return rc;
-    HIP_TRY(h, hipMemsetAsync(v.opp_count, 0, 4 * (2 * ENV_COUNT_STRIDE + 2 * POP_PARTS * POP_STRIDE), h->stream));
+    HIP_TRY(h, hipMemsetAsync(v.opp_count, 0, ol.total - ol.count, h->stream));   // the lists' counts and the pop counters
     HIP_TRY(h, hipMemsetAsync(v.opp_lookahead, 0, (size_t)n * 4, h->stream));
   }
   {   // monsoon_env_afterstates_dev allocates nothing: its grid and the overflow blocks of its workgroups are settled here
@@ -2398,7 +2284,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   HIP_TRY(h, hipMemsetAsync(v.mark, 1, (size_t)n, h->stream));
   HIP_TRY(h, hipMemsetAsync(h->b.meta, 0, (size_t)n * sizeof(GameMeta), h->stream));
   launch_env_reseed(h, n);
-  hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, v, n, 1);
+  LAUNCH_LANES(h, k_env_init, n, h->b, v, n, 1);
   HIP_TRY(h, hipGetLastError());
   if (cfg->opponent == 2) {   // the opening turns of the episodes the opponent starts (list 1)
     rc = launch_env_opp(h, n, 1);
@@ -2416,17 +2302,11 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
 // again after the re-initialisation.
 int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_step_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
-  if (!actions_dev) {
-    h->err = "monsoon_env_step_dev: actions_dev is NULL";
-    return MONSOON_ERR_ARG;
-  }
+  if (int rc = require_env(h, "monsoon_env_step_dev")) return rc;
+  if (!actions_dev) return bad_arg(h, "monsoon_env_step_dev", "actions_dev is NULL");
   HIP_TRY(h, bind_device(h));
   const int n = h->env_n;
-  hipLaunchKernelGGL(k_env_step, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, actions_dev);
+  LAUNCH_LANES(h, k_env_step, n, h->b, h->env, n, actions_dev);
   if (h->env.opponent == 2) {
     int rc = launch_env_opp(h, n, 0);
     if (rc) return rc;
@@ -2439,7 +2319,7 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
     HIP_TRY(h, hipEventRecord(h->reseed_ev[1], h->stream));
     h->reseed_have = true;
   }
-  hipLaunchKernelGGL(k_env_init, dim3((n + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, n, 0);
+  LAUNCH_LANES(h, k_env_init, n, h->b, h->env, n, 0);
   HIP_TRY(h, hipGetLastError());
   if (h->env.opponent == 2) return launch_env_opp(h, n, 1);
   return MONSOON_OK;
@@ -2449,19 +2329,13 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev) {
 // written (env_after.h).
 int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int32_t max_after) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_afterstates_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
+  if (int rc = require_env(h, "monsoon_env_afterstates_dev")) return rc;
   const char* bad = nullptr;
   if (!out || !out->n_legal || !out->action) bad = "out, out->n_legal and out->action are required";
   else if (max_after < 1 || max_after > MONSOON_NUM_ACTIONS) bad = "1 <= max_after <= 156";
   else if (((uintptr_t)out->obs | (uintptr_t)out->n_legal) & 3) bad = "n_legal and obs must be 4-byte aligned";
   else if (((uintptr_t)out->features | (uintptr_t)out->before_features) & 7) bad = "features and before_features must be 8-byte aligned";
-  if (bad) {
-    h->err = std::string("monsoon_env_afterstates_dev: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_afterstates_dev", bad);
   HIP_TRY(h, bind_device(h));
   const EnvAfterOps* o = monsoon_env_after_ops();
   o->launch(h->after_grid, o->lds_bytes, h->stream, h->b, *out, h->env_n, max_after);
@@ -2471,10 +2345,7 @@ int monsoon_env_afterstates_dev(monsoon_t* h, const monsoon_env_after* out, int3
 
 int monsoon_env_entry_bytes(monsoon_t* h, int32_t* out) {
   if (!h || !out) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_entry_bytes: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
+  if (int rc = require_env(h, "monsoon_env_entry_bytes")) return rc;
   *out = monsoon_env_snap_ops()->entry_bytes;
   return MONSOON_OK;
 }
@@ -2487,19 +2358,13 @@ static int snap_grid(const monsoon_t* h, int m) { return std::min((m + SNAP_WAVE
 // written.
 int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_dev, int32_t m) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_save_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
+  if (int rc = require_env(h, "monsoon_env_save_dev")) return rc;
   const char* bad = nullptr;
   if (!entries_dev) bad = "entries_dev is NULL";
   else if ((uintptr_t)entries_dev & 15) bad = "entries_dev must be 16-byte aligned";
   else if (m < 0) bad = "m < 0";
   else if (!slots_dev && m > h->env_n) bad = "m > n without slots_dev";
-  if (bad) {
-    h->err = std::string("monsoon_env_save_dev: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_save_dev", bad);
   if (m == 0) return MONSOON_OK;
   HIP_TRY(h, bind_device(h));
   monsoon_env_snap_ops()->save(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, slots_dev, m, (uint32_t)monsoon_version());
@@ -2512,26 +2377,20 @@ int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_d
 int monsoon_env_load_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev, int32_t m,
                          uint8_t* loaded_dev) {
   if (!h) return MONSOON_ERR_ARG;
-  if (!h->env_on) {
-    h->err = "monsoon_env_load_dev: no env loaded (call monsoon_env_reset; monsoon_reset / monsoon_rollout end env mode)";
-    return MONSOON_ERR_STATE;
-  }
+  if (int rc = require_env(h, "monsoon_env_load_dev")) return rc;
   const char* bad = nullptr;
   if (!entries_dev) bad = "entries_dev is NULL";
   else if ((uintptr_t)entries_dev & 15) bad = "entries_dev must be 16-byte aligned";
   else if (m < 0 || n_entries < 0) bad = "m < 0 or n_entries < 0";
   else if (!dst_dev && m > h->env_n) bad = "m > n without dst_dev";
   else if (m > h->cfg.max_games) bad = "m > max_games";
-  if (bad) {
-    h->err = std::string("monsoon_env_load_dev: ") + bad;
-    return MONSOON_ERR_ARG;
-  }
+  if (bad) return bad_arg(h, "monsoon_env_load_dev", bad);
   if (m == 0) return MONSOON_OK;
   HIP_TRY(h, bind_device(h));
   uint8_t* flags = loaded_dev ? loaded_dev : h->d_snap_flag;
   monsoon_env_snap_ops()->load(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, n_entries, src_dev, dst_dev, m, flags,
                                (uint32_t)monsoon_version());
-  hipLaunchKernelGGL(k_env_view, dim3((m + API_LANES - 1) / API_LANES), dim3(64), API_LDS_BYTES, h->stream, h->b, h->env, m, dst_dev, flags);
+  LAUNCH_LANES(h, k_env_view, m, h->b, h->env, m, dst_dev, flags);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
 }
