@@ -74,16 +74,23 @@ class BatchEngine:
         _lib.check(self.h, rc, what, self.lib)
 
     # ---- Seam G, batched ------------------------------------------------------------------
+    @staticmethod
+    def _decks_factions(n, decks, factions):
+        """decks as uint8[n][2][12] (one [2][12] pair stands for all n) and factions as uint8[n][2]; None stays None."""
+        if decks is not None:
+            decks = np.ascontiguousarray(decks, dtype=np.uint8)
+            if decks.shape == (2, 12):
+                decks = np.broadcast_to(decks, (n, 2, 12)).copy()
+            if decks.shape != (n, 2, 12):
+                raise ValueError(f"decks must be [n][2][12], got {decks.shape}")
+        if factions is not None:
+            factions = np.ascontiguousarray(factions, dtype=np.uint8).reshape(n, 2)
+        return decks, factions
+
     def reset(self, seeds, decks, factions=None):
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         n = len(seeds)
-        decks = np.ascontiguousarray(decks, dtype=np.uint8)
-        if decks.shape == (2, 12):
-            decks = np.broadcast_to(decks, (n, 2, 12)).copy()
-        if decks.shape != (n, 2, 12):
-            raise ValueError(f"decks must be [n][2][12], got {decks.shape}")
-        if factions is not None:
-            factions = np.ascontiguousarray(factions, dtype=np.uint8).reshape(n, 2)
+        decks, factions = self._decks_factions(n, decks, factions)
         self._ck(self.lib.monsoon_reset(self.h, n, _ptr(seeds), _ptr(decks), _ptr(factions)), "monsoon_reset")
         self.n = n
 
@@ -216,14 +223,7 @@ class BatchEngine:
         decks[n][2][12] (None with a pool), factions[n][2] or None.  Synchronises."""
         seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
         n = len(seed0)
-        if decks is not None:
-            decks = np.ascontiguousarray(decks, dtype=np.uint8)
-            if decks.shape == (2, 12):
-                decks = np.broadcast_to(decks, (n, 2, 12)).copy()
-            if decks.shape != (n, 2, 12):
-                raise ValueError(f"decks must be [n][2][12], got {decks.shape}")
-        if factions is not None:
-            factions = np.ascontiguousarray(factions, dtype=np.uint8).reshape(n, 2)
+        decks, factions = self._decks_factions(n, decks, factions)
         self._ck(self.lib.monsoon_env_reset(self.h, ctypes.byref(config), ctypes.byref(views), n, _ptr(seed0), _ptr(decks),
                                             _ptr(factions)), "monsoon_env_reset")
         self.n = n
@@ -317,18 +317,8 @@ class BatchEngine:
     def rollout_logged(self, weights, matches, deck_pairs, max_turns, scores=True, n_legal=True):
         """monsoon_rollout_logged: rollout_vs_expert (the bot's rows included) that also writes down every committed step.
         Returns (counts, results, steps, log), log a RolloutLog whose score / n_legal are None where not asked for."""
-        weights, m, deck_pairs = self._rollout_args(weights, matches, deck_pairs)
-        counts = np.zeros((len(weights), 3), dtype=np.int32)
-        results = np.zeros(len(m), dtype=np.int8)
-        log = RolloutLog.empty(len(m), max_turns, scores, n_legal)
-        c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
-        self._ck(self.lib.monsoon_rollout_logged(self.h, _ptr(weights), len(weights), _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
-                                                 max_turns, _ptr(counts), _ptr(results), _ptr(log.steps), ctypes.byref(c_log)),
-                 "monsoon_rollout_logged")
-        # the handle now holds the last batch of the schedule; a logged call's batches are cut by the log's budget too
-        batch = min(self.max_games, max(1, LOG_BUDGET // (11 * max_turns)))
-        self.n = len(m) - ((len(m) - 1) // batch) * batch
-        return counts, results, log.steps, log
+        log = RolloutLog.empty(len(matches), max_turns, scores, n_legal)
+        return self._rollout("monsoon_rollout_logged", weights, matches, deck_pairs, max_turns, True, log) + (log,)
 
     @staticmethod
     def _rollout_args(weights, matches, deck_pairs):
@@ -342,16 +332,22 @@ class BatchEngine:
             m = arr
         return weights, m, deck_pairs
 
-    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results):
+    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results, log=None):
+        """One rollout entry of the library.  log: the RolloutLog that monsoon_rollout_logged fills, one row per match (its
+        steps are the call's steps)."""
         weights, m, deck_pairs = self._rollout_args(weights, matches, deck_pairs)
         n_ind = weights.shape[0]
         counts = np.zeros((n_ind, 3), dtype=np.int32)
         results = np.zeros(len(m), dtype=np.int8) if want_results else None
-        steps = np.zeros(len(m), dtype=np.int32) if want_results else None
+        steps = log.steps if log is not None else np.zeros(len(m), dtype=np.int32) if want_results else None
+        extra, batch = (), self.max_games
+        if log is not None:
+            c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
+            extra = (ctypes.byref(c_log),)
+            batch = min(batch, max(1, LOG_BUDGET // (11 * max_turns)))   # a logged call's batches are cut by the log's budget too
         self._ck(getattr(self.lib, entry)(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
-                                          max_turns, _ptr(counts), _ptr(results), _ptr(steps)), entry)
-        # the handle now holds the last batch of the schedule
-        self.n = len(m) - ((len(m) - 1) // self.max_games) * self.max_games
+                                          max_turns, _ptr(counts), _ptr(results), _ptr(steps), *extra), entry)
+        self.n = len(m) - ((len(m) - 1) // batch) * batch   # the handle now holds the last batch of the schedule
         return (counts, results, steps) if want_results else counts
 
     def rollout_faults(self, n_matches):

@@ -17,7 +17,7 @@ import time
 
 import numpy as np
 
-MATCH_DTYPE = np.dtype([("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", "<u4")])
+from .engine import MATCH_DTYPE  # noqa: F401  (defined once, next to the C ABI; engine.py needs no torch either)
 
 
 def hash32(*vals):
@@ -95,6 +95,18 @@ def match_wins(matches, results):
     return np.asarray(results) == np.where(matches["p1"] >= 0, 0, 1)
 
 
+def bot_plays(matches):
+    """True if the scripted bot is a side of any match: such a schedule is monsoon_rollout_vs_expert's."""
+    return bool(((matches["p1"] < 0) | (matches["p2"] < 0)).any())
+
+
+def mirrored_pair(deck):
+    """One deck (12 card ids or a DECKS key) on both sides, as a one-pair table uint8[1][2][12]."""
+    from .cards import deck_indices
+    deck = deck_indices(deck)
+    return np.stack([deck, deck])[None]
+
+
 def _uncount(counts, matches, results):
     """Take the given matches, with the results they had, out of counts[n][3]."""
     rows = match_rows(matches)
@@ -132,42 +144,43 @@ def record_limited(faults):
     return (faults >= CAPACITY_CODE) & (faults != DEPTH_CODE)
 
 
+def _replace_rows(counts, results, steps, faults, matches, idx, played, counted=True):
+    """Rows idx of a rollout become `played` = (counts, results, steps, faults) of matches[idx]: the games are taken out
+    of counts[n][3] with the results they had (counted False: they were not played before) and counted anew.  In place."""
+    c, r, s, f = played
+    if counted:
+        _uncount(counts, matches[idx], results[idx])
+    counts += np.asarray(c, dtype=counts.dtype)
+    results[idx], steps[idx], faults[idx] = r, s, f
+
+
 def replace_capacity_faulted(counts, results, steps, faults, matches, replay):
-    """The games of a rollout that hit a limit of the record (fault code >= 16: the reference's deep copies nest without
-    bound, a record does not) are played again by `replay(sub_matches) -> (counts, results, steps, faults)` -- the same
-    games on the build with the larger record -- and the rows of the first attempt replaced.  Returns the number of
-    games replayed; the arrays are updated in place."""
+    """The two-record form for callers of the C ABI: the games of a rollout that hit a limit of the record (fault code
+    >= 16: the reference's deep copies nest without bound, a record does not) are played again by `replay(sub_matches) ->
+    (counts, results, steps, faults)` -- the same games on the build with the larger record -- and the rows of the first
+    attempt replaced.  Returns the number of games replayed; the arrays are updated in place.
+
+    Its rule is NOT the ladder's record_limited: it takes every code >= CAPACITY_CODE, the recursion guard's DEPTH_CODE
+    (18) among them, which the ladder never replays (the guard is the same on every record: the replay ends as it did)."""
     bad = np.nonzero(faults >= CAPACITY_CODE)[0]
-    if len(bad) == 0:
-        return 0
-    c2, r2, s2, f2 = replay(matches[bad])
-    _uncount(counts, matches[bad], results[bad])
-    counts += np.asarray(c2, dtype=counts.dtype)
-    results[bad], steps[bad], faults[bad] = r2, s2, f2
+    if len(bad):
+        _replace_rows(counts, results, steps, faults, matches, bad, replay(matches[bad]))
     return len(bad)
 
 
-def tiered_rollout(play, n_rows, matches, deck_pairs, concurrent=False):
-    """A schedule played on the smallest record each game needs.  play(tier, sub_matches, sub_deck_pairs) ->
-    (counts[n_rows][3], results, steps, faults) runs matches on one build (tier 0 standard, 1 extended, 2 large record);
-    it is handed only the deck pairs its matches name (a build refuses a table holding a card it does not support).
-
-    Tier per GAME, not per call: only a deck pair holding ua20 / b005 needs the extended record (2 400 bytes against
-    752: the hot kernel runs half as many wavefronts with half as many candidate lanes on it), so a schedule of random
-    109-card decks -- 37 % of whose games hold one of the two -- is split in two sub-schedules.  Then the ladder: games
-    that hit a limit of their record (fault code >= 16) are played again on the next larger one and their rows replaced
-    (nested b005 memories are deep copies of the whole game, cards/b005.py:14-33, card.py:71-75: the reference's copies
-    nest without bound, a record does not).  concurrent: the standard and the extended sub-schedule are played from two
-    host threads (two handles, a stream each: the wavefronts of one fill the GPU while the other's batch drains or its
-    host side works).  Returns (counts, results, steps, faults, replays, tier_sizes)."""
+def _ladder(play, n_rows, matches, deck_pairs, concurrent=False, put=None):
+    """The tier ladder, once: the tier of each game, the first pass, the climb and the replacement of rows.
+    play(tier, sub_matches, sub_deck_pairs) -> (counts[n_rows][3], results, steps, faults), with a fifth item where put
+    is given: a payload per row of the call, placed by put(rows, payload) (a replayed game's payload is that of the last
+    tier that played it).  Returns (counts, results, steps, faults, replays, tier_sizes)."""
     from .cards import needs_extended_each
     matches = np.asarray(matches)
     deck_pairs = np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12)
     ext_pair = needs_extended_each(deck_pairs)
 
-    def run(t, sub):
-        used, inv = np.unique(sub["deck"], return_inverse=True)
-        sub = sub.copy()
+    def run(t, idx):   # a call is handed only the deck pairs its matches name
+        used, inv = np.unique(matches["deck"][idx], return_inverse=True)
+        sub = matches[idx].copy()
         sub["deck"] = inv
         return play(t, sub, deck_pairs[used])
     tier = ext_pair[matches["deck"]].astype(np.int8) if len(ext_pair) > 1 else np.full(len(matches), int(ext_pair[0]), dtype=np.int8)
@@ -176,29 +189,44 @@ def tiered_rollout(play, n_rows, matches, deck_pairs, concurrent=False):
     steps = np.zeros(len(matches), dtype=np.int32)
     faults = np.zeros(len(matches), dtype=np.uint8)
     first = [np.nonzero(tier == t)[0] for t in (0, 1)]
-    sizes = [len(idx) for idx in first]
     todo = [(t, idx) for t, idx in enumerate(first) if len(idx)]
     if concurrent and len(todo) == 2:
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=2) as pool:
-            done = list(pool.map(lambda ti: run(ti[0], matches[ti[1]]), todo))
+            done = list(pool.map(lambda ti: run(*ti), todo))
     else:
-        done = [run(t, matches[idx]) for t, idx in todo]
-    for (t, idx), (c, r, s_, f) in zip(todo, done):
-        counts += np.asarray(c, dtype=np.int64)
-        results[idx], steps[idx], faults[idx] = r, s_, f
+        done = [run(t, idx) for t, idx in todo]
+
+    def place(t, idx, played, counted):
+        _replace_rows(counts, results, steps, faults, matches, idx, played[:4], counted)
+        tier[idx] = t
+        if put is not None:
+            put(idx, played[4])
+    for (t, idx), played in zip(todo, done):
+        place(t, idx, played, False)
     replays = 0
     for t in (1, 2):   # standard -> extended -> large
         bad = np.nonzero(record_limited(faults) & (tier < t))[0]
-        if not len(bad):
-            continue
-        replays += len(bad)
-        c2, r2, s2, f2 = run(t, matches[bad])
-        _uncount(counts, matches[bad], results[bad])
-        counts += np.asarray(c2, dtype=np.int64)
-        results[bad], steps[bad], faults[bad] = r2, s2, f2
-        tier[bad] = t
-    return counts, results, steps, faults, replays, sizes
+        if len(bad):
+            replays += len(bad)
+            place(t, bad, run(t, bad), True)
+    return counts, results, steps, faults, replays, [len(idx) for idx in first]
+
+
+def tiered_rollout(play, n_rows, matches, deck_pairs, concurrent=False):
+    """A schedule played on the smallest record each game needs (_ladder).  play(tier, sub_matches, sub_deck_pairs) ->
+    (counts[n_rows][3], results, steps, faults) runs matches on one build (tier 0 standard, 1 extended, 2 large record);
+    it is handed only the deck pairs its matches name (a build refuses a table holding a card it does not support).
+
+    Tier per GAME, not per call: only a deck pair holding ua20 / b005 needs the extended record (2 400 bytes against
+    752: the hot kernel runs half as many wavefronts with half as many candidate lanes on it), so a schedule of random
+    109-card decks -- 37 % of whose games hold one of the two -- is split in two sub-schedules.  Then the ladder: games
+    that hit a limit of their record (record_limited) are played again on the next larger one and their rows replaced
+    (nested b005 memories are deep copies of the whole game, cards/b005.py:14-33, card.py:71-75: the reference's copies
+    nest without bound, a record does not).  concurrent: the standard and the extended sub-schedule are played from two
+    host threads (two handles, a stream each: the wavefronts of one fill the GPU while the other's batch drains or its
+    host side works).  Returns (counts, results, steps, faults, replays, tier_sizes)."""
+    return _ladder(play, n_rows, matches, deck_pairs, concurrent)
 
 
 class FitnessEvaluator:
@@ -246,18 +274,16 @@ class FitnessEvaluator:
             eng = self._engine(0)
             # one decision of as many games as fill the GPU: loads the code objects and makes the runtime size the
             # launch-time buffers (work-stack overflow blocks, the queue's scratch) for a full grid -- 0.8 s the first time
-            from .cards import deck_indices
-            d = deck_indices("N12M")
             n = min(self.config.max_concurrent_games, 8192)
             m = np.zeros(n, dtype=MATCH_DTYPE)
             m["seed"] = np.arange(n)
-            eng.rollout(np.zeros((1, 10)), m, np.stack([d, d])[None], 1)
+            eng.rollout(np.zeros((1, 10)), m, mirrored_pair("N12M"), 1)
             eng.reset_stats()
 
     def _hip_rollout(self, weights, matches, deck_pairs, max_turns):
         import threading
         lock = threading.Lock()
-        vs_expert = bool(((matches["p1"] < 0) | (matches["p2"] < 0)).any())   # the scripted bot plays: monsoon_rollout_vs_expert
+        vs_expert = bot_plays(matches)
 
         def play(tier, sub, sub_pairs):
             eng = self._engine(tier)
@@ -292,20 +318,30 @@ class FitnessEvaluator:
         champion played, step by step.  deck_pairs None: config.deck on both sides.  Returns (counts, results, steps,
         faults, log); the evaluator's statistics are left alone."""
         from .game_log import logged_rollout
-        matches = np.asarray(matches)
         if deck_pairs is None:
-            from .cards import deck_indices
-            deck = deck_indices(self.config.deck)
-            deck_pairs = np.stack([deck, deck])[None]
-        return logged_rollout(self._engine, np.asarray(weights, dtype=np.float64), matches, deck_pairs, self.config.max_turns)
+            deck_pairs = mirrored_pair(self.config.deck)
+        return logged_rollout(self._engine, np.asarray(weights, dtype=np.float64), np.asarray(matches), deck_pairs, self.config.max_turns)
 
-    def _decks_for(self, matches, generation, tag=1):
-        """Deck pairs [n_decks][2][12] for a schedule; fills matches["deck"].  Without a deck_config: config.deck both
-        sides.  With one: utils.py:155-219 per GAME, as games/evolutionary_stormbound.py:52 draws them (one pair for
-        the whole generation while the schedule is in its exploit phase).  tag: the stream tag of a per-game deck_config
-        (decks.TAG_POPULATION / TAG_EXPERT), unused otherwise."""
+    def _deck_source(self):
+        """Where this evaluator's decks come from: its DeckEvolutionConfig, else config.deck (a DECKS key or RANDOM_DECK)."""
+        return self.config.deck if self.deck_config is None else self.deck_config
+
+    @staticmethod
+    def _seed_keyed(source):
+        """True for a deck source whose per-game decks depend on the game's seed alone: configuration C5 and a per_game schedule."""
+        from .cards import RANDOM_DECK
+        return bool(getattr(source, "per_game", False)) or (isinstance(source, str) and source == RANDOM_DECK)
+
+    def _decks_for(self, matches, generation, tag=1, source=None):
+        """Deck pairs [n_decks][2][12] for a schedule; fills matches["deck"].  source (None: _deck_source(), the
+        evaluator's own) is a deck for both sides as config.deck names one, RANDOM_DECK among them, or a
+        DeckEvolutionConfig: utils.py:155-219 per GAME, as games/evolutionary_stormbound.py:52 draws them (one pair for
+        the whole generation while the schedule is in its exploit phase).  tag: the stream tag of a per-game
+        DeckEvolutionConfig (decks.TAG_POPULATION / TAG_EXPERT), unused otherwise."""
         from .cards import C5_STREAM_XOR, RANDOM_DECK, deck_indices, draw_random_decks_numpy, observable_pool
-        if self.deck_config is None and self.config.deck == RANDOM_DECK:
+        if source is None:
+            source = self._deck_source()
+        if isinstance(source, str) and source == RANDOM_DECK:
             # configuration C5: two decks per game from the 109 observable cards, drawn by the game's own pre-stream
             pre = matches["seed"] ^ np.uint32(C5_STREAM_XOR)
             matches["deck"] = np.arange(len(matches))
@@ -314,28 +350,27 @@ class FitnessEvaluator:
             if self._rollout_fn is not None:   # CPU stand-in (tests): numpy itself
                 return draw_random_decks_numpy(pre)
             return self._engine(0).draw_decks(pre, observable_pool())
-        if self.deck_config is None:
-            deck = deck_indices(self.config.deck)
-            return np.stack([deck, deck])[None]
-        if self.deck_config.is_static(generation):
-            d1, d2 = self.deck_config.get_deck_configuration(generation)
+        if not hasattr(source, "get_deck_configuration"):
+            return mirrored_pair(source)
+        if source.is_static(generation):
+            d1, d2 = source.get_deck_configuration(generation)
             return np.stack([deck_indices(d1), deck_indices(d2)])[None]
         matches["deck"] = np.arange(len(matches))
         pairs = np.zeros((len(matches), 2, 12), dtype=np.uint8)
-        if self.deck_config.per_game:
+        if source.per_game:
             # every game draws from a stream of its own (decks.game_decks): on the device, unless a stand-in plays the games
             # or the schedule is one the device entry does not take (schedule_params is None: the host draw stays)
-            params = self.deck_config.schedule_params(generation, tag)
+            params = source.schedule_params(generation, tag)
             if params is not None and self._schedule_draw_fn is not None:
                 return self._schedule_draw_fn(params, matches["seed"])
             if params is not None and self._rollout_fn is None:
                 return self._engine(0).draw_schedule(params, matches["seed"])
             for k, seed in enumerate(matches["seed"]):
-                d1, d2 = self.deck_config.game_decks(generation, seed, tag)
+                d1, d2 = source.game_decks(generation, seed, tag)
                 pairs[k, 0], pairs[k, 1] = deck_indices(d1), deck_indices(d2)
             return pairs
         for k in range(len(matches)):
-            d1, d2 = self.deck_config.get_deck_configuration(generation)
+            d1, d2 = source.get_deck_configuration(generation)
             pairs[k, 0], pairs[k, 1] = deck_indices(d1), deck_indices(d2)
         return pairs
 
@@ -350,8 +385,47 @@ class FitnessEvaluator:
         return None
 
     # -- Seam F ------------------------------------------------------------------------------
+    def _play_schedule(self, matches, weights, n_rows, generation, tag, source, counted):
+        """One schedule, evaluated: this rank's shard of it (by row individual, of n_rows), its decks from `source`
+        (_decks_for) under stream tag `tag`, the rollout, and the one all-reduce.  Returns counts[len(weights)][3] of the
+        whole job.  counted: the games' look-ahead steps and decisions go to the statistics -- total_* on this rank,
+        job_* summed over ranks, riding as a last row of the counts tensor; else total_* end as they began."""
+        source = self._deck_source() if source is None else source
+        dist = self._dist()
+
+        def shard(m):
+            return m if dist is None else shard_by_individual(m, n_rows, dist.get_rank(), dist.get_world_size())
+        if self._seed_keyed(source):
+            # per-game decks that depend on the game's seed alone: every rank draws only the games it plays
+            mine = shard(matches)
+            if dist is not None:
+                mine = mine.copy()
+            deck_pairs = self._decks_for(mine, generation, tag, source) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
+        else:
+            # one pair for all, or a sequential stream (utils.py:155-219): drawn for the WHOLE schedule, so every rank sees the same decks
+            deck_pairs = self._decks_for(matches, generation, tag, source)
+            mine = shard(matches)
+            if dist is not None and len(deck_pairs) > 1 and len(mine):   # keep only this rank's decks
+                deck_pairs = deck_pairs[mine["deck"]]
+                mine = mine.copy()
+                mine["deck"] = np.arange(len(mine))
+        fn = self._rollout_fn or self._hip_rollout
+        counts = np.zeros((len(weights), 3), dtype=np.int64)
+        before = self.total_env_steps, self.total_decisions   # the rollout, or its stand-in, adds its games to these
+        if len(mine):
+            counts += np.asarray(fn(weights, mine, deck_pairs, self.config.max_turns), dtype=np.int64)
+        played = [self.total_env_steps - before[0], self.total_decisions - before[1], 0]
+        if not counted:
+            self.total_env_steps, self.total_decisions = before
+            return counts if dist is None else self._all_reduce_counts(dist, counts)
+        if dist is not None:
+            # this rank's env-steps and decisions ride along as one more row: still one collective per evaluation
+            counts, played = self._all_reduce_counts(dist, counts, played)
+        self.job_env_steps += int(played[0])
+        self.job_decisions += int(played[1])
+        return counts
+
     def evaluate_population(self, population, generation=0):
-        from .cards import deck_indices
         cfg = self.config
         n = len(population)
         opponents = list(population)
@@ -371,34 +445,9 @@ class FitnessEvaluator:
             np.add.at(counts[:, 0], matches["p1"], 1)
             np.add.at(counts[:, 2], matches["p1"], 1)
         else:
+            from .decks import TAG_POPULATION
             weights = np.stack([np.asarray(o.weights, dtype=np.float64) for o in opponents])
-            from .cards import RANDOM_DECK
-            dist = self._dist()
-            mine = matches
-            if (self.deck_config is None and cfg.deck == RANDOM_DECK) or (self.deck_config is not None and self.deck_config.per_game):
-                # per-game decks that depend on the game's seed alone: every rank draws only the games it plays
-                if dist is not None:
-                    mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size()).copy()
-                deck_pairs = self._decks_for(mine, generation) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
-            else:
-                deck_pairs = self._decks_for(matches, generation)   # a sequential stream (utils.py:155-219): drawn for the WHOLE schedule, so every rank sees the same decks
-                if dist is not None:
-                    mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size())
-                    if len(deck_pairs) > 1 and len(mine):   # keep only this rank's decks
-                        deck_pairs = deck_pairs[mine["deck"]]
-                        mine = mine.copy()
-                        mine["deck"] = np.arange(len(mine))
-            fn = self._rollout_fn or self._hip_rollout
-            counts = np.zeros((n_total, 3), dtype=np.int64)
-            before = self.total_env_steps, self.total_decisions
-            if len(mine):
-                counts += np.asarray(fn(weights, mine, deck_pairs, cfg.max_turns), dtype=np.int64)
-            played = [self.total_env_steps - before[0], self.total_decisions - before[1], 0]
-            if dist is not None:
-                # this rank's env-steps and decisions ride along as one more row: still one collective per evaluation
-                counts, played = self._all_reduce_counts(dist, counts, played)
-            self.job_env_steps += int(played[0])
-            self.job_decisions += int(played[1])
+            counts = self._play_schedule(matches, weights, n, generation, TAG_POPULATION, None, True)
         self.total_games += len(matches)
         self.total_time += time.time() - start
         self.eval_times.append(time.time() - start)
@@ -415,41 +464,21 @@ class FitnessEvaluator:
         evaluate_population returns does not depend on whether this was called.  In a random phase of a deck schedule the
         games play the schedule's own decks if it is a per_game=True one (stream tag 2), random109 decks otherwise."""
         from .cards import RANDOM_DECK
-        cfg = self.config
+        from .decks import TAG_EXPERT
         n = len(population)
-        games = int(cfg.expert_eval_games if games_per_individual is None else games_per_individual)
+        games = int(self.config.expert_eval_games if games_per_individual is None else games_per_individual)
         if games <= 0:
             raise ValueError("games_per_individual must be positive")
         matches = expert_schedule(n, games, generation, sides)
         weights = np.stack([np.asarray(o.weights, dtype=np.float64) for o in population])
-        dist = self._dist()
-        mine = matches
-        if dist is not None:
-            mine = shard_by_individual(matches, n, dist.get_rank(), dist.get_world_size()).copy()
-        from .decks import TAG_EXPERT
-        detour = self.deck_config is not None and not self.deck_config.is_static(generation) and not self.deck_config.per_game
-        if detour:
-            # The random phase of a sequential DeckEvolutionConfig draws every game's decks from ONE stream: drawing from it
-            # here would change the decks of the next evaluate_population.  These games take their decks as configuration C5
-            # does instead, each from its own seed's pre-stream.  (A per_game=True schedule has no such stream: its games
-            # play the schedule's own decks, drawn with the stream tag of this call.)
-            deck_config, deck, self.deck_config = self.deck_config, cfg.deck, None
-            cfg.deck = RANDOM_DECK
-        try:
-            deck_pairs = self._decks_for(mine, generation, TAG_EXPERT) if len(mine) else np.zeros((1, 2, 12), dtype=np.uint8)
-        finally:
-            if detour:
-                self.deck_config, cfg.deck = deck_config, deck
-        fn = self._rollout_fn or self._hip_rollout
-        counts = np.zeros((n, 3), dtype=np.int64)
-        if len(mine):
-            keep = self.total_env_steps, self.total_decisions
-            counts += np.asarray(fn(weights, mine, deck_pairs, cfg.max_turns), dtype=np.int64)
-            self.total_env_steps, self.total_decisions = keep
-        if dist is not None:
-            counts = self._all_reduce_counts(dist, counts)
-        self.last_vs_expert = counts
-        return fitness_from_counts(counts, games)
+        # The random phase of a sequential DeckEvolutionConfig draws every game's decks from ONE stream: drawing from it
+        # here would change the decks of the next evaluate_population.  These games take their decks as configuration C5
+        # does instead, each from its own seed's pre-stream.  (A per_game=True schedule has no such stream: its games
+        # play the schedule's own decks, drawn with the stream tag of this call.)
+        dc = self.deck_config
+        detour = dc is not None and not dc.is_static(generation) and not dc.per_game
+        self.last_vs_expert = self._play_schedule(matches, weights, n, generation, TAG_EXPERT, RANDOM_DECK if detour else None, False)
+        return fitness_from_counts(self.last_vs_expert, games)
 
     @staticmethod
     def _all_reduce_counts(dist, counts, extra=None):

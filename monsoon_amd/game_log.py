@@ -7,47 +7,23 @@ step interface and yields the (state, action) pairs a learner wants.
 import numpy as np
 
 from .engine import RolloutLog
-from .fitness import _uncount, record_limited
+from .fitness import _ladder, bot_plays
 
 
 def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns):
     """A schedule played on the smallest record each game needs, with its log.  engine_for_tier(tier) is the engine of a
     record (0 standard, 1 extended, 2 large): anything with BatchEngine's rollout_logged and rollout_faults.  The rule is
-    fitness.tiered_rollout's: a deck pair holding ua20 / b005 starts on the extended record, a game that ends on a limit of
-    its record (fitness.record_limited) is played again on the next larger one, and its rows -- the log's among them -- are
-    replaced.  An engine is handed only the deck pairs its sub-schedule names.
+    fitness.tiered_rollout's, the same function (fitness._ladder): a deck pair holding ua20 / b005 starts on the extended
+    record, a game that ends on a limit of its record (fitness.record_limited) is played again on the next larger one, and
+    its rows -- the log's among them -- are replaced.  An engine is handed only the deck pairs its sub-schedule names.
     Returns (counts[n_rows][3], results, steps, faults, log)."""
-    from .cards import needs_extended_each
-    matches = np.asarray(matches)
-    deck_pairs = np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12)
-    n = len(matches)
-    tier = needs_extended_each(deck_pairs)[matches["deck"]].astype(np.int8)
-    counts = np.zeros((len(weights), 3), dtype=np.int64)
-    results, steps, faults = np.zeros(n, dtype=np.int8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
-    log = RolloutLog.empty(n, max_turns)
+    log = RolloutLog.empty(len(matches), max_turns)
 
-    def run(t, idx, first):
-        used, inv = np.unique(matches["deck"][idx], return_inverse=True)
-        sub = matches[idx].copy()
-        sub["deck"] = inv
+    def play(t, sub, sub_pairs):
         eng = engine_for_tier(t)
-        c, r, s, lg = eng.rollout_logged(weights, sub, deck_pairs[used], max_turns)
-        if not first:
-            _uncount(counts, matches[idx], results[idx])
-        counts[:] += np.asarray(c, dtype=np.int64)
-        results[idx], steps[idx], faults[idx] = r, s, eng.rollout_faults(len(idx))
-        log.put(idx, lg)
-        tier[idx] = t
-
-    for t in (0, 1):
-        idx = np.nonzero(tier == t)[0]
-        if len(idx):
-            run(t, idx, True)
-    for t in (1, 2):   # standard -> extended -> large
-        bad = np.nonzero(record_limited(faults) & (tier < t))[0]
-        if len(bad):
-            run(t, bad, False)
-    return counts, results, steps, faults, log
+        c, r, s, lg = eng.rollout_logged(weights, sub, sub_pairs, max_turns)
+        return c, r, s, eng.rollout_faults(len(sub)), lg
+    return _ladder(play, len(weights), matches, deck_pairs, put=log.put)[:4] + (log,)
 
 
 def replay(engine, matches, deck_pairs, log):
@@ -61,7 +37,7 @@ def replay(engine, matches, deck_pairs, log):
     the bot's choice draws from the game's own stream (expert_action consumes it), which step alone does not reproduce,
     so such a game cannot be replayed from its actions."""
     matches = np.asarray(matches)
-    if ((matches["p1"] < 0) | (matches["p2"] < 0)).any():
+    if bot_plays(matches):
         raise ValueError("replay: a match with the scripted bot cannot be replayed from its actions (the bot draws from the game's stream)")
     deck_pairs = np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 2, 12)
     n = len(matches)

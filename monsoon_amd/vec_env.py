@@ -10,6 +10,7 @@ Episode decks come from the reset decks, from a pool, or from a deck schedule (`
 exploit / explore / balance curriculum, drawn on the device per episode; `set_deck_schedule` moves its generation).
 torch is used for device memory and stream ordering only; there is no CPU fallback.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -139,7 +140,6 @@ class VecEnv:
         stay those of `factions` (episode 0 only, as ever).  Every faction's pool holds ua20 and Shadowfen's b005, so a
         schedule made from a config needs VecEnv(extended=1) once it draws (explore and balance phases): on the standard
         build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised."""
-        import torch
         if opponent not in OPPONENTS:
             raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
         seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
@@ -176,9 +176,7 @@ class VecEnv:
             self.views = self._alloc(n)
         self.n = n
         views = EnvViews(**{name: t.data_ptr() for name, t in self.views.items()})
-        # the views may still be read by work queued on torch's stream
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        try:
+        with self._after_torch_stream():
             if opp is not None:
                 self.engine.env_set_opponents(opp[0], opp[1], n)
             self._heuristic = False
@@ -188,9 +186,19 @@ class VecEnv:
             self.engine.env_reset(cfg, views, seed0, decks, factions)
             self._heuristic = opp is not None
             self._schedule = deck_schedule
+        return self.views
+
+    @contextlib.contextmanager
+    def _after_torch_stream(self):
+        """The bracket of the synchronising setters (reset, set_opponents, set_deck_schedule): the env's stream waits for
+        torch's current one -- the views may still be read by work queued there -- and torch's waits for the env's when the
+        body is left, also by an exception.  Unconditional, unlike _on_env_stream's."""
+        import torch
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        try:
+            yield
         finally:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        return self.views
 
     @staticmethod
     def _opponents(weights, rows, n):
@@ -211,15 +219,11 @@ class VecEnv:
     def set_opponents(self, weights, rows=None):
         """A league update between steps: the heuristic opponents' weights ([10] or [k][10]; k at most the k given to
         reset) and each slot's row (None = row 0).  They apply from the next step; a captured step graph stays valid."""
-        import torch
         if not self._heuristic:
             raise MonsoonError('VecEnv.set_opponents needs reset(opponent="heuristic", ...) first')
         w, r = self._opponents(weights, rows, self.n)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        try:
+        with self._after_torch_stream():
             self.engine.env_set_opponents(w, r, self.n)
-        finally:
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
     @staticmethod
     def _schedule_params(deck_schedule, generation):
@@ -235,16 +239,12 @@ class VecEnv:
         the one given to reset) between steps: every episode that starts from the next step on draws from it, running
         episodes keep their decks, a captured step graph stays valid.  MonsoonError if the env was not reset with a
         deck_schedule.  Synchronises the env's stream."""
-        import torch
         if self._schedule is None:
             raise MonsoonError("VecEnv.set_deck_schedule needs reset(deck_schedule=...) first")
         new = self._schedule if deck_schedule is None else deck_schedule
         params = self._schedule_params(new, generation)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        try:
+        with self._after_torch_stream():
             self.engine.env_set_schedule(params)
-        finally:
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
         self._schedule = new
 
     def decks(self):
@@ -270,13 +270,7 @@ class VecEnv:
         if not isinstance(actions, torch.Tensor) or actions.dtype != torch.uint8 or not actions.is_cuda or actions.shape != (self.n,):
             raise ValueError(f"actions must be a uint8 CUDA tensor of shape ({self.n},)")
         actions = actions.contiguous()
-        cur = torch.cuda.current_stream(self.device)
-        env = self.stream
-        if cur.cuda_stream != env.cuda_stream:
-            env.wait_stream(cur)   # the actions were written on torch's stream
-        self.engine.env_step_dev(actions.data_ptr())
-        if cur.cuda_stream != env.cuda_stream:
-            cur.wait_stream(env)
+        self._on_env_stream(lambda: self.engine.env_step_dev(actions.data_ptr()))
         return self.views
 
     def afterstates(self, max_after=64, obs=True):
@@ -308,13 +302,7 @@ class VecEnv:
             t["action"].fill_(255)
             self._after[obs] = ((self.n, max_after), t, EnvAfter(**{name: x.data_ptr() for name, x in t.items()}))
         _, tensors, struct = self._after[obs]
-        cur = torch.cuda.current_stream(self.device)
-        env = self.stream
-        if cur.cuda_stream != env.cuda_stream:
-            env.wait_stream(cur)   # the tensors may still be read by work queued on torch's stream
-        self.engine.env_afterstates_dev(struct, max_after)
-        if cur.cuda_stream != env.cuda_stream:
-            cur.wait_stream(env)
+        self._on_env_stream(lambda: self.engine.env_afterstates_dev(struct, max_after))
         return tensors
 
     @property
@@ -333,11 +321,13 @@ class VecEnv:
         return t.contiguous(), int(t.shape[0])
 
     def _on_env_stream(self, call):
+        """call(), a launch on the env's stream, ordered against torch's current stream on both sides -- unless that IS the
+        env's stream (a step captured on it): then nothing waits, which is what lets single-stream capture work."""
         import torch
         cur = torch.cuda.current_stream(self.device)
         env = self.stream
         if cur.cuda_stream != env.cuda_stream:
-            env.wait_stream(cur)   # the index tensors were written, the entries may still be read, on torch's stream
+            env.wait_stream(cur)   # the call's inputs were written, its outputs may still be read, on torch's stream
         call()
         if cur.cuda_stream != env.cuda_stream:
             cur.wait_stream(env)

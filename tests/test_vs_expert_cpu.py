@@ -136,29 +136,77 @@ def test_evaluate_vs_expert_is_the_model_game_by_game():
     assert ev.evaluate_vs_expert(pop, 2, games_per_individual=6, sides="first") != [] and (ev.last_vs_expert[:, 2] == 6).all()
 
 
+def _both(w, m, d, t):
+    """A rollout_fn that serves both kinds of schedule."""
+    from oracle_rollout import oracle_rollout_fn
+    return (M.vs_expert_rollout_fn if (np.asarray(m)["p1"] < 0).any() or (np.asarray(m)["p2"] < 0).any() else oracle_rollout_fn)(w, m, d, t)
+
+
+def _explore():
+    """Generation 3 / 4 of this schedule are in its explore phase: a deck pair per game from one seeded stream."""
+    from monsoon_amd.cards import DECKS
+    from monsoon_amd.decks import DeckEvolutionConfig
+    return DeckEvolutionConfig(DECKS["IRONCLAD"], DECKS["SWARM"], exploit_generations=1, explore_generations=6, seed=9)
+
+
+def _two_generations(with_bot, deck_config, ev=None):
+    """evaluate_population of generations 3 and 4, with an evaluate_vs_expert call in between or not: what the GA sees."""
+    if ev is None:
+        ev = FitnessEvaluator(_config(), deck_config() if deck_config else None, rollout_fn=_both)
+    pop = _population()
+    out = [ev.evaluate_population(pop, generation=3)]
+    if with_bot:
+        ev.evaluate_vs_expert(pop, generation=3, games_per_individual=2)
+    out.append(ev.evaluate_population(pop, generation=4))
+    return out, [h.weights.tolist() for h in ev.hall_of_fame], (ev.total_games, ev.total_env_steps, ev.total_decisions)
+
+
 def test_evaluate_population_does_not_notice():
     """Hall of fame, statistics and a deck schedule's sequential stream are left alone: evaluate_population returns the
     same lists with an evaluate_vs_expert call in between as without one."""
-    from oracle_rollout import oracle_rollout_fn
-    from monsoon_amd.cards import DECKS
-    from monsoon_amd.decks import DeckEvolutionConfig
+    for deck_config in (None, _explore):
+        assert _two_generations(True, deck_config) == _two_generations(False, deck_config)
 
-    def both(fn):   # the evaluator's rollout_fn serves both kinds of schedule
-        return lambda w, m, d, t: (M.vs_expert_rollout_fn if (np.asarray(m)["p1"] < 0).any() or (np.asarray(m)["p2"] < 0).any() else fn)(w, m, d, t)
 
-    def run(with_bot, deck_config):
-        ev = FitnessEvaluator(_config(), deck_config() if deck_config else None, rollout_fn=both(oracle_rollout_fn))
-        pop = _population()
-        out = [ev.evaluate_population(pop, generation=3)]
-        if with_bot:
-            ev.evaluate_vs_expert(pop, generation=3, games_per_individual=2)
-        out.append(ev.evaluate_population(pop, generation=4))
-        return out, [h.weights.tolist() for h in ev.hall_of_fame], (ev.total_games, ev.total_env_steps, ev.total_decisions)
+def test_vs_expert_detour_changes_nothing_of_the_evaluator_or_its_config():
+    """In a random phase of a sequential DeckEvolutionConfig the vs-bot games take configuration C5's per-seed decks, and
+    the deck source is an argument: inside the deck_draw_fn and rollout_fn hooks the caller's config still names its own
+    deck and the evaluator still holds its schedule (anything sharing the config reads it as it is), also after a hook
+    that raises.  The decks are numpy's draw from seed ^ C5_STREAM_XOR, and what the GA sees is what an evaluator that
+    never played the bot sees."""
+    from monsoon_amd.cards import C5_STREAM_XOR, draw_random_decks_numpy
+    cfg, dc = _config(), _explore()
+    seen, played, boom = [], [], []
 
-    # generation 3 / 4 of this schedule are in its explore phase: a deck pair per game from one seeded stream
-    explore = lambda: DeckEvolutionConfig(DECKS["IRONCLAD"], DECKS["SWARM"], exploit_generations=1, explore_generations=6, seed=9)   # noqa: E731
-    for deck_config in (None, explore):
-        assert run(True, deck_config) == run(False, deck_config)
+    def state():
+        return cfg.deck, ev.deck_config is dc, ev.config is cfg
+
+    def draw(pre, pool):
+        seen.append((state(), np.array(pre)))
+        if boom:
+            raise RuntimeError(boom[0])
+        return draw_random_decks_numpy(pre, pool)
+
+    def roll(w, m, d, t):
+        if (np.asarray(m)["p1"] < 0).any() or (np.asarray(m)["p2"] < 0).any():
+            played.append((state(), np.array(m), np.array(d)))
+            if boom:
+                raise RuntimeError(boom[0])
+        return _both(w, m, d, t)
+    ev = FitnessEvaluator(cfg, dc, rollout_fn=roll, deck_draw_fn=draw)
+    assert _two_generations(True, None, ev) == _two_generations(False, _explore)
+    sched = expert_schedule(4, 2, 3)
+    assert len(seen) == 1 and len(played) == 1
+    assert seen[0][0] == ("N12M", True, True) and played[0][0] == ("N12M", True, True)
+    assert np.array_equal(seen[0][1], sched["seed"] ^ np.uint32(C5_STREAM_XOR))
+    assert np.array_equal(played[0][1]["seed"], sched["seed"]) and np.array_equal(played[0][1]["deck"], np.arange(8))
+    assert np.array_equal(played[0][2], draw_random_decks_numpy(sched["seed"] ^ np.uint32(C5_STREAM_XOR)))
+    for where in ("draw", "roll"):
+        boom[:] = [where]
+        ev = FitnessEvaluator(cfg, dc, rollout_fn=roll if where == "roll" else _both, deck_draw_fn=draw if where == "draw" else None)
+        with pytest.raises(RuntimeError, match=where):
+            ev.evaluate_vs_expert(_population(), generation=3, games_per_individual=2)
+        assert state() == ("N12M", True, True)   # state() reads the evaluator in use
 
 
 def test_record_limited_vs_bot_game_is_replayed_on_its_own_row():
