@@ -233,6 +233,55 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
                            int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                            int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log);
 
+/* Logged games played again on the device into the (state, action) rows a learner trains on: one row per kept log entry,
+ * holding the state BEFORE that entry's step.  No decision is recomputed: every entry costs one committed step.
+ * matches, deck_pairs, the log (log_action[n_matches][log_stride], log_steps[n_matches] entries per row, what
+ * monsoon_rollout_logged wrote as log->action and out_steps), keep and the three out_* arrays are HOST buffers; the rows
+ * are DEVICE buffers of the caller.  p1 / p2 of a match are read only for MONSOON_PLAYER_EXPERT: no weight table is needed.
+ * Every game is reset from its seed and deck pair, then for entry k = 0 .. log_steps[g]-1 with action a, in this order:
+ *  1. the game is over by the rollout's rules -- a winner, a fault, or an observation that raised after the step before:
+ *     it stops with MONSOON_REPLAY_ENDED_EARLY;
+ *  2. a is not < 156 or not legal (PASS, 155, is always accepted, as monsoon_step accepts it): MONSOON_REPLAY_ILLEGAL;
+ *  3. if keep is NULL or keep[g][k] != 0 the entry's row is written (below);
+ *  4. if the side to play is MONSOON_PLAYER_EXPERT in the match, the bot's expert_action runs and consumes the game's
+ *     stream as it did in the rollout; it raises: MONSOON_REPLAY_BOT_RAISED; its action is not a: MONSOON_REPLAY_BOT_DIFFERS;
+ *  5. a is stepped.  A step that faults, or after which the observation raises, ends the game (the code in out_fault,
+ *     as monsoon_rollout_faults reports it: a code >= 16 other than 18 is a limit of this build's record).
+ * out_status[g] = 0 or the stop's code, out_replayed[g] = the steps committed, out_fault[g] = the game's fault code.
+ * Rows are in match order, then entry order: game g's first kept entry is row base[g] = the kept entries k < log_steps of
+ * the games before it, S of them in all (*out_rows).  action[0 .. S) is filled with 255 before anything is replayed, so the
+ * rows of a stopped game from its stop on read action 255; THEIR OTHER COLUMNS ARE UNSPECIFIED.
+ * At most max_games games are played at a time, as the rollouts do; the last batch stays loaded in its final states
+ * (monsoon_state_hash, monsoon_get_stats work as after a rollout; every side that is not the bot holds weight row 0).  The
+ * device copy of the log lives in the handle and grows on demand.  The call returns when the host outputs are written,
+ * and counts as one timed launch per batch (monsoon_kernel_time).
+ * MONSOON_ERR_ARG, with nothing launched, no output written and the loaded games untouched: a NULL h / matches /
+ * deck_pairs / log_action / log_steps / rows / rows->action, n_matches / n_decks / log_stride <= 0, a deck index outside
+ * n_decks, a card this build does not support, log_steps[g] outside 0 .. log_stride, S > rows_cap, legal / obs / game / step
+ * not 4-byte or state_hash not 8-byte aligned.  out_rows, out_status, out_replayed, out_fault may be NULL. */
+#define MONSOON_REPLAY_OK          0
+#define MONSOON_REPLAY_ILLEGAL     1   /* a logged action that is not legal where it is replayed */
+#define MONSOON_REPLAY_BOT_DIFFERS 2   /* the bot's expert_action is not the logged action */
+#define MONSOON_REPLAY_BOT_RAISED  3   /* the bot's expert_action raised where the log has a step */
+#define MONSOON_REPLAY_ENDED_EARLY 4   /* the game ended before its last entry */
+typedef struct {          /* DEVICE pointers, S rows; all but action may be NULL and then cost nothing */
+  int32_t*  obs;          /* [S][27][5][4] the observation BEFORE the step, 0 where it raises */
+  uint8_t*  legal;        /* [S][156] 1 = legal (monsoon_env_views' layout) */
+  uint8_t*  obs_raises;   /* [S] */
+  uint8_t*  to_play;      /* [S] */
+  uint8_t*  action;       /* [S] required; 255 = a row the replay did not reach */
+  uint8_t*  bot;          /* [S] 1 = a step of the scripted bot */
+  int32_t*  game;         /* [S] match index */
+  int32_t*  step;         /* [S] entry index k */
+  uint64_t* state_hash;   /* [S] canonical hash of the state before the step (what monsoon_state_hash reports) */
+} monsoon_replay_rows;
+int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches,
+                              const uint8_t* deck_pairs, int32_t n_decks,
+                              const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps,
+                              const uint8_t* keep /* [n_matches][log_stride], NULL = every entry */,
+                              const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows,
+                              uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault);
+
 /* Per-game decks of configuration C5 on the device: for every seed, numpy.random.RandomState(seed).choice(pool, 12,
  * replace=False) twice -> out_pairs[n][2][12] (card indices taken from pool[pool_n], 12 <= pool_n <= 128).  The caller
  * passes the pre-stream seeds (game seed ^ 0x9E3779B9).  Host buffers in and out; needs no loaded games.

@@ -70,6 +70,13 @@ class RolloutLog(ctypes.Structure):     # monsoon_rollout_log: caller-owned host
     _fields_ = [(name, ctypes.c_void_p) for name in ("action", "score", "n_legal")]
 
 
+class ReplayRows(ctypes.Structure):     # monsoon_replay_rows: caller-owned device buffers (NULL = not wanted, except action)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "legal", "obs_raises", "to_play", "action", "bot", "game", "step",
+                                                      "state_hash")]
+
+
+REPLAY_OK, REPLAY_ILLEGAL, REPLAY_BOT_DIFFERS, REPLAY_BOT_RAISED, REPLAY_ENDED_EARLY = range(5)   # MONSOON_REPLAY_*
+
 SIGNATURES = {
     "monsoon_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_void_p)]),
     "monsoon_destroy": (None, [ctypes.c_void_p]),
@@ -108,6 +115,10 @@ SIGNATURES = {
     "monsoon_rollout_logged": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(RolloutLog)]),
+    "monsoon_replay_logged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.POINTER(ReplayRows), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_rollout_faults": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_draw_decks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "monsoon_draw_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),

@@ -80,6 +80,26 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
   return e.card_int_id(e.m.ld8(H_HIST + 2 * k + 1));
 }
 
+// The order obs_word reads a record's deck in, by the whole wave: a lane per deck card finds its place in the stable
+// (cost, card id) order of engine se_'s deck and writes ord_[place].  The first barrier lets the readers of the order
+// before finish, the second publishes this one.  Spelled in place like MSB_EACH_GRANULE (after_slot per successor,
+// replay_row per row: replay_log.h): as a function it moved after_slot's scalar registers about (scripts/isa_diff.sh).
+#define MSB_OBS_DECK_ORDER(se_, lane_, ord_)                                                          \
+  {                                                                                                   \
+    const int lo = se_.local(), dn = se_.pl_deck_n(lo);                                               \
+    __syncthreads();                                                                                  \
+    for (int v = lane_; v < dn; v += 64) {                                                            \
+      const int kc = se_.deck_cost(lo, v), kid = se_.deck_card(lo, v);                                \
+      int r = 0;                                                                                      \
+      for (int j = 0; j < dn; j++) {                                                                  \
+        const int oc = se_.deck_cost(lo, j), oid = se_.deck_card(lo, j);                              \
+        r += (oc < kc || (oc == kc && (oid < kid || (oid == kid && j < v)))) ? 1 : 0;                 \
+      }                                                                                               \
+      ord_[r] = (uint8_t)v;                                                                           \
+    }                                                                                                 \
+    __syncthreads();                                                                                  \
+  }
+
 // The afterstates of slot g by the calling wavefront; K = max_after.  Call with the whole wave.
 template <int U>
 __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after& o, const int K, const int g, const int lane) {
@@ -174,18 +194,7 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
         if (!((part >> c) & 1)) continue;   // (uniform)
         typename L::SubEngine se;
         se.m.c16 = c * 16;
-        const int lo = se.local(), dn = se.pl_deck_n(lo);
-        __syncthreads();   // the order of the candidate before has been read
-        for (int v = lane; v < dn; v += 64) {   // a lane per deck card: its place in the stable (cost, card id) order
-          const int kc = se.deck_cost(lo, v), kid = se.deck_card(lo, v);
-          int r = 0;
-          for (int j = 0; j < dn; j++) {
-            const int oc = se.deck_cost(lo, j), oid = se.deck_card(lo, j);
-            r += (oc < kc || (oc == kc && (oid < kid || (oid == kid && j < v)))) ? 1 : 0;
-          }
-          ord[r] = (uint8_t)v;
-        }
-        __syncthreads();
+        MSB_OBS_DECK_ORDER(se, lane, ord)   // (its first barrier: the order of the candidate before has been read)
         int32_t* out = o.obs + ((size_t)g * K + base + c) * MONSOON_OBS_INTS;
         for (int i = lane; i < MONSOON_OBS_INTS; i += 64) out[i] = obs_word(se, i, ord);
       }

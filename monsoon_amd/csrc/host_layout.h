@@ -108,6 +108,21 @@ inline RolloutLog rollout_log(size_t entries, bool score, bool n_legal) {
   return l;
 }
 
+// d_replay, what one batch of monsoon_replay_logged_dev takes to the device and brings back: `games` games, `entries` =
+// games x log_stride; without a keep mask its array takes no room (NONE).  status .. fault come back in three copies.
+struct Replay { size_t base = 0, steps, replayed, action, keep, status, fault, total; };   // i64 | i32 | i32 [games], u8 | u8 [entries], u8 | u8 [games]
+inline Replay replay(size_t games, size_t entries, bool keep) {
+  Replay l;
+  l.steps = l.base + 8 * games;
+  l.replayed = l.steps + 4 * games;
+  l.action = l.replayed + 4 * games;
+  l.keep = keep ? l.action + entries : NONE;
+  l.status = l.action + (keep ? 2 : 1) * entries;
+  l.fault = l.status + games;
+  l.total = l.fault + games;
+  return l;
+}
+
 // d_results of a rollout: results, then fault codes (monsoon_rollout_faults)
 struct Results { size_t result = 0, fault, total; };                         // i8 [cap] | u8 [cap]
 inline Results results(size_t cap) { return {0, cap, 2 * cap}; }

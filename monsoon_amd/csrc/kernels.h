@@ -4,7 +4,8 @@
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
 // (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, env_opp.hip and env_after.hip hold one
-// further instantiation each; monsoon_hip.hip holds the API kernels and the host side.
+// further instantiation each, replay_log.hip one of the rules core without the decision loop; monsoon_hip.hip holds the
+// API kernels and the host side.
 //
 // Execution model
 //   * Hot kernel k_play<U,W>: ONE WAVEFRONT PER GAME at a time (a persistent grid of resident wavefronts, each popping
@@ -672,7 +673,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
-// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_env_opp): `mine` / `other` are this launch's counter
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_replay_log, k_env_opp): `mine` / `other` are this launch's counter
 // set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
 // nothing for it leaves before enter(), which runs once ahead of the first game.
 template <class Enter, class Play>

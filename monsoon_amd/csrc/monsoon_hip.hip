@@ -23,6 +23,7 @@
 #include "host_layout.h"
 #include "host_mem.h"
 #include "kernels.h"
+#include "replay_log.h"
 
 using namespace msb;
 using namespace msbk;
@@ -724,6 +725,10 @@ struct monsoon {
   // monsoon_rollout_logged: the log of one batch (layout::rollout_log), grown on demand
   uint8_t* d_log = nullptr;
   size_t log_cap = 0;   // bytes
+  // monsoon_replay_logged_dev: one batch's log, keep mask, row bases and outcome (layout::replay), grown on demand
+  uint8_t* d_replay = nullptr;
+  size_t replay_cap = 0;   // bytes
+  int replay_waves = 0;    // resident wavefronts of k_replay_log (queried once per handle)
   // kernel timing: event pairs are created once and reused
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   std::vector<char> ev_split;   // pair i times a split call: its end event lies on the last sub-batch's stream (drain_timing)
@@ -1895,6 +1900,109 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
   if (!log || !log->action) return bad_arg(h, "monsoon_rollout_logged", "log and log->action are required");
   return rollout_impl(h, "monsoon_rollout_logged", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
                       max_turns, out_counts, out_results, out_steps, log);
+}
+
+// Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.
+static int replay_batch(monsoon_t* h, int base, int n, const monsoon_match* matches, const uint8_t* deck_pairs, const uint8_t* log_action,
+                        int32_t log_stride, const int32_t* log_steps, const uint8_t* keep, const int64_t* row_base, const monsoon_replay_rows& rows,
+                        const layout::Replay& l, uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault) {
+  std::vector<uint32_t> seeds(n);
+  std::vector<uint8_t> decks((size_t)n * 24);
+  std::vector<int32_t> p1(n), p2(n);
+  bool bot_rows = false;
+  for (int i = 0; i < n; i++) {   // a side is the bot or not: the replay plays nobody's weights (row 0 stands for "not the bot")
+    const monsoon_match& mm = matches[base + i];
+    seeds[i] = mm.seed;
+    memcpy(&decks[(size_t)i * 24], deck_pairs + (size_t)mm.deck * 24, 24);
+    p1[i] = mm.p1 == MONSOON_PLAYER_EXPERT ? MONSOON_PLAYER_EXPERT : 0;
+    p2[i] = mm.p2 == MONSOON_PLAYER_EXPERT ? MONSOON_PLAYER_EXPERT : 0;
+    bot_rows |= p1[i] < 0 || p2[i] < 0;
+  }
+  int rc = monsoon_reset(h, n, seeds.data(), decks.data(), nullptr);
+  if (rc) return rc;
+  h->bot_rows = bot_rows;
+  const size_t entries = (size_t)n * log_stride, at = (size_t)base * log_stride;
+  uint8_t* d = h->d_replay;
+  HIP_TRY(h, hipMemcpyAsync(h->d_p1, p1.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_p2, p2.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_assign, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_p1, h->d_p2, base);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(d + l.base, row_base + base, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.steps, log_steps + base, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d + l.action, log_action + at, entries, hipMemcpyHostToDevice, h->stream));
+  if (keep) HIP_TRY(h, hipMemcpyAsync(d + l.keep, keep + at, entries, hipMemcpyHostToDevice, h->stream));
+  const ReplayArgs ra = {rows, d + l.action, keep ? d + l.keep : nullptr, (const int32_t*)(d + l.steps), (const int64_t*)(d + l.base),
+                         d + l.status, (int32_t*)(d + l.replayed), d + l.fault, log_stride};
+  const ReplayOps* o = monsoon_replay_log_ops();
+  const int lds = o->lds_bytes + g_lds_pad;
+  if (!h->replay_waves) {
+    rc = resident_waves(h, o->occupancy, lds, 4096, &h->replay_waves);
+    if (rc) return rc;
+  }
+  // the persistent form needs a wavefront for every one of its POP_PARTS ranges (launch_play)
+  int grid = h->replay_waves;
+  const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
+  if (!pers) grid = n;   // a wavefront per game
+  rc = grow_ovf(h, (size_t)grid * o->lanes);
+  if (rc) return rc;
+  size_t slot = 0;
+  rc = timing_begin(h, &slot);
+  if (rc) return rc;
+  o->launch(grid, lds, h->stream, h->b, ra, n, pers, h->parity[0]);
+  if (pers) h->parity[0] ^= 1;   // (only a persistent launch consumes its counter set: launch_play)
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(h->ev_pool[slot].second, h->stream));
+  if (out_status) HIP_TRY(h, hipMemcpyAsync(out_status + base, d + l.status, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  if (out_replayed) HIP_TRY(h, hipMemcpyAsync(out_replayed + base, d + l.replayed, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (out_fault) HIP_TRY(h, hipMemcpyAsync(out_fault + base, d + l.fault, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return drain_timing(h);
+}
+
+int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks,
+                              const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps, const uint8_t* keep,
+                              const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows, uint8_t* out_status, int32_t* out_replayed,
+                              uint8_t* out_fault) {
+  const char* who = "monsoon_replay_logged_dev";
+  if (!h) return MONSOON_ERR_ARG;
+  if (!matches || !deck_pairs || !log_action || !log_steps || n_matches <= 0 || n_decks <= 0 || log_stride <= 0) return bad_arg(h, who, "bad argument");
+  if (!rows || !rows->action) return bad_arg(h, who, "rows and rows->action are required");
+  if (((uintptr_t)rows->obs | (uintptr_t)rows->legal | (uintptr_t)rows->game | (uintptr_t)rows->step) & 3)
+    return bad_arg(h, who, "obs, legal, game and step must be 4-byte aligned");
+  if ((uintptr_t)rows->state_hash & 7) return bad_arg(h, who, "state_hash must be 8-byte aligned");
+  // The whole schedule, every deck and the log's shape are checked, and the rows counted, before anything is loaded or launched.
+  std::vector<int64_t> row_base(n_matches);
+  int64_t total = 0;
+  for (int i = 0; i < n_matches; i++) {
+    if (matches[i].deck >= (uint32_t)n_decks) return bad_arg(h, who, "schedule entry " + std::to_string(i) + " out of range");
+    if (log_steps[i] < 0 || log_steps[i] > log_stride) return bad_arg(h, who, "log_steps[" + std::to_string(i) + "] outside 0 .. log_stride");
+    row_base[i] = total;
+    if (keep) {
+      const uint8_t* kr = keep + (size_t)i * log_stride;
+      for (int k = 0; k < log_steps[i]; k++) total += kr[k] ? 1 : 0;
+    } else {
+      total += log_steps[i];
+    }
+  }
+  if (total > rows_cap) return bad_arg(h, who, std::to_string(total) + " rows do not fit rows_cap = " + std::to_string(rows_cap));
+  int rc = check_decks(h, deck_pairs, (size_t)n_decks * 24, who);
+  if (rc) return rc;
+  HIP_TRY(h, bind_device(h));
+  const int cap = h->cfg.max_games;
+  const layout::Replay l = layout::replay((size_t)std::min(cap, n_matches), (size_t)std::min(cap, n_matches) * log_stride, keep != nullptr);
+  if (l.total > h->replay_cap) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (nothing in flight may still read the block that is freed)
+    HIP_TRY(h, h->mem.grow(h->d_replay, h->replay_cap, l.total, l.total, Grow::Replace));
+  }
+  if (total) HIP_TRY(h, hipMemsetAsync(rows->action, 0xFF, (size_t)total, h->stream));   // a row the replay does not reach
+  for (int base = 0; base < n_matches; base += cap) {
+    const int n = n_matches - base < cap ? n_matches - base : cap;
+    rc = replay_batch(h, base, n, matches, deck_pairs, log_action, log_stride, log_steps, keep, row_base.data(), *rows, l, out_status,
+                      out_replayed, out_fault);
+    if (rc) return rc;
+  }
+  if (out_rows) *out_rows = total;
+  return MONSOON_OK;
 }
 
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches) {

@@ -350,6 +350,29 @@ class BatchEngine:
         self.n = len(m) - ((len(m) - 1) // batch) * batch   # the handle now holds the last batch of the schedule
         return (counts, results, steps) if want_results else counts
 
+    def replay_logged(self, matches, deck_pairs, log_action, log_steps, rows, rows_cap, keep=None):
+        """monsoon_replay_logged_dev: the logged games played again, one committed step per entry, the state before every
+        kept entry written to row (kept entries before it) of `rows` -- a _lib.ReplayRows of DEVICE pointers with room for
+        rows_cap rows.  log_action uint8[n][stride], log_steps int32[n], keep uint8[n][stride] or None (every entry).
+        Returns (rows written, status uint8[n] (_lib.REPLAY_*), replayed int32[n], fault uint8[n])."""
+        _, m, deck_pairs = self._rollout_args(np.zeros((1, 10)), matches, deck_pairs)
+        log_action = np.ascontiguousarray(log_action, dtype=np.uint8)
+        log_steps = np.ascontiguousarray(log_steps, dtype=np.int32)
+        if log_action.ndim != 2 or log_action.shape[0] != len(m) or log_steps.shape != (len(m),):
+            raise ValueError("replay_logged: one log row and one step count per match")
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8)
+            if keep.shape != log_action.shape:
+                raise ValueError("replay_logged: keep has the shape of the log")
+        status, replayed = np.zeros(len(m), dtype=np.uint8), np.zeros(len(m), dtype=np.int32)
+        fault, n_rows = np.zeros(len(m), dtype=np.uint8), ctypes.c_int64(0)
+        self._ck(self.lib.monsoon_replay_logged_dev(self.h, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs), _ptr(log_action),
+                                                    log_action.shape[1], _ptr(log_steps), _ptr(keep), ctypes.byref(rows), int(rows_cap),
+                                                    ctypes.byref(n_rows), _ptr(status), _ptr(replayed), _ptr(fault)),
+                 "monsoon_replay_logged_dev")
+        self.n = len(m) - ((len(m) - 1) // self.max_games) * self.max_games   # the handle now holds the last batch
+        return n_rows.value, status, replayed, fault
+
     def rollout_faults(self, n_matches):
         """Fault code of every game of the last rollout (>= 16: a limit of this build's record, see include/monsoon.h)."""
         out = np.zeros(n_matches, dtype=np.uint8)

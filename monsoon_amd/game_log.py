@@ -2,10 +2,12 @@
 
 logged_rollout plays a schedule over the record tiers as fitness.tiered_rollout does and keeps every game's log;
 FitnessEvaluator.logged_games is its entry over an evaluator's own engines; replay plays logged games again through the
-step interface and yields the (state, action) pairs a learner wants.
+step interface and yields the (state, action) pairs a learner wants; dataset / dataset_batches / step_sides play them
+again on the device (monsoon_replay_logged_dev), games with the scripted bot included, into torch tensors of rows.
 """
 import numpy as np
 
+from . import _lib
 from .engine import RolloutLog
 from .fitness import _ladder, bot_plays
 
@@ -56,3 +58,154 @@ def replay(engine, matches, deck_pairs, log):
         yield live, engine.status()[:, 0], mask, engine.observe()[0], action
         engine.step(action)
     return engine.state_hash()
+
+
+# ---- replay on the device: (observation, action) rows as torch tensors -----------------------------------------------
+# name -> (torch dtype, shape of a row): the columns of monsoon_replay_rows.  state_hash holds the bits of the uint64 that
+# state_hash() reports (view it as uint64 on the host: t.cpu().numpy().view(numpy.uint64)).
+COLUMNS = {"obs": ("int32", (27, 5, 4)), "legal": ("uint8", (156,)), "obs_raises": ("uint8", ()), "to_play": ("uint8", ()),
+           "action": ("uint8", ()), "bot": ("uint8", ()), "game": ("int32", ()), "step": ("int32", ()), "state_hash": ("int64", ())}
+ROW_BYTES = {"obs": 2160, "legal": 156, "obs_raises": 1, "to_play": 1, "action": 1, "bot": 1, "game": 4, "step": 4, "state_hash": 8}
+
+
+def kept_counts(steps, keep=None):
+    """int64[n]: the rows each game gets -- its entries k < steps[g], those with keep[g][k] != 0 if a mask is given."""
+    steps = np.asarray(steps, dtype=np.int64)
+    if keep is None:
+        return steps.copy()
+    keep = np.asarray(keep)
+    if keep.ndim != 2 or keep.shape[0] != len(steps) or (len(steps) and int(steps.max()) > keep.shape[1]):
+        raise ValueError("keep: one row per game, at least as long as the game")
+    return ((keep != 0) & (np.arange(keep.shape[1])[None, :] < steps[:, None])).sum(axis=1).astype(np.int64)
+
+
+def row_bases(steps, keep=None):
+    """(base int64[n], S): rows are in match order, then entry order -- game g's first kept entry is row base[g], S rows in all."""
+    counts = kept_counts(steps, keep)
+    ends = np.cumsum(counts)
+    return ends - counts, int(ends[-1]) if len(ends) else 0
+
+
+def batch_cuts(counts, max_rows):
+    """[(g0, g1), ...]: the games cut into runs of whole consecutive games, each as long as max_rows rows allow (greedy).
+    ValueError if one game alone has more rows than max_rows."""
+    cuts, g0, rows = [], 0, 0
+    for g, c in enumerate(np.asarray(counts, dtype=np.int64).tolist()):
+        if c > max_rows:
+            raise ValueError(f"dataset_batches: game {g} alone has {c} rows, max_rows is {max_rows}")
+        if rows + c > max_rows:
+            cuts.append((g0, g))
+            g0, rows = g, 0
+        rows += c
+    if g0 < len(counts):
+        cuts.append((g0, len(counts)))
+    return cuts
+
+
+def outcome(results, game, to_play):
+    """+1 / 0 / -1 per row, from the side to play: results[n] is the rollout's (-1 a draw, 0 FIRST won, 1 SECOND won), game
+    the rows' match index (an index array of the results' library), to_play their side.  Works on numpy arrays and on
+    torch tensors alike; the caller casts the result."""
+    r = results[game]
+    return (r >= 0) * (1 - 2 * (r != to_play))
+
+
+def _want(columns):
+    columns = tuple(columns)
+    bad = [c for c in columns if c not in COLUMNS]
+    if bad:
+        raise ValueError(f"unknown column(s) {bad}: choose from {tuple(COLUMNS)}")
+    return columns if "action" in columns else columns + ("action",)
+
+
+def _tensors(engine, names, cap):
+    import torch
+    dev = torch.device("cuda", engine.device)
+    return {c: torch.empty((max(int(cap), 1),) + COLUMNS[c][1], dtype=getattr(torch, COLUMNS[c][0]), device=dev) for c in names}
+
+
+def _replay_into(engine, tensors, matches, deck_pairs, action, steps, keep):
+    """One monsoon_replay_logged_dev call into the first rows of `tensors`: (rows, status, replayed, fault)."""
+    import torch
+    torch.cuda.current_stream(tensors["action"].device).synchronize()   # the library works on the handle's stream
+    rows = _lib.ReplayRows(**{c: t.data_ptr() for c, t in tensors.items()})
+    return engine.replay_logged(matches, deck_pairs, action, steps, rows, tensors["action"].shape[0], keep)
+
+
+def _columns_for(columns, results):
+    names = _want(columns)
+    if results is not None:
+        names += tuple(c for c in ("game", "to_play") if c not in names)
+    return names
+
+
+def _hand_out(tensors, columns, n_rows, results, status, replayed, fault):
+    import torch
+    out = {c: tensors[c][:n_rows] for c in _want(columns)}
+    if results is not None:
+        res = torch.as_tensor(np.ascontiguousarray(results, dtype=np.int8), device=tensors["action"].device)
+        out["outcome"] = outcome(res, tensors["game"][:n_rows].long(), tensors["to_play"][:n_rows]).to(torch.int8)
+    out.update(status=status, replayed=replayed, fault=fault)
+    return out
+
+
+def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS), results=None):
+    """The (state, action) rows of logged games as torch CUDA tensors, replayed on the device by `engine` (games with the
+    scripted bot included: its expert_action runs again and consumes the stream as it did).  One row per entry k <
+    log.steps[g] (with keep uint8 / bool [n][T]: per entry with keep[g][k]), in match order, then entry order, holding the
+    state BEFORE the step: a dict of the chosen `columns` (COLUMNS; action always) plus the host arrays status uint8[n]
+    (_lib.REPLAY_*: 0 = replayed to its last entry), replayed int32[n] and fault uint8[n].  The rows of a game that
+    stopped early read action 255 from the stop on; their other columns are unspecified.  results int8[n] (the rollout's)
+    adds outcome int8[S]: +1 / 0 / -1 from the side to play.
+
+    torch has to be imported before the engine is created, for the reason VecEnv.__init__ gives (it has to load its own
+    ROCm runtime first): `import torch` before the first BatchEngine(...) of the process."""
+    import torch
+    if not torch.cuda.is_available():
+        raise _lib.MonsoonError("dataset: torch sees no device -- import torch before the first BatchEngine is created")
+    matches = np.asarray(matches)
+    if log.action.shape[0] != len(matches):
+        raise ValueError("dataset: one log row per match")
+    _, total = row_bases(log.steps, keep)
+    tensors = _tensors(engine, _columns_for(columns, results), total)
+    n_rows, status, replayed, fault = _replay_into(engine, tensors, matches, deck_pairs, log.action, log.steps, keep)
+    return _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
+
+
+def dataset_batches(engine, matches, deck_pairs, log, max_rows, keep=None, columns=tuple(COLUMNS), results=None):
+    """dataset over a log too large for one set of tensors (65 536 games are about 30 GB of observations): a generator over
+    runs of whole consecutive games whose rows fit max_rows (batch_cuts), each item dataset's dict for that run plus
+    games = (g0, g1); game holds the index into the whole schedule.  ONE set of tensors is allocated and every item is a
+    view of it: the next item overwrites the one before, so use or copy an item before asking for the next.
+    ValueError if one game alone has more than max_rows rows."""
+    import torch
+    if not torch.cuda.is_available():
+        raise _lib.MonsoonError("dataset_batches: torch sees no device -- import torch before the first BatchEngine is created")
+    matches = np.asarray(matches)
+    counts = kept_counts(log.steps, keep)
+    cuts = batch_cuts(counts, max_rows)
+    cap = max((int(counts[a:b].sum()) for a, b in cuts), default=0)
+    tensors = _tensors(engine, _columns_for(columns, results), cap)
+    for a, b in cuts:
+        n_rows, status, replayed, fault = _replay_into(engine, tensors, matches[a:b], deck_pairs, log.action[a:b], log.steps[a:b],
+                                                        None if keep is None else np.asarray(keep)[a:b])
+        if "game" in tensors:
+            tensors["game"][:n_rows] += a
+        item = _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
+        item["games"] = (a, b)
+        yield item
+
+
+def step_sides(engine, matches, deck_pairs, log):
+    """(to_play int8[n][T], bot bool[n][T]) on the host: who played entry k of game g (-1 behind the game's last replayed
+    entry) and whether it was the scripted bot -- from a columns-only replay without observations.  What a keep mask is
+    built from: the winner's decisions only, no bot steps, every 4th entry, ..."""
+    d = dataset(engine, matches, deck_pairs, log, columns=("to_play", "bot", "game", "step"))
+    cols = {c: d[c].cpu().numpy() for c in ("to_play", "bot", "game", "step", "action")}
+    to_play = np.full(log.action.shape, -1, dtype=np.int8)
+    bot = np.zeros(log.action.shape, dtype=bool)
+    reached = cols["action"] != 255
+    g, k = cols["game"][reached], cols["step"][reached]
+    to_play[g, k] = cols["to_play"][reached]
+    bot[g, k] = cols["bot"][reached] != 0
+    return to_play, bot
