@@ -282,6 +282,44 @@ int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_
                               const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows,
                               uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault);
 
+/* monsoon_replay_logged_dev whose rows also carry the candidates the choice was made among: for every kept entry the
+ * afterstates of the state its row shows, K = max_after entries per row.  Row r of `after` is what
+ * monsoon_env_afterstates_dev (below) writes for a slot in that state, with monsoon_env_after's meaning word for word --
+ * the order of the entries, n_legal beyond K, action 255 for k >= min(n_legal, K), the status codes, reward 0 and winner -2
+ * where the step raised, features and obs only where status == 0 -- except that before_features reads zeros where the
+ * row's observation raises.  chosen[r] is the rank of the row's logged action in the ascending legal list, so
+ * action[r][chosen[r]] is rows->action[r] wherever 0 <= chosen[r] < K; it is -1 for a PASS that is accepted without being
+ * in the legal set.  Entries k >= min(n_legal, K) of every column but action, what monsoon_env_after leaves unwritten,
+ * and every column of the rows behind a game's stop (rows->action 255) are UNSPECIFIED.
+ * The look-ahead of a row happens in step 3 of the order above, when the row is written and before the bot's
+ * expert_action, and consumes nothing: the game's cursor, stream blocks and record, the rows, out_status, out_replayed and
+ * out_fault are those of monsoon_replay_logged_dev with the same arguments.  A candidate that hits a limit of this
+ * build's record (a code >= 16 other than 18) shows it in status only; out_fault reports committed steps.
+ * monsoon_get_stats after the call: lookahead_steps counts the candidates stepped, min(n_legal, K) per kept entry that was
+ * reached; decisions counts nothing, as after monsoon_replay_logged_dev.
+ * after == NULL: the call is monsoon_replay_logged_dev (max_after is not read).  Otherwise MONSOON_ERR_ARG, with nothing
+ * launched, no output written and the loaded games untouched, for whatever monsoon_replay_logged_dev refuses, max_after
+ * outside 1..156, a NULL after->n_legal or after->action, n_legal or obs not 4-byte, chosen not 2-byte, features or
+ * before_features not 8-byte aligned. */
+typedef struct {            /* DEVICE pointers; S rows, K = max_after entries per row; any may be NULL except n_legal and action */
+  int32_t* n_legal;         /* [S]        legal actions of the row's state (the full count, also beyond K) */
+  int16_t* chosen;          /* [S]        rank of the row's logged action in the ascending legal list (may be >= K); -1 if it is not in the legal set */
+  uint8_t* action;          /* [S][K]     k-th legal action, ascending; 255 for k >= min(n_legal, K) */
+  uint8_t* status;          /* [S][K]     monsoon_env_after's status */
+  int8_t*  reward;          /* [S][K] */
+  int8_t*  winner;          /* [S][K] */
+  double*  features;        /* [S][K][10] only where status == 0 */
+  double*  before_features; /* [S][10]    zeros where the row's observation raises */
+  int32_t* obs;             /* [S][K][27][5][4] only where status == 0 */
+} monsoon_replay_after;
+int monsoon_replay_logged_after_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches,
+                                    const uint8_t* deck_pairs, int32_t n_decks,
+                                    const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps,
+                                    const uint8_t* keep /* [n_matches][log_stride], NULL = every entry */,
+                                    const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows,
+                                    uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault,
+                                    const monsoon_replay_after* after, int32_t max_after /* 1..156 */);
+
 /* Per-game decks of configuration C5 on the device: for every seed, numpy.random.RandomState(seed).choice(pool, 12,
  * replace=False) twice -> out_pairs[n][2][12] (card indices taken from pool[pool_n], 12 <= pool_n <= 128).  The caller
  * passes the pre-stream seeds (game seed ^ 0x9E3779B9).  Host buffers in and out; needs no loaded games.

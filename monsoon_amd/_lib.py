@@ -75,6 +75,11 @@ class ReplayRows(ctypes.Structure):     # monsoon_replay_rows: caller-owned devi
                                                       "state_hash")]
 
 
+class ReplayAfter(ctypes.Structure):    # monsoon_replay_after: caller-owned device buffers (NULL = not wanted, except n_legal and action)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("n_legal", "chosen", "action", "status", "reward", "winner", "features",
+                                                      "before_features", "obs")]
+
+
 REPLAY_OK, REPLAY_ILLEGAL, REPLAY_BOT_DIFFERS, REPLAY_BOT_RAISED, REPLAY_ENDED_EARLY = range(5)   # MONSOON_REPLAY_*
 
 SIGNATURES = {
@@ -119,6 +124,11 @@ SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.POINTER(ReplayRows), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "monsoon_replay_logged_after_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                                       ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.POINTER(ReplayRows), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ReplayAfter),
+                                                       ctypes.c_int32]),
     "monsoon_rollout_faults": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_draw_decks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "monsoon_draw_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),

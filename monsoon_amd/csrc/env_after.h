@@ -4,7 +4,8 @@
 // then passes that clone the record, take their actions, step them and hand each successor out -- status, reward, winner,
 // the ten features, the observation -- instead of scoring it.  There is no arg-max, no v_best, no commit and no refill,
 // and nothing of the handle is written: the record and its meta row are only read, the stream is read through the two
-// resident blocks.
+// resident blocks.  What follows the staging is spelled as MSB_AFTER_STATE, which the replay of logged games expands
+// per kept row as well (replay_log.h replay_game<U, true>).
 // k_env_after (env_after.hip) gives every slot to one wavefront.
 #pragma once
 #include "env.h"
@@ -100,6 +101,94 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
     __syncthreads();                                                                                  \
   }
 
+// The look-ahead of the state column 0 holds, into entry row_ of o_ (a monsoon_env_after with K_ entries per row): game
+// g_'s record with the stream window at rng_ attached, v_par_ its image in registers, ls_ its legal set (rem is used up).
+// n_legal, the draw hint, the "before" features, then the passes; column 0 is a candidate's afterwards.  For the whole
+// wave, where b, pe, ce, priv and L are what after_slot calls so.  Spelled in place like MSB_EACH_GRANULE, for after_slot
+// and replay_game (replay_log.h): as a function template it reordered k_env_after's code object (scripts/isa_diff.sh).
+#if MSB_AFTER_OBS_COOP
+#define MSB_AFTER_OBS_(o_, K_, row_, lane_)                                                                                                           \
+      const unsigned long long part = __ballot(ok);   /* (candidates sit on lanes 0 .. U-1) */                                                        \
+      MSB_AS_LDS uint8_t* ord = (MSB_AS_LDS uint8_t*)(uintptr_t)L::CF;   /* (the features have left CF, the stacks are empty) */                      \
+      for (int c = 0; c < n_act; c++) {                                                                                                               \
+        if (!((part >> c) & 1)) continue;   /* (uniform) */                                                                                           \
+        typename L::SubEngine se;                                                                                                                     \
+        se.m.c16 = c * 16;                                                                                                                            \
+        MSB_OBS_DECK_ORDER(se, lane_, ord)   /* (its first barrier: the order of the candidate before has been read) */                               \
+        int32_t* out = o_.obs + (row_ * K_ + base + c) * MONSOON_OBS_INTS;                                                                            \
+        for (int i = lane_; i < MONSOON_OBS_INTS; i += 64) out[i] = obs_word(se, i, ord);                                                             \
+      }
+#else
+#define MSB_AFTER_OBS_(o_, K_, row_, lane_) if (ok) ce.observe(o_.obs + e * MONSOON_OBS_INTS);
+#endif
+#define MSB_AFTER_STATE(o_, K_, row_, g_, rng_, ls_, v_par_, lane_)                                                                                   \
+  {                                                                                                                                                   \
+  const int n_legal = ls_.n;                                                                                                                          \
+  const int n_do = n_legal < K_ ? n_legal : K_;   /* the afterstates this call hands out */                                                           \
+  if (lane_ == 0) o_.n_legal[row_] = n_legal;                                                                                                         \
+  for (int k = n_do + lane_; k < K_; k += 64) (o_.action + row_ * K_)[k] = 255;                                                                       \
+  L::draw_hint(pe, b, g_, rng_, ls_.mask[2], lane_);                                                                                                  \
+  if (o_.before_features && !pe.observation_raises()) {   /* (uniform) */                                                                             \
+    if constexpr (!L::COOP) {   /* (as play_game spells it) */                                                                                        \
+      if (lane_ == 0) pe.features(L::wf() + 10);                                                                                                      \
+    } else {                                                                                                                                          \
+      int sl = lane_;   /* (opaque, as in play_game) */                                                                                               \
+      asm volatile("" : "+v"(sl));                                                                                                                    \
+      coop_features<U>(pe, sl, true, L::wf() + 10);                                                                                                   \
+    }                                                                                                                                                 \
+    __syncthreads();                                                                                                                                  \
+    if (lane_ < 10) o_.before_features[row_ * 10 + lane_] = L::wf()[10 + lane_];                                                                      \
+  }                                                                                                                                                   \
+  __syncthreads();                                                                                                                                    \
+                                                                                                                                                      \
+  for (int base = 0; base < n_do; base += U) {                                                                                                        \
+    const int n_act = n_do - base < U ? n_do - base : U;                                                                                              \
+    {   /* clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use */                        \
+      __syncthreads();                                                                                                                                \
+      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane_, priv[gr_ * U + col] = v_par_[j_])                                         \
+      __syncthreads();                                                                                                                                \
+    }                                                                                                                                                 \
+    const bool active = lane_ < n_act;                                                                                                                \
+    const size_t e = row_ * K_ + base + (active ? lane_ : 0);   /* this candidate's entry */                                                          \
+    int a = 255;                                                                                                                                      \
+    pass_actions(ls_.rem, n_act, [&](const int l, const int act) { a = lane_ == l ? act : a; });                                                      \
+    int status = 0;                                                                                                                                   \
+    if (active) {                                                                                                                                     \
+      const int rd = ce.step(a);                                                                                                                      \
+      const int f = ce.fault();                                                                                                                       \
+      /* a step that raised leaves no reward and no winner: 0 and -2 (include/monsoon.h) */                                                           \
+      int reward = 0, winner = -2;                                                                                                                    \
+      if (!f) {                                                                                                                                       \
+        reward = rd & 1;                                                                                                                              \
+        if (ce.have_winner()) winner = ce.winner_of(ce.pl_base(0), ce.pl_base(1));                                                                    \
+      }                                                                                                                                               \
+      status = f ? f : (ce.observation_raises() ? FAULT_INT_CARD : 0);                                                                                \
+      o_.action[e] = (uint8_t)a;                                                                                                                      \
+      if (o_.status) o_.status[e] = (uint8_t)status;                                                                                                  \
+      if (o_.reward) o_.reward[e] = (int8_t)reward;                                                                                                   \
+      if (o_.winner) o_.winner[e] = (int8_t)winner;                                                                                                   \
+    }                                                                                                                                                 \
+    const bool ok = active && status == 0;   /* the successors that have features and an observation */                                               \
+    if (o_.features) {   /* (uniform) */                                                                                                              \
+      if constexpr (!L::COOP) {                                                                                                                       \
+        double fa[10];                                                                                                                                \
+        if (ok) L::cand_features(ce, fa, o_.features + e * 10);                                                                                       \
+      } else {                                                                                                                                        \
+        const unsigned long long part = __ballot(ok);   /* (candidates sit on lanes 0 .. U-1) */                                                      \
+        if (part) {                                                                                                                                   \
+          L::coop_cand_features(part, lane_, L::CF);   /* (the stacks are empty once the pass has stepped) */                                         \
+          __syncthreads();                                                                                                                            \
+          for (int i = lane_; i < U * 10; i += 64)                                                                                                    \
+            if ((part >> (i / 10)) & 1) o_.features[(row_ * K_ + base) * 10 + i] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[i];                   \
+        }                                                                                                                                             \
+      }                                                                                                                                               \
+    }                                                                                                                                                 \
+    if (o_.obs) {   /* (uniform) 2 160 bytes per successor: the bulk of what this call writes */                                                      \
+      MSB_AFTER_OBS_(o_, K_, row_, lane_)                                                                                                             \
+    }                                                                                                                                                 \
+  }                                                                                                                                                   \
+  }
+
 // The afterstates of slot g by the calling wavefront; K = max_after.  Call with the whole wave.
 template <int U>
 __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after& o, const int K, const int g, const int lane) {
@@ -126,83 +215,7 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
   MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])
 
   LegalSet ls = legal_set(pe);
-  const int n_legal = ls.n;
-  const int n_do = n_legal < K ? n_legal : K;   // the afterstates this call hands out
-  if (lane == 0) o.n_legal[g] = n_legal;
-  for (int k = n_do + lane; k < K; k += 64) act_row[k] = 255;
-  L::draw_hint(pe, b, g, meta.rng, ls.mask[2], lane);
-  if (o.before_features && !pe.observation_raises()) {   // (uniform)
-    if constexpr (!L::COOP) {   // (as play_game spells it)
-      if (lane == 0) pe.features(L::wf() + 10);
-    } else {
-      int sl = lane;   // (opaque, as in play_game)
-      asm volatile("" : "+v"(sl));
-      coop_features<U>(pe, sl, true, L::wf() + 10);
-    }
-    __syncthreads();
-    if (lane < 10) o.before_features[(size_t)g * 10 + lane] = L::wf()[10 + lane];
-  }
-  __syncthreads();
-
-  for (int base = 0; base < n_do; base += U) {
-    const int n_act = n_do - base < U ? n_do - base : U;
-    {   // clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use
-      __syncthreads();
-      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
-      __syncthreads();
-    }
-    const bool active = lane < n_act;
-    const size_t e = (size_t)g * K + base + (active ? lane : 0);   // this candidate's entry
-    int a = 255;
-    pass_actions(ls.rem, n_act, [&](const int l, const int act) { a = lane == l ? act : a; });
-    int status = 0;
-    if (active) {
-      const int rd = ce.step(a);
-      const int f = ce.fault();
-      // a step that raised leaves no reward and no winner: 0 and -2 (include/monsoon.h)
-      int reward = 0, winner = -2;
-      if (!f) {
-        reward = rd & 1;
-        if (ce.have_winner()) winner = ce.winner_of(ce.pl_base(0), ce.pl_base(1));
-      }
-      status = f ? f : (ce.observation_raises() ? FAULT_INT_CARD : 0);
-      o.action[e] = (uint8_t)a;
-      if (o.status) o.status[e] = (uint8_t)status;
-      if (o.reward) o.reward[e] = (int8_t)reward;
-      if (o.winner) o.winner[e] = (int8_t)winner;
-    }
-    const bool ok = active && status == 0;   // the successors that have features and an observation
-    if (o.features) {   // (uniform)
-      if constexpr (!L::COOP) {
-        double fa[10];
-        if (ok) L::cand_features(ce, fa, o.features + e * 10);
-      } else {
-        const unsigned long long part = __ballot(ok);   // (candidates sit on lanes 0 .. U-1)
-        if (part) {
-          L::coop_cand_features(part, lane, L::CF);   // (the stacks are empty once the pass has stepped)
-          __syncthreads();
-          for (int i = lane; i < U * 10; i += 64)
-            if ((part >> (i / 10)) & 1) o.features[((size_t)g * K + base) * 10 + i] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[i];
-        }
-      }
-    }
-    if (o.obs) {   // (uniform) 2 160 bytes per successor: the bulk of what this call writes
-#if MSB_AFTER_OBS_COOP
-      const unsigned long long part = __ballot(ok);   // (candidates sit on lanes 0 .. U-1)
-      MSB_AS_LDS uint8_t* ord = (MSB_AS_LDS uint8_t*)(uintptr_t)L::CF;   // (the features have left CF, the stacks are empty)
-      for (int c = 0; c < n_act; c++) {
-        if (!((part >> c) & 1)) continue;   // (uniform)
-        typename L::SubEngine se;
-        se.m.c16 = c * 16;
-        MSB_OBS_DECK_ORDER(se, lane, ord)   // (its first barrier: the order of the candidate before has been read)
-        int32_t* out = o.obs + ((size_t)g * K + base + c) * MONSOON_OBS_INTS;
-        for (int i = lane; i < MONSOON_OBS_INTS; i += 64) out[i] = obs_word(se, i, ord);
-      }
-#else
-      if (ok) ce.observe(o.obs + e * MONSOON_OBS_INTS);
-#endif
-    }
-  }
+  MSB_AFTER_STATE(o, K, (size_t)g, g, meta.rng, ls, v_par, lane)
 }
 
 // k_env_after<U, W> at the build's default variant (env_after.hip).

@@ -729,6 +729,7 @@ struct monsoon {
   uint8_t* d_replay = nullptr;
   size_t replay_cap = 0;   // bytes
   int replay_waves = 0;    // resident wavefronts of k_replay_log (queried once per handle)
+  int replay_after_waves = 0;   // ... of k_replay_after
   // kernel timing: event pairs are created once and reused
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   std::vector<char> ev_split;   // pair i times a split call: its end event lies on the last sub-batch's stream (drain_timing)
@@ -1905,7 +1906,8 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
 // Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.
 static int replay_batch(monsoon_t* h, int base, int n, const monsoon_match* matches, const uint8_t* deck_pairs, const uint8_t* log_action,
                         int32_t log_stride, const int32_t* log_steps, const uint8_t* keep, const int64_t* row_base, const monsoon_replay_rows& rows,
-                        const layout::Replay& l, uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault) {
+                        const layout::Replay& l, uint8_t* out_status, int32_t* out_replayed, uint8_t* out_fault, const monsoon_replay_after* after,
+                        int max_after) {
   std::vector<uint32_t> seeds(n);
   std::vector<uint8_t> decks((size_t)n * 24);
   std::vector<int32_t> p1(n), p2(n);
@@ -1933,14 +1935,18 @@ static int replay_batch(monsoon_t* h, int base, int n, const monsoon_match* matc
   if (keep) HIP_TRY(h, hipMemcpyAsync(d + l.keep, keep + at, entries, hipMemcpyHostToDevice, h->stream));
   const ReplayArgs ra = {rows, d + l.action, keep ? d + l.keep : nullptr, (const int32_t*)(d + l.steps), (const int64_t*)(d + l.base),
                          d + l.status, (int32_t*)(d + l.replayed), d + l.fault, log_stride};
-  const ReplayOps* o = monsoon_replay_log_ops();
+  // with candidates: k_replay_after, the same grid rules, its own occupancy
+  const ReplayOps* ol = monsoon_replay_log_ops();
+  const ReplayAfterOps* oa = monsoon_replay_after_ops();
+  const KernelOps* o = after ? static_cast<const KernelOps*>(oa) : ol;
+  int& waves = after ? h->replay_after_waves : h->replay_waves;
   const int lds = o->lds_bytes + g_lds_pad;
-  if (!h->replay_waves) {
-    rc = resident_waves(h, o->occupancy, lds, 4096, &h->replay_waves);
+  if (!waves) {
+    rc = resident_waves(h, o->occupancy, lds, 4096, &waves);
     if (rc) return rc;
   }
   // the persistent form needs a wavefront for every one of its POP_PARTS ranges (launch_play)
-  int grid = h->replay_waves;
+  int grid = waves;
   const int pers = (g_persistent && grid < n && grid >= POP_PARTS) ? 1 : 0;
   if (!pers) grid = n;   // a wavefront per game
   rc = grow_ovf(h, (size_t)grid * o->lanes);
@@ -1948,7 +1954,10 @@ static int replay_batch(monsoon_t* h, int base, int n, const monsoon_match* matc
   size_t slot = 0;
   rc = timing_begin(h, &slot);
   if (rc) return rc;
-  o->launch(grid, lds, h->stream, h->b, ra, n, pers, h->parity[0]);
+  if (after)
+    oa->launch(grid, lds, h->stream, h->b, ra, *after, max_after, n, pers, h->parity[0]);
+  else
+    ol->launch(grid, lds, h->stream, h->b, ra, n, pers, h->parity[0]);
   if (pers) h->parity[0] ^= 1;   // (only a persistent launch consumes its counter set: launch_play)
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev_pool[slot].second, h->stream));
@@ -1959,17 +1968,25 @@ static int replay_batch(monsoon_t* h, int base, int n, const monsoon_match* matc
   return drain_timing(h);
 }
 
-int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks,
-                              const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps, const uint8_t* keep,
-                              const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows, uint8_t* out_status, int32_t* out_replayed,
-                              uint8_t* out_fault) {
-  const char* who = "monsoon_replay_logged_dev";
+// monsoon_replay_logged_dev (after == nullptr) and monsoon_replay_logged_after_dev: one set of checks, one batch loop.
+static int replay_impl(monsoon_t* h, const char* who, const monsoon_match* matches, int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks,
+                       const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps, const uint8_t* keep,
+                       const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows, uint8_t* out_status, int32_t* out_replayed,
+                       uint8_t* out_fault, const monsoon_replay_after* after, int32_t max_after) {
   if (!h) return MONSOON_ERR_ARG;
   if (!matches || !deck_pairs || !log_action || !log_steps || n_matches <= 0 || n_decks <= 0 || log_stride <= 0) return bad_arg(h, who, "bad argument");
   if (!rows || !rows->action) return bad_arg(h, who, "rows and rows->action are required");
   if (((uintptr_t)rows->obs | (uintptr_t)rows->legal | (uintptr_t)rows->game | (uintptr_t)rows->step) & 3)
     return bad_arg(h, who, "obs, legal, game and step must be 4-byte aligned");
   if ((uintptr_t)rows->state_hash & 7) return bad_arg(h, who, "state_hash must be 8-byte aligned");
+  if (after) {
+    if (max_after < 1 || max_after > MONSOON_NUM_ACTIONS) return bad_arg(h, who, "max_after outside 1..156");
+    if (!after->n_legal || !after->action) return bad_arg(h, who, "after->n_legal and after->action are required");
+    if (((uintptr_t)after->n_legal | (uintptr_t)after->obs) & 3) return bad_arg(h, who, "after->n_legal and after->obs must be 4-byte aligned");
+    if ((uintptr_t)after->chosen & 1) return bad_arg(h, who, "after->chosen must be 2-byte aligned");
+    if (((uintptr_t)after->features | (uintptr_t)after->before_features) & 7)
+      return bad_arg(h, who, "after->features and after->before_features must be 8-byte aligned");
+  }
   // The whole schedule, every deck and the log's shape are checked, and the rows counted, before anything is loaded or launched.
   std::vector<int64_t> row_base(n_matches);
   int64_t total = 0;
@@ -1998,11 +2015,27 @@ int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_
   for (int base = 0; base < n_matches; base += cap) {
     const int n = n_matches - base < cap ? n_matches - base : cap;
     rc = replay_batch(h, base, n, matches, deck_pairs, log_action, log_stride, log_steps, keep, row_base.data(), *rows, l, out_status,
-                      out_replayed, out_fault);
+                      out_replayed, out_fault, after, max_after);
     if (rc) return rc;
   }
   if (out_rows) *out_rows = total;
   return MONSOON_OK;
+}
+
+int monsoon_replay_logged_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks,
+                              const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps, const uint8_t* keep,
+                              const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows, uint8_t* out_status, int32_t* out_replayed,
+                              uint8_t* out_fault) {
+  return replay_impl(h, "monsoon_replay_logged_dev", matches, n_matches, deck_pairs, n_decks, log_action, log_stride, log_steps, keep, rows,
+                     rows_cap, out_rows, out_status, out_replayed, out_fault, nullptr, 0);
+}
+
+int monsoon_replay_logged_after_dev(monsoon_t* h, const monsoon_match* matches, int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks,
+                                    const uint8_t* log_action, int32_t log_stride, const int32_t* log_steps, const uint8_t* keep,
+                                    const monsoon_replay_rows* rows, int64_t rows_cap, int64_t* out_rows, uint8_t* out_status,
+                                    int32_t* out_replayed, uint8_t* out_fault, const monsoon_replay_after* after, int32_t max_after) {
+  return replay_impl(h, after ? "monsoon_replay_logged_after_dev" : "monsoon_replay_logged_dev", matches, n_matches, deck_pairs, n_decks,
+                     log_action, log_stride, log_steps, keep, rows, rows_cap, out_rows, out_status, out_replayed, out_fault, after, max_after);
 }
 
 int monsoon_rollout_faults(monsoon_t* h, uint8_t* out, int32_t n_matches) {

@@ -6,6 +6,8 @@
 // is to play, which consumes the stream as the rollout did -- before the cursor is committed the way play_game's commit
 // does.  No decision is recomputed: no clone, no features, no arg-max; columns 1 .. U-1 stay unused.
 // k_replay_log (replay_log.hip) gives every game to one wavefront.
+// replay_game<U, true> (monsoon_replay_logged_after_dev, k_replay_after in replay_after.hip) puts after_slot's look-ahead
+// (env_after.h MSB_AFTER_STATE) inside it: a kept entry also gets the afterstates of the state its row shows.
 #pragma once
 #include "env_after.h"
 
@@ -64,8 +66,10 @@ __device__ MSB_INL void replay_row(const DevBuffers& b, const monsoon_replay_row
 }
 
 // Game g of the batch by the calling wavefront: its log entries, one committed step each.  Call with the whole wave.
-template <int U>
-__device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, const int g, const int lane) {
+// AFTER: every kept entry's row also gets its K afterstates (oa, with the row's rank among the legal actions in chosen).
+template <int U, bool AFTER = false>
+__device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, const int g, const int lane,
+                                    const monsoon_env_after& oa = monsoon_env_after{}, int16_t* const chosen = nullptr, const int K = 0) {
   typedef PlayLds<U> L;
   GameMeta meta = b.meta[g];
   MSB_AS_LDS u32x4* priv = L::priv();
@@ -106,6 +110,26 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
     const bool bot = (pe.local() == 0 ? meta.p1 : meta.p2) < 0;   // (uniform) the scripted bot is to play
     if (!keep || keep[k]) {
       replay_row<U>(b, ra.rows, pe, ls, meta, g, r, k, a, bot, lane);
+      if constexpr (AFTER) {
+        // The look-ahead of the row's state.  Its clones overwrite column 0, the live record here: the record (stream window
+        // attached) waits in registers and is staged again before lane 0 steps it, so the look-ahead consumes nothing --
+        // cursor, stream blocks and meta are the committed ones.  The draw hint it sets is cleared again: the committed
+        // REPLACE and the bot draw serially.  (replay_row's order has left the stack area behind the look-ahead's barriers.)
+        MSB_EACH_GRANULE(L::GPL, lane, v_rec[j_] = priv[gr_ * U])
+        if (chosen && lane == 0) {   // the rank of a in the ascending legal list (PASS may be outside it)
+          const int rank = __popcll(word & ((1ull << (a & 63)) - 1)) + (a >= 64 ? __popcll(ls.mask[0]) : 0) + (a >= 128 ? __popcll(ls.mask[1]) : 0);
+          chosen[r] = (int16_t)(((word >> (a & 63)) & 1) ? rank : -1);
+        }
+        if (oa.before_features && pe.observation_raises() && lane < 10) oa.before_features[r * 10 + lane] = 0.0;   // (the others: below)
+        LegalSet la = ls;
+        MSB_AFTER_STATE(oa, K, r, g, meta.rng, la, v_rec, lane)
+        meta.lookahead += (uint32_t)(ls.n < K ? ls.n : K);   // the candidates stepped; no decision is counted
+        __syncthreads();   // the last pass's successors have been read out of the columns
+        MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_rec[j_])
+        if constexpr (L::COOP_DRAW) {
+          if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;
+        }
+      }
       r++;
     }
     __syncthreads();   // the row has been read out of column 0 and the order out of the stack area
@@ -182,5 +206,12 @@ struct ReplayOps : KernelOps {
   void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, ReplayArgs ra, int n, int persistent, int parity);
 };
 const ReplayOps* monsoon_replay_log_ops();
+
+// k_replay_after<U, W> at the build's default variant (replay_after.hip): k_replay_log with the look-ahead of every kept row.
+struct ReplayAfterOps : KernelOps {
+  void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, ReplayArgs ra, monsoon_replay_after after, int max_after, int n,
+                 int persistent, int parity);
+};
+const ReplayAfterOps* monsoon_replay_after_ops();
 
 }  // namespace msbk

@@ -350,10 +350,12 @@ class BatchEngine:
         self.n = len(m) - ((len(m) - 1) // batch) * batch   # the handle now holds the last batch of the schedule
         return (counts, results, steps) if want_results else counts
 
-    def replay_logged(self, matches, deck_pairs, log_action, log_steps, rows, rows_cap, keep=None):
+    def replay_logged(self, matches, deck_pairs, log_action, log_steps, rows, rows_cap, keep=None, after=None, max_after=0):
         """monsoon_replay_logged_dev: the logged games played again, one committed step per entry, the state before every
         kept entry written to row (kept entries before it) of `rows` -- a _lib.ReplayRows of DEVICE pointers with room for
         rows_cap rows.  log_action uint8[n][stride], log_steps int32[n], keep uint8[n][stride] or None (every entry).
+        after = a _lib.ReplayAfter of DEVICE pointers with max_after entries per row (monsoon_replay_logged_after_dev): every
+        kept entry's row also gets the afterstates of its state.
         Returns (rows written, status uint8[n] (_lib.REPLAY_*), replayed int32[n], fault uint8[n])."""
         _, m, deck_pairs = self._rollout_args(np.zeros((1, 10)), matches, deck_pairs)
         log_action = np.ascontiguousarray(log_action, dtype=np.uint8)
@@ -366,10 +368,11 @@ class BatchEngine:
                 raise ValueError("replay_logged: keep has the shape of the log")
         status, replayed = np.zeros(len(m), dtype=np.uint8), np.zeros(len(m), dtype=np.int32)
         fault, n_rows = np.zeros(len(m), dtype=np.uint8), ctypes.c_int64(0)
-        self._ck(self.lib.monsoon_replay_logged_dev(self.h, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs), _ptr(log_action),
-                                                    log_action.shape[1], _ptr(log_steps), _ptr(keep), ctypes.byref(rows), int(rows_cap),
-                                                    ctypes.byref(n_rows), _ptr(status), _ptr(replayed), _ptr(fault)),
-                 "monsoon_replay_logged_dev")
+        entry = "monsoon_replay_logged_dev" if after is None else "monsoon_replay_logged_after_dev"
+        extra = () if after is None else (ctypes.byref(after), int(max_after))
+        self._ck(getattr(self.lib, entry)(self.h, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs), _ptr(log_action),
+                                          log_action.shape[1], _ptr(log_steps), _ptr(keep), ctypes.byref(rows), int(rows_cap),
+                                          ctypes.byref(n_rows), _ptr(status), _ptr(replayed), _ptr(fault), *extra), entry)
         self.n = len(m) - ((len(m) - 1) // self.max_games) * self.max_games   # the handle now holds the last batch
         return n_rows.value, status, replayed, fault
 

@@ -3,7 +3,9 @@
 logged_rollout plays a schedule over the record tiers as fitness.tiered_rollout does and keeps every game's log;
 FitnessEvaluator.logged_games is its entry over an evaluator's own engines; replay plays logged games again through the
 step interface and yields the (state, action) pairs a learner wants; dataset / dataset_batches / step_sides play them
-again on the device (monsoon_replay_logged_dev), games with the scripted bot included, into torch tensors of rows.
+again on the device (monsoon_replay_logged_dev), games with the scripted bot included, into torch tensors of rows; with a
+candidate column (CANDIDATE_COLUMNS) every row also carries the afterstates of its state (monsoon_replay_logged_after_dev),
+which candidates / candidate_mask hand to vec_env.select_actions and to a learner over afterstate features.
 """
 import numpy as np
 
@@ -66,6 +68,14 @@ def replay(engine, matches, deck_pairs, log):
 COLUMNS = {"obs": ("int32", (27, 5, 4)), "legal": ("uint8", (156,)), "obs_raises": ("uint8", ()), "to_play": ("uint8", ()),
            "action": ("uint8", ()), "bot": ("uint8", ()), "game": ("int32", ()), "step": ("int32", ()), "state_hash": ("int64", ())}
 ROW_BYTES = {"obs": 2160, "legal": 156, "obs_raises": 1, "to_play": 1, "action": 1, "bot": 1, "game": 4, "step": 4, "state_hash": 8}
+# ... and of monsoon_replay_after, "K" = max_after: the candidates the row's choice was made among, entry k the k-th legal
+# action in ascending order.  Naming one of them turns the look-ahead on; _CANDIDATE_BASE comes along, as action does.
+CANDIDATE_COLUMNS = {"n_legal": ("int32", ()), "chosen": ("int16", ()), "after_action": ("uint8", ("K",)), "after_status": ("uint8", ("K",)),
+                     "after_reward": ("int8", ("K",)), "after_winner": ("int8", ("K",)), "after_features": ("float64", ("K", 10)),
+                     "before_features": ("float64", (10,)), "after_obs": ("int32", ("K", 27, 5, 4))}
+_CANDIDATE_BASE = ("n_legal", "after_action", "after_status")   # what it takes to read any other candidate column
+_AFTER_FIELD = {"n_legal": "n_legal", "chosen": "chosen", "after_action": "action", "after_status": "status", "after_reward": "reward",
+                "after_winner": "winner", "after_features": "features", "before_features": "before_features", "after_obs": "obs"}
 
 
 def kept_counts(steps, keep=None):
@@ -112,24 +122,45 @@ def outcome(results, game, to_play):
 
 def _want(columns):
     columns = tuple(columns)
-    bad = [c for c in columns if c not in COLUMNS]
+    bad = [c for c in columns if c not in COLUMNS and c not in CANDIDATE_COLUMNS]
     if bad:
-        raise ValueError(f"unknown column(s) {bad}: choose from {tuple(COLUMNS)}")
-    return columns if "action" in columns else columns + ("action",)
+        raise ValueError(f"unknown column(s) {bad}: choose from {tuple(COLUMNS) + tuple(CANDIDATE_COLUMNS)}")
+    if "action" not in columns:
+        columns += ("action",)
+    if any(c in CANDIDATE_COLUMNS for c in columns):
+        columns += tuple(c for c in _CANDIDATE_BASE if c not in columns)
+    return columns
 
 
-def _tensors(engine, names, cap):
+def _max_after(names, max_after):
+    """K of a call over the columns `names`: 0 without a candidate column, else max_after, which must be an integer in 1..156."""
+    if not any(c in CANDIDATE_COLUMNS for c in names):
+        return 0
+    if isinstance(max_after, bool) or not isinstance(max_after, (int, np.integer)) or not 1 <= max_after <= 156:
+        raise ValueError("a candidate column needs max_after, an integer in 1..156")
+    return int(max_after)
+
+
+def _tensors(engine, names, cap, max_after=0):
     import torch
     dev = torch.device("cuda", engine.device)
-    return {c: torch.empty((max(int(cap), 1),) + COLUMNS[c][1], dtype=getattr(torch, COLUMNS[c][0]), device=dev) for c in names}
+    out = {}
+    for c in names:
+        dt, shape = COLUMNS[c] if c in COLUMNS else CANDIDATE_COLUMNS[c]
+        shape = tuple(max_after if d == "K" else d for d in shape)
+        out[c] = torch.empty((max(int(cap), 1),) + shape, dtype=getattr(torch, dt), device=dev)
+    return out
 
 
-def _replay_into(engine, tensors, matches, deck_pairs, action, steps, keep):
-    """One monsoon_replay_logged_dev call into the first rows of `tensors`: (rows, status, replayed, fault)."""
+def _replay_into(engine, tensors, matches, deck_pairs, action, steps, keep, max_after=0):
+    """One monsoon_replay_logged_dev / _after_dev call into the first rows of `tensors`: (rows, status, replayed, fault)."""
     import torch
     torch.cuda.current_stream(tensors["action"].device).synchronize()   # the library works on the handle's stream
-    rows = _lib.ReplayRows(**{c: t.data_ptr() for c, t in tensors.items()})
-    return engine.replay_logged(matches, deck_pairs, action, steps, rows, tensors["action"].shape[0], keep)
+    rows = _lib.ReplayRows(**{c: t.data_ptr() for c, t in tensors.items() if c in COLUMNS})
+    after = None
+    if max_after:
+        after = _lib.ReplayAfter(**{_AFTER_FIELD[c]: t.data_ptr() for c, t in tensors.items() if c in CANDIDATE_COLUMNS})
+    return engine.replay_logged(matches, deck_pairs, action, steps, rows, tensors["action"].shape[0], keep, after, max_after)
 
 
 def _columns_for(columns, results):
@@ -137,6 +168,26 @@ def _columns_for(columns, results):
     if results is not None:
         names += tuple(c for c in ("game", "to_play") if c not in names)
     return names
+
+
+def candidates(d):
+    """The candidate columns of dataset rows as the dict VecEnv.afterstates returns, a row for a slot: action, status,
+    n_legal, and whichever of reward, winner, features, obs the rows carry -- so vec_env.select_actions(candidates(d),
+    values) picks per row among its legal actions as it does per slot.  Views, no copy; works on CPU tensors too."""
+    if "after_action" not in d:
+        raise ValueError("candidates: the rows carry no candidate column (dataset(..., columns=(..., 'after_features'), max_after=K))")
+    names = {"action": "after_action", "status": "after_status", "n_legal": "n_legal", "reward": "after_reward", "winner": "after_winner",
+             "features": "after_features", "obs": "after_obs"}
+    return {k: d[c] for k, c in names.items() if c in d}
+
+
+def candidate_mask(d):
+    """bool [S][K]: the entries of the rows' candidates that exist (k < min(n_legal, K)) and have features and an
+    observation (status == 0) -- what a loss over after_features / after_obs is masked with.  Pure torch."""
+    import torch
+    c = candidates(d)
+    k = c["action"].shape[1]
+    return (torch.arange(k, device=c["action"].device)[None, :] < c["n_legal"][:, None]) & (c["status"] == 0)
 
 
 def _hand_out(tensors, columns, n_rows, results, status, replayed, fault):
@@ -149,7 +200,7 @@ def _hand_out(tensors, columns, n_rows, results, status, replayed, fault):
     return out
 
 
-def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS), results=None):
+def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS), results=None, max_after=64):
     """The (state, action) rows of logged games as torch CUDA tensors, replayed on the device by `engine` (games with the
     scripted bot included: its expert_action runs again and consumes the stream as it did).  One row per entry k <
     log.steps[g] (with keep uint8 / bool [n][T]: per entry with keep[g][k]), in match order, then entry order, holding the
@@ -157,6 +208,17 @@ def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS),
     (_lib.REPLAY_*: 0 = replayed to its last entry), replayed int32[n] and fault uint8[n].  The rows of a game that
     stopped early read action 255 from the stop on; their other columns are unspecified.  results int8[n] (the rollout's)
     adds outcome int8[S]: +1 / 0 / -1 from the side to play.
+
+    A name of CANDIDATE_COLUMNS in `columns` turns the look-ahead on (monsoon_replay_logged_after_dev): the row also carries
+    the successor of every legal action of its state, K = max_after (1..156) entries, entry k the k-th legal action in
+    ascending order, in the meaning of VecEnv.afterstates -- n_legal int32[S] (the full count, also beyond K), chosen
+    int16[S] (the rank of `action` in that order, -1 for a PASS outside the legal set), after_action / after_status uint8
+    [S][K], after_reward / after_winner int8[S][K], after_features float64[S][K][10], before_features float64[S][10] (zeros
+    where the row's observation raises), after_obs int32[S][K][27][5][4].  n_legal, after_action and after_status come
+    along, as action does; entries k >= min(n_legal, K) read after_action 255 and are otherwise unspecified, as are the
+    features and observation of an entry with after_status != 0 (candidate_mask).  Per row that is 80 * K bytes of
+    after_features and 2 160 * K of after_obs (K = 64: 5 KB and 138 KB), so ask for after_obs through dataset_batches.
+    Without such a name max_after is not read and the call is what it was.
 
     torch has to be imported before the engine is created, for the reason VecEnv.__init__ gives (it has to load its own
     ROCm runtime first): `import torch` before the first BatchEngine(...) of the process."""
@@ -167,17 +229,19 @@ def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS),
     if log.action.shape[0] != len(matches):
         raise ValueError("dataset: one log row per match")
     _, total = row_bases(log.steps, keep)
-    tensors = _tensors(engine, _columns_for(columns, results), total)
-    n_rows, status, replayed, fault = _replay_into(engine, tensors, matches, deck_pairs, log.action, log.steps, keep)
+    names = _columns_for(columns, results)
+    k_after = _max_after(names, max_after)
+    tensors = _tensors(engine, names, total, k_after)
+    n_rows, status, replayed, fault = _replay_into(engine, tensors, matches, deck_pairs, log.action, log.steps, keep, k_after)
     return _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
 
 
-def dataset_batches(engine, matches, deck_pairs, log, max_rows, keep=None, columns=tuple(COLUMNS), results=None):
+def dataset_batches(engine, matches, deck_pairs, log, max_rows, keep=None, columns=tuple(COLUMNS), results=None, max_after=64):
     """dataset over a log too large for one set of tensors (65 536 games are about 30 GB of observations): a generator over
     runs of whole consecutive games whose rows fit max_rows (batch_cuts), each item dataset's dict for that run plus
     games = (g0, g1); game holds the index into the whole schedule.  ONE set of tensors is allocated and every item is a
     view of it: the next item overwrites the one before, so use or copy an item before asking for the next.
-    ValueError if one game alone has more than max_rows rows."""
+    Candidate columns and max_after as in dataset.  ValueError if one game alone has more than max_rows rows."""
     import torch
     if not torch.cuda.is_available():
         raise _lib.MonsoonError("dataset_batches: torch sees no device -- import torch before the first BatchEngine is created")
@@ -185,10 +249,12 @@ def dataset_batches(engine, matches, deck_pairs, log, max_rows, keep=None, colum
     counts = kept_counts(log.steps, keep)
     cuts = batch_cuts(counts, max_rows)
     cap = max((int(counts[a:b].sum()) for a, b in cuts), default=0)
-    tensors = _tensors(engine, _columns_for(columns, results), cap)
+    names = _columns_for(columns, results)
+    k_after = _max_after(names, max_after)
+    tensors = _tensors(engine, names, cap, k_after)
     for a, b in cuts:
         n_rows, status, replayed, fault = _replay_into(engine, tensors, matches[a:b], deck_pairs, log.action[a:b], log.steps[a:b],
-                                                        None if keep is None else np.asarray(keep)[a:b])
+                                                        None if keep is None else np.asarray(keep)[a:b], k_after)
         if "game" in tensors:
             tensors["game"][:n_rows] += a
         item = _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
