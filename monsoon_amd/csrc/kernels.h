@@ -37,6 +37,7 @@
 #include "canon.h"
 #include "coop_features.h"
 #include "coop_draw.h"
+#include "coop_legal.h"
 #include "pass_glue.h"
 
 namespace msbk {
@@ -286,9 +287,18 @@ struct LegalSet {
   uint64_t mask[3], rem[3];
   int n;
 };
+// The whole wave computes it from tile and hand masks (coop_legal.h) on the standard record; the extended records keep
+// the serial legal_mask_v(), as they keep the serial features and draw.  -DMSB_COOP_LEGAL=0 builds the serial form everywhere.
+#if MSB_COOP_LEGAL && !(defined(MSB_EXT) && MSB_EXT)
+constexpr bool COOP_LEGAL = SG <= 64;
+#else
+constexpr bool COOP_LEGAL = false;
+#endif
 template <class E>
 __device__ MSB_INL LegalSet legal_set(E& pe) {
-  const msb_u64x4 lm = pe.legal_mask_v();
+  msb_u64x4 lm;
+  if constexpr (COOP_LEGAL) lm = coop_legal_v<E>();
+  else lm = pe.legal_mask_v();
   const uint64_t m0 = uni64(lm[0]), m1 = uni64(lm[1]), m2 = uni64(lm[2]);
   const int n = __popcll(m0) + __popcll(m1) + __popcll(m2);
   return LegalSet{{m0, m1, m2}, {m0, m1, m2}, n};
@@ -457,8 +467,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     }
 #if defined(MSB_STUDY_LEGAL)
     {   // study build (scripts/step_cost.sh): the legal mask computed once more
-      msb_u64x4 lm2 = pe.legal_mask_v();
-      asm volatile("" : : "v"(lm2[0]), "v"(lm2[1]), "v"(lm2[2]) : "memory");
+      const LegalSet ls2 = legal_set(pe);   // (in the form this build uses)
+      asm volatile("" : : "s"(ls2.mask[0]), "s"(ls2.mask[1]), "s"(ls2.mask[2]) : "memory");
     }
 #endif
     LegalSet ls = legal_set(pe);

@@ -1097,16 +1097,49 @@ struct Engine {
     PList r_ = get_targets_impl(pov, t, exclude_pk);
     return r_;
   }
-  MSB_HD MSB_A_TARGETS PList get_targets_impl(int pov, Tgt t, int exclude_pk) {
-    MSB_SCOPE(PS_GET_TARGETS);
-    PList out;
-    out.clear();
-    const bool asc = (pov == local());
+  // The per-entity predicate of Board.get_targets (board.py:167-204) over the entity's granule g: kind, side, type /
+  // xtype / hero, status / xstatus and strength limit.  The one statement of it: get_targets_hit below visits the
+  // occupied tiles one after the other with it, coop_legal.h gives every tile a lane of its own.
+  MSB_HD MSB_INL bool target_matches(const msb_u32x4 g, const int pov, const Tgt t) const {
     const int kind = tg_kind(t), side = tg_side(t), limit = tg_limit(t);
     const int types = tg_types(t), xtypes = tg_xtypes(t), status = tg_status(t), xstatus = tg_xstatus(t);
     const bool want_types = (types | xtypes | (tg_non_hero(t) ? 1 : 0)) != 0;
-    // Pass 1: visit only the occupied tiles and collect the matching ones as a tile bit mask (the board is
-    // read as five 32-bit rows; one 16-byte LDS read per entity).  Pass 2 emits them in iteration order.
+    int str = (int)(int16_t)(g[2] >> 16);
+    if (str <= 0) return false;
+    int c = (int)(g[0] & 0xff);
+    bool is_unit = ((g[3] >> 24) & EK_UNIT) != 0;
+    bool strength_ok = limit == LIMIT_NONE || str <= limit;
+    bool ok;
+    if (is_unit) {
+      int ty = want_types ? card_types(c) : 0;   // table lookup only for type filters
+      bool type_ok = types == 0 || (ty & types) != 0;
+      bool xtype_ok = xtypes == 0 || (ty & xtypes) == 0;
+      bool hero_ok = !tg_non_hero(t) || !(ty & (1 << UT_HERO));
+      int stm = 0;
+      if (status | xstatus) {
+        for (int s = 0; s < 4; s++)
+          if ((g[1] >> (8 * s)) & 0xff) stm |= 1 << s;
+        if (g[2] & 0xff) stm |= 1 << 4;
+      }
+      bool st_ok = status == 0 || (stm & status) != 0;
+      bool xst_ok = xstatus == 0 || (stm & xstatus) == 0;
+      ok = type_ok && xtype_ok && hero_ok && st_ok && xst_ok && strength_ok && (kind == TK_ANY || kind == TK_UNIT);
+    } else {
+      ok = strength_ok && (kind == TK_ANY || kind == TK_STRUCTURE);
+    }
+    int own = (int)((g[0] >> 8) & EF_OWNER);
+    bool side_ok = side == TS_ANY || (side == TS_FRIENDLY && own == pov) || (side == TS_ENEMY && own != pov);
+    return ok && side_ok;
+  }
+  // Which bases a descriptor adds behind the tiles: b0 the point of view's own, b1 the other one (board.py:196-203)
+  MSB_HD MSB_INL static int target_bases(const Tgt t) {
+    if (!tg_base(t)) return 0;
+    const int side = tg_side(t);
+    return ((side == TS_FRIENDLY || side == TS_ANY) ? 1 : 0) | ((side == TS_ENEMY || side == TS_ANY) ? 2 : 0);
+  }
+  // Pass 1 of get_targets: visit only the occupied tiles and collect the matching ones as a tile bit mask (the board is
+  // read as five 32-bit rows; one 16-byte LDS read per entity).
+  MSB_HD MSB_INL uint32_t get_targets_hit(const int pov, const Tgt t) const {
     const uint32_t r0 = board_row(0), r1 = board_row(1), r2 = board_row(2), r3 = board_row(3), r4 = board_row(4);
     uint32_t occ = row_occ4(r0) | (row_occ4(r1) << 4) | (row_occ4(r2) << 8) | (row_occ4(r3) << 12) | (row_occ4(r4) << 16);
     const unsigned long long b01 = (unsigned long long)r0 | ((unsigned long long)r1 << 32);
@@ -1118,33 +1151,17 @@ struct Engine {
       const unsigned long long bw = tile < 8 ? b01 : (tile < 16 ? b23 : (unsigned long long)r4);
       const int e = (int)((bw >> (8 * (tile & 7))) & 0xff);
       const msb_u32x4 g = m.ld128g(eg(e));   // the whole entity in one LDS read
-      int str = (int)(int16_t)(g[2] >> 16);
-      if (str <= 0) continue;
-      int c = (int)(g[0] & 0xff);
-      bool is_unit = ((g[3] >> 24) & EK_UNIT) != 0;
-      bool strength_ok = limit == LIMIT_NONE || str <= limit;
-      bool ok;
-      if (is_unit) {
-        int ty = want_types ? card_types(c) : 0;   // table lookup only for type filters
-        bool type_ok = types == 0 || (ty & types) != 0;
-        bool xtype_ok = xtypes == 0 || (ty & xtypes) == 0;
-        bool hero_ok = !tg_non_hero(t) || !(ty & (1 << UT_HERO));
-        int stm = 0;
-        if (status | xstatus) {
-          for (int s = 0; s < 4; s++)
-            if ((g[1] >> (8 * s)) & 0xff) stm |= 1 << s;
-          if (g[2] & 0xff) stm |= 1 << 4;
-        }
-        bool st_ok = status == 0 || (stm & status) != 0;
-        bool xst_ok = xstatus == 0 || (stm & xstatus) == 0;
-        ok = type_ok && xtype_ok && hero_ok && st_ok && xst_ok && strength_ok && (kind == TK_ANY || kind == TK_UNIT);
-      } else {
-        ok = strength_ok && (kind == TK_ANY || kind == TK_STRUCTURE);
-      }
-      int own = (int)((g[0] >> 8) & EF_OWNER);
-      bool side_ok = side == TS_ANY || (side == TS_FRIENDLY && own == pov) || (side == TS_ENEMY && own != pov);
-      if (ok && side_ok) hit |= 1u << tile;
+      if (target_matches(g, pov, t)) hit |= 1u << tile;
     }
+    return hit;
+  }
+  MSB_HD MSB_A_TARGETS PList get_targets_impl(int pov, Tgt t, int exclude_pk) {
+    MSB_SCOPE(PS_GET_TARGETS);
+    PList out;
+    out.clear();
+    const bool asc = (pov == local());
+    uint32_t hit = get_targets_hit(pov, t);
+    // Pass 2 emits them in iteration order:
     // ascending tiles for the local point of view, descending for the remote one (board.py:160-166)
     {
       unsigned long long w0 = 0, w1 = 0;
@@ -1159,11 +1176,11 @@ struct Engine {
       }
       out.w = msb_u64x4{w0, w1, 0ull, (unsigned long long)n};
     }
-    if (tg_base(t)) {
+    if (const int bases = target_bases(t)) {
       P friendly = asc ? P{-1, 5} : P{-1, -1};
       P enemy = asc ? P{-1, -1} : P{-1, 5};
-      if (side == TS_FRIENDLY || side == TS_ANY) out.push(friendly);
-      if (side == TS_ENEMY || side == TS_ANY) out.push(enemy);
+      if (bases & 1) out.push(friendly);
+      if (bases & 2) out.push(enemy);
     }
     if (exclude_pk != PK_NONE) {
       int m = out.n();

@@ -177,6 +177,11 @@ constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
 #ifndef MSB_COOP_DRAW
 #define MSB_COOP_DRAW 1
 #endif
+// The legal set of a decision by the whole wave (coop_legal.h, kernels.h legal_set): standard record only.  0 builds the
+// serial legal_mask_v() everywhere.
+#ifndef MSB_COOP_LEGAL
+#define MSB_COOP_LEGAL 1
+#endif
 constexpr int LDS_RECORDS = WK_OVF_LDS + 16;         // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
