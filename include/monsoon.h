@@ -233,6 +233,57 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
                            int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                            int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log);
 
+/* A logged rollout whose heuristic decisions may explore (epsilon-greedy), with the greedy choice kept in the log:
+ * monsoon_rollout_logged's contract word for word, with one change at a heuristic decision.  Let k be the committed-step
+ * index of the decision (its entry of the log), n_legal >= 1 its legal count and s the side to play.  The decision
+ * EXPLORES when bit s of ex->sides is set, and ex->until_step <= 0 or k < ex->until_step, and draw0 < ex->threshold; it
+ * then commits the r-th action of the ascending legal list instead of the arg-max:
+ *
+ *   draw0 = hash32(ex->seed, match.seed, k, 0)
+ *   draw1 = hash32(ex->seed, match.seed, k, 1)
+ *   r     = ((uint64_t)draw1 * n_legal) >> 32
+ *
+ * hash32 is monsoon_amd/fitness.py's hash32 (32-bit integer arithmetic only), so the host reproduces every draw exactly.
+ * The draws are keyed by the match's seed and the step index -- not by the slot, the batch or the record build:
+ *  - the games per batch never change a game;
+ *  - a game that is played again on a larger record (monsoon_rollout_faults, fitness._ladder) explores exactly as it did
+ *    on the smaller one, step for step, for as long as the two games see the same legal counts;
+ *  - two matches with the same seed share their draws (they differ only through their decks and players): give the
+ *    matches of a schedule distinct seeds, or expect correlated exploration.
+ * What does not change: the arg-max still runs over all candidates; log->score stays the decision's best score
+ * (monsoon_decide's out_score), log->action is what was COMMITTED, log->n_legal the legal count; every legal action is
+ * stepped exactly once (lookahead_steps and decisions count as before) and the commit re-executes nothing -- the committed
+ * successor is the taken candidate's look-ahead record, its fault or raising observation ends the game as a draw with that
+ * code, its features are the next decision's "before" side, exactly as for the arg-max winner.  The scripted bot's steps
+ * never explore.  No draw touches the game's own numpy stream.  out_counts, out_results, out_steps, monsoon_rollout_faults,
+ * monsoon_get_stats and monsoon_state_hash work as after monsoon_rollout_logged and describe the games that were played:
+ * THE COUNTS OF AN EXPLORING CALL ARE NOT FITNESS (an individual that explored did not play its own policy).
+ * xlog (may be NULL, each array may be NULL) adds per entry: greedy, the arg-max action of the decision (what
+ * monsoon_rollout_logged would have logged there); explored, 1 where the draw said "explore" (also when the drawn action
+ * is the greedy one); taken_score, the score of the committed action.
+ * ex == NULL or ex->threshold == 0: no decision explores and every output of monsoon_rollout_logged is what that call
+ * writes, bit for bit; greedy == action, explored == 0 and taken_score == score on decisions.
+ * Device log: an entry takes B = 1 + 8 [score] + 2 [n_legal] + 1 [greedy] + 1 [explored] + 8 [taken_score] bytes, 1 .. 21,
+ * counting the arrays asked for, and a call plays min(max_games, max(1, 256 MiB / (B * max_turns))) games per batch
+ * (without an exploring rule and without an array of xlog the call is monsoon_rollout_logged itself, batch cap included).
+ * The kernel is one more instantiation of the decision loop at the build's default variant (k_play_explore).
+ * MONSOON_ERR_ARG with nothing launched: whatever monsoon_rollout_logged refuses, and ex->sides with a bit above bit 1. */
+typedef struct {
+  uint32_t seed;        /* names the stream of exploration draws */
+  uint32_t threshold;   /* a decision explores iff draw0 < threshold; 0 = never */
+  uint32_t sides;       /* bit 0: FIRST's decisions may explore, bit 1: SECOND's */
+  int32_t  until_step;  /* only decisions at committed-step index k < until_step; <= 0 = no limit */
+} monsoon_explore;
+typedef struct {        /* caller-owned HOST buffers, row stride max_turns, each may be NULL */
+  uint8_t* greedy;      /* [n_matches][max_turns] the arg-max action of the decision; 255 for a bot step and behind the last step */
+  uint8_t* explored;    /* [n_matches][max_turns] 1 = this decision's draw said "explore"; 0 for a bot step and behind */
+  double*  taken_score; /* [n_matches][max_turns] score of the action that was committed; NaN for a bot step and behind */
+} monsoon_explore_log;
+int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                            int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
+                            int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log,
+                            const monsoon_explore* ex, const monsoon_explore_log* xlog);
+
 /* Logged games played again on the device into the (state, action) rows a learner trains on: one row per kept log entry,
  * holding the state BEFORE that entry's step.  No decision is recomputed: every entry costs one committed step.
  * matches, deck_pairs, the log (log_action[n_matches][log_stride], log_steps[n_matches] entries per row, what

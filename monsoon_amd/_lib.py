@@ -70,6 +70,14 @@ class RolloutLog(ctypes.Structure):     # monsoon_rollout_log: caller-owned host
     _fields_ = [(name, ctypes.c_void_p) for name in ("action", "score", "n_legal")]
 
 
+class Explore(ctypes.Structure):        # monsoon_explore: the exploration rule of monsoon_rollout_explore
+    _fields_ = [("seed", ctypes.c_uint32), ("threshold", ctypes.c_uint32), ("sides", ctypes.c_uint32), ("until_step", ctypes.c_int32)]
+
+
+class ExploreLog(ctypes.Structure):     # monsoon_explore_log: caller-owned host buffers (NULL = not wanted)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("greedy", "explored", "taken_score")]
+
+
 class ReplayRows(ctypes.Structure):     # monsoon_replay_rows: caller-owned device buffers (NULL = not wanted, except action)
     _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "legal", "obs_raises", "to_play", "action", "bot", "game", "step",
                                                       "state_hash")]
@@ -120,6 +128,10 @@ SIGNATURES = {
     "monsoon_rollout_logged": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(RolloutLog)]),
+    "monsoon_rollout_explore": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.POINTER(RolloutLog), ctypes.POINTER(Explore),
+                                               ctypes.POINTER(ExploreLog)]),
     "monsoon_replay_logged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.POINTER(ReplayRows), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),

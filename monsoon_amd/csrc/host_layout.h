@@ -108,6 +108,35 @@ inline RolloutLog rollout_log(size_t entries, bool score, bool n_legal) {
   return l;
 }
 
+// d_log of monsoon_rollout_explore: the same three arrays, then the three the exploring kernel adds, the 8-byte ones
+// first; an array the caller does not ask for takes no room.  explore_entry_bytes is what one entry takes (1 .. 21), the
+// figure the call's batch cap is cut by.
+struct ExploreLog { size_t score, taken_score, n_legal, action, greedy, explored, total; };   // f64 | f64 | i16 | u8 | u8 | u8, [entries] each
+constexpr size_t explore_entry_bytes(bool score, bool n_legal, bool greedy, bool explored, bool taken_score) {
+  return 1 + (score ? 8 : 0) + (n_legal ? 2 : 0) + (greedy ? 1 : 0) + (explored ? 1 : 0) + (taken_score ? 8 : 0);
+}
+inline ExploreLog explore_log(size_t entries, bool score, bool n_legal, bool greedy, bool explored, bool taken_score) {
+  ExploreLog l;
+  size_t at = 0;
+  const auto field = [&](bool on, size_t bytes) {
+    const size_t off = on ? at : NONE;
+    if (on) at += entries * bytes;
+    return off;
+  };
+  l.score = field(score, 8);
+  l.taken_score = field(taken_score, 8);
+  l.n_legal = field(n_legal, 2);
+  l.action = field(true, 1);
+  l.greedy = field(greedy, 1);
+  l.explored = field(explored, 1);
+  l.total = at;
+  return l;
+}
+// games per batch of a logged call: as many as `budget` bytes of device log hold, one at least, max_games at most
+constexpr size_t log_batch_cap(size_t max_games, size_t budget, size_t entry_bytes, size_t max_turns) {
+  return budget / (entry_bytes * max_turns) < 1 ? 1 : budget / (entry_bytes * max_turns) < max_games ? budget / (entry_bytes * max_turns) : max_games;
+}
+
 // d_replay, what one batch of monsoon_replay_logged_dev takes to the device and brings back: `games` games, `entries` =
 // games x log_stride; without a keep mask its array takes no room (NONE).  status .. fault come back in three copies.
 struct Replay { size_t base = 0, steps, replayed, action, keep, status, fault, total; };   // i64 | i32 | i32 [games], u8 | u8 [entries], u8 | u8 [games]

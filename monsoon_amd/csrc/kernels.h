@@ -3,7 +3,7 @@
 // them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, env_opp.hip and env_after.hip hold one
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, env_opp.hip and env_after.hip hold one
 // further instantiation each, replay_log.hip one of the rules core without the decision loop; monsoon_hip.hip holds the
 // API kernels and the host side.
 //
@@ -342,6 +342,55 @@ __device__ MSB_INL void log_step(const PlayLog& lg, const int g, const int lane,
   }
 }
 
+// What play_game<.., EXPLORE = true> needs beyond the PlayLog (k_play_explore, play_explore.hip; include/monsoon.h
+// monsoon_rollout_explore): the rule's four words, the match seed of every game of the batch, and the three further log
+// arrays (rows like the PlayLog's, each may be null).
+struct PlayExplore {
+  uint32_t seed, threshold, sides;
+  int until_step;
+  const uint32_t* match_seed;   // [n]
+  uint8_t* greedy;              // [n][stride] the decision's arg-max action
+  uint8_t* explored;            // [n][stride] 1 = the decision's draw said "explore"
+  double* taken_score;          // [n][stride] score of the committed action
+};
+// monsoon_amd/fitness.py hash32 over four words: integer arithmetic only, so the host reproduces every draw.
+__device__ MSB_INL uint32_t explore_hash32(const uint32_t a, const uint32_t b, const uint32_t c, const uint32_t d) {
+  const uint32_t v[4] = {a, b, c, d};
+  uint32_t h = 0x9E3779B9u;
+  _Pragma("unroll") for (int i = 0; i < 4; i++) {
+    h ^= v[i] + 0x7F4A7C15u + (h << 6) + (h >> 2);
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+  }
+  return h;
+}
+// The rank in the ascending legal list that the decision at committed step k commits instead of its arg-max, -1 where it
+// does not explore (all arguments wave-uniform, so is the result).
+__device__ MSB_INL int explore_rank(const PlayExplore& ex, const uint32_t match_seed, const int side, const int k, const int n_legal) {
+  if (!((ex.sides >> side) & 1u) || (ex.until_step > 0 && k >= ex.until_step) || n_legal <= 0) return -1;
+  if (explore_hash32(ex.seed, match_seed, (uint32_t)k, 0u) >= ex.threshold) return -1;
+  return (int)(((unsigned long long)explore_hash32(ex.seed, match_seed, (uint32_t)k, 1u) * (unsigned)n_legal) >> 32);
+}
+// What an exploring decision carries from its passes to its commit: the rank it commits (-1: its arg-max), that action
+// and its score.  It lives in the caller (k_play_explore) and reaches play_game as a pointer: declared in play_game, three
+// dead scalars changed the register allocation of every existing instantiation, and even an empty struct that of
+// k_env_opp.
+struct ExploreTake {
+  int r = -1, a = 0;
+  double s = 0.0;
+};
+__device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, const int g, const int lane, const int k, const int greedy,
+                                    const int explored, const double taken_score) {
+  if (lane == 0 && k < lg.stride) {
+    const size_t at = (size_t)g * lg.stride + k;
+    if (ex.greedy) ex.greedy[at] = (uint8_t)greedy;
+    if (ex.explored) ex.explored[at] = (uint8_t)explored;
+    if (ex.taken_score) ex.taken_score[at] = taken_score;
+  }
+}
+
 // Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
 // to the last; HBM sees one read and one write of it per call.
 // ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
@@ -352,12 +401,16 @@ __device__ MSB_INL void log_step(const PlayLog& lg, const int g, const int lane,
 // expert_action() and, unless that raised, step() on column 0 -- the current record's image with the stream window
 // attached -- and column 0 is then "the best successor" that the commit takes over.
 // LOG = true (k_play_log, play_log.hip; with VS = true): every committed step is written down in `lg`.
+// EXPLORE = true (k_play_explore, play_explore.hip; with LOG = true): a decision whose draw says so (explore_rank) commits
+// the r-th legal action (xt->r) instead of the arg-max.  Everything new is wave-uniform: the pass that holds rank r takes
+// lane r - base -- its record into v_best, its fault and feature flag, its features into wf[20..29], its score -- and on
+// such a decision the running arg-max moves run_a / run_s only, so v_best is written exactly once, in whichever pass.
 //
 // MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
 // whole wave (the used-up block becomes the new "next" block; the twist buffer is the column area, hence the second copy
 // of v_best); the committed successor's features (feat_ok: wf[20..29] holds them) become the "before" side of the next
-// decision.  It is the one macro local to play_game: it moves the register arrays, and the bot's round expands it a
+// decision.  It and MSB_TAKE_LANE (the exploring form's) are the macros local to play_game: it moves the register arrays, and the bot's round expands it a
 // second time.
 #define MSB_COMMIT_BEST()                                                                           \
   __syncthreads();                                                                                  \
@@ -381,9 +434,18 @@ __device__ MSB_INL void log_step(const PlayLog& lg, const int g, const int lane,
     __syncthreads();                                                                                \
     MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])                                                     \
   }
-template <int U, bool ENV = false, bool VS = false, bool LOG = false>
+// EXPLORE: candidate lane wl_ of this pass is what the commit takes -- its fault, its feature flag and features, its record.
+#define MSB_TAKE_LANE(wl_)                                                                          \
+  cfault = __builtin_amdgcn_readlane(my_fault, wl_);                                                \
+  feat_ok = __builtin_amdgcn_readlane(my_feat, wl_);                                                \
+  if (feat_ok && lane < 10) wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl_ * 10 + lane]; \
+  __syncthreads();                                                                                  \
+  MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl_])
+template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
-                                  const EnvPolicy& pol, const PlayLog& lg = PlayLog{}) {
+                                  const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
+                                  ExploreTake* const xt = nullptr) {
+  static_assert(!EXPLORE || (LOG && !ENV), "the exploring form is a logging rollout");
   typedef PlayLds<U> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -504,6 +566,9 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     int cfault = 0;
     int feat_ok = 0;                  // wf[20..29] holds the features of the best successor so far
     int la_fault = 0;                 // first build-limit fault a look-ahead of this decision hit
+    if constexpr (EXPLORE)
+      xt->r = explore_rank(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
+                        meta.steps, n_legal);
     for (int base = 0; base < n_legal; base += U) {
       double s = 0.0;   // except Exception -> 0.0 (evo/heuristic_agent.py:48-51)
       int my_fault = 0;
@@ -606,18 +671,37 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       if (ca != NONE_A && (run_a == NONE_A || cs > run_s)) {   // later passes hold larger action ids: strict >
         run_s = cs;
         run_a = ca;
-        unsigned long long bal = __ballot(a == ca);
-        const int wl = __ffsll((long long)bal) - 1;
-        cfault = __builtin_amdgcn_readlane(my_fault, wl);
-        feat_ok = __builtin_amdgcn_readlane(my_feat, wl);
-        if (feat_ok && lane < 10)   // the winner keeps its features: the next decision's "before" side
-          wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl * 10 + lane];
-        __syncthreads();
-        MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
+        if constexpr (!EXPLORE) {
+          unsigned long long bal = __ballot(a == ca);
+          const int wl = __ffsll((long long)bal) - 1;
+          cfault = __builtin_amdgcn_readlane(my_fault, wl);
+          feat_ok = __builtin_amdgcn_readlane(my_feat, wl);
+          if (feat_ok && lane < 10)   // the winner keeps its features: the next decision's "before" side
+            wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl * 10 + lane];
+          __syncthreads();
+          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
+        } else if (xt->r < 0) {   // (a decision that explores moves the two scalars only: its v_best is the explored lane's, below)
+          const int wl = __ffsll((long long)__ballot(a == ca)) - 1;
+          MSB_TAKE_LANE(wl)
+        }
+      }
+      if constexpr (EXPLORE) {
+        if (xt->r >= base && xt->r < base + U) {   // (uniform) the pass that holds the explored rank: lane r - base is what the commit takes
+          const int wl = __builtin_amdgcn_readfirstlane(xt->r - base);   // (< n_act: xt->r < n_legal)
+          xt->a = __builtin_amdgcn_readlane(a, wl);
+          const unsigned long long sb = (unsigned long long)__double_as_longlong(s);
+          xt->s = __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sb >> 32), wl) << 32) |
+                                                    (unsigned)__builtin_amdgcn_readlane((int)(unsigned)sb, wl)));
+          MSB_TAKE_LANE(wl)
+        }
       }
       PROF_MARK(6);   // argmax + new best into registers
     }
     MSB_COMMIT_BEST()
+    if constexpr (EXPLORE) {   // the log keeps the arg-max next to what was committed
+      log_explore(ex, lg, g, lane, meta.steps, run_a, xt->r >= 0, xt->r >= 0 ? xt->s : run_s);
+      if (xt->r >= 0) run_a = xt->a;   // (run_s stays the decision's best score)
+    }
     if constexpr (LOG) log_step(lg, g, lane, meta.steps, run_a, run_s, n_legal);
     meta.steps++;
     meta.last_action = (uint8_t)run_a;
@@ -656,6 +740,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   }
   MSB_EACH_GRANULE(L::GPL, lane, grec[gr_] = v_par[j_])
 #undef MSB_COMMIT_BEST
+#undef MSB_TAKE_LANE
   if (lane == 0) {
     b.meta[g] = meta;
     if constexpr (ENV) {
@@ -747,5 +832,12 @@ struct LogOps : KernelOps {
                PlayLog lg);   // never split: the whole batch, the first pair of counter sets
 };
 const LogOps* monsoon_play_log_ops();
+
+// k_play_explore<DEFAULT_U, DEFAULT_W> (play_explore.hip): k_play_log whose decisions may explore (PlayExplore).
+struct ExploreOps : KernelOps {
+  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+               PlayLog lg, PlayExplore ex);   // never split, like LogOps::play
+};
+const ExploreOps* monsoon_play_explore_ops();
 
 }  // namespace msbk

@@ -670,8 +670,9 @@ __global__ void k_ga_select(const double* fitness, int n, int* out_order) {
 // Host side
 // ================================================================================================
 // What launch_play launches: k_play of the handle's variant, k_play_vs (the kernel that knows the scripted bot, the
-// build's default variant) or k_play_log (k_play_vs that writes every committed step into a log).
-enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_KINDS = 3 };
+// build's default variant), k_play_log (k_play_vs that writes every committed step into a log) or k_play_explore (k_play_log
+// whose decisions may explore).
+enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_EXPLORE = 3, PLAY_KINDS = 4 };
 
 // Device memory: everything the handle allocates is recorded in `mem` when it is allocated and freed from that record by
 // monsoon_destroy; the pointers below and in `b`, `env` and `env_sched` only refer to it.  Events and the split streams
@@ -1610,19 +1611,20 @@ struct PlayCall {
   bool write_scores = false;     // every candidate's score goes to b.scores
   bool timed = false;            // an event pair of the handle round the call (kernel_ms)
   bool split = false;            // PLAY only (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below
-  const PlayLog* log = nullptr;  // PLAY_LOG only (monsoon_rollout_logged): where every committed step is written
+  const PlayLog* log = nullptr;  // PLAY_LOG and PLAY_EXPLORE (monsoon_rollout_logged / _explore): where every committed step is written
+  const PlayExplore* explore = nullptr;   // PLAY_EXPLORE only: the exploration rule, the batch's match seeds, the further log arrays
 };
 
-// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS and PLAY_LOG are never split.
+// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG and PLAY_EXPLORE are never split.
 static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
-  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG;
+  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG, explore = call.kind == PLAY_EXPLORE;
   bool timed = call.timed;
   if (h->bot_rows && call.kind == PLAY) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
   }
   const VariantOps* vp = vs ? monsoon_vs_expert_ops() : h->var;
-  const KernelOps* v = log ? static_cast<const KernelOps*>(monsoon_play_log_ops()) : vp;
+  const KernelOps* v = explore ? static_cast<const KernelOps*>(monsoon_play_explore_ops()) : log ? static_cast<const KernelOps*>(monsoon_play_log_ops()) : vp;
   const int lds = v->lds_bytes + g_lds_pad;
   int& grid_waves = h->grid_waves[call.kind];
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
@@ -1684,7 +1686,9 @@ static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
   }
   for (int s = 0; s < parts; s++) {
     const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
-    if (log)   // (parts == 1)
+    if (explore)   // (parts == 1)
+      monsoon_play_explore_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log, *call.explore);
+    else if (log)   // (parts == 1)
       monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log);
     else
       vp->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, call.max_turns, call.rounds, call.write_scores, pers, h->parity[s], g0, s);
@@ -1775,13 +1779,21 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
 }
 
 // A logged call's batch is cut so that its device log stays within LOG_BUDGET whatever max_turns is: 11 bytes per entry
-// (action + score + legal count), max_turns entries per game.
+// (action + score + legal count), max_turns entries per game; an exploring call's by the columns it asks for, 1 .. 21 bytes
+// (layout::explore_entry_bytes).
 constexpr size_t LOG_BUDGET = (size_t)256 << 20;
+
+// What an exploring call adds to a logged one: the caller's further host arrays and the kernel's argument (device
+// pointers into d_log; match_seed is set per batch).
+struct ExploreCall {
+  const monsoon_explore_log* host;
+  PlayExplore dev;
+};
 
 // Matches [base, base + n) of a rollout: load them, one launch plays the whole batch to the end, collect.  A batch without
 // a bot is k_play's, counted by k_collect, as ever.
 static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max_turns, const uint32_t* seeds, const uint8_t* decks, const int32_t* p1,
-                         const int32_t* p2, const monsoon_rollout_log* log, const PlayLog& dlog) {
+                         const int32_t* p2, const monsoon_rollout_log* log, const PlayLog& dlog, const ExploreCall* xc) {
   int rc = monsoon_reset(h, n, seeds, decks, nullptr);
   if (!rc) rc = assign_players(h, p1, p2, base, min_row);
   if (rc) return rc;
@@ -1792,12 +1804,21 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
     if (dlog.score) HIP_TRY(h, hipMemsetAsync(dlog.score, 0xFF, cnt * 8, h->stream));
     if (dlog.n_legal) HIP_TRY(h, hipMemsetAsync(dlog.n_legal, 0, cnt * 2, h->stream));
   }
+  PlayExplore dex;
+  if (xc) {   // likewise: greedy 255, explored 0, taken_score NaN -- also what a bot step reads, which writes none of them
+    dex = xc->dev;
+    dex.match_seed = h->d_seeds;   // (monsoon_reset left the batch's seeds there)
+    if (dex.greedy) HIP_TRY(h, hipMemsetAsync(dex.greedy, 0xFF, cnt, h->stream));
+    if (dex.explored) HIP_TRY(h, hipMemsetAsync(dex.explored, 0, cnt, h->stream));
+    if (dex.taken_score) HIP_TRY(h, hipMemsetAsync(dex.taken_score, 0xFF, cnt * 8, h->stream));
+  }
   PlayCall call;
-  call.kind = log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
+  call.kind = xc ? PLAY_EXPLORE : log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
   call.max_turns = max_turns;
   call.rounds = max_turns + 1;
   call.timed = true;
   call.log = log ? &dlog : nullptr;
+  call.explore = xc ? &dex : nullptr;
   rc = launch_play(h, n, call);
   if (rc) return rc;
   hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
@@ -1808,15 +1829,22 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
     if (dlog.score) HIP_TRY(h, hipMemcpyAsync(log->score + row, dlog.score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
     if (dlog.n_legal) HIP_TRY(h, hipMemcpyAsync(log->n_legal + row, dlog.n_legal, cnt * 2, hipMemcpyDeviceToHost, h->stream));
   }
+  if (xc) {
+    if (dex.greedy) HIP_TRY(h, hipMemcpyAsync(xc->host->greedy + row, dex.greedy, cnt, hipMemcpyDeviceToHost, h->stream));
+    if (dex.explored) HIP_TRY(h, hipMemcpyAsync(xc->host->explored + row, dex.explored, cnt, hipMemcpyDeviceToHost, h->stream));
+    if (dex.taken_score) HIP_TRY(h, hipMemcpyAsync(xc->host->taken_score + row, dex.taken_score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+  }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return drain_timing(h);
 }
 
 // monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and
-// monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log)
+// monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log);
+// monsoon_rollout_explore is the logged call with ex non-null (played by k_play_explore, xlog's arrays copied likewise)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                         int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
-                        int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr) {
+                        int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr, const monsoon_explore* ex = nullptr,
+                        const monsoon_explore_log* xlog = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
@@ -1844,7 +1872,20 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
   h->rollout_matches = 0;
   int cap = h->cfg.max_games;
   PlayLog dlog = {nullptr, nullptr, nullptr, max_turns};
-  if (log) {
+  ExploreCall xc = {xlog, PlayExplore{}};
+  if (ex) {
+    const bool gr = xlog && xlog->greedy, xp = xlog && xlog->explored, ts = xlog && xlog->taken_score;
+    cap = (int)layout::log_batch_cap((size_t)cap, LOG_BUDGET, layout::explore_entry_bytes(log->score, log->n_legal, gr, xp, ts), (size_t)max_turns);
+    const layout::ExploreLog l = layout::explore_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal, gr, xp, ts);
+    HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
+    if (log->score) dlog.score = (double*)(h->d_log + l.score);
+    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
+    dlog.action = h->d_log + l.action;
+    xc.dev.seed = ex->seed, xc.dev.threshold = ex->threshold, xc.dev.sides = ex->sides, xc.dev.until_step = ex->until_step;
+    if (gr) xc.dev.greedy = h->d_log + l.greedy;
+    if (xp) xc.dev.explored = h->d_log + l.explored;
+    if (ts) xc.dev.taken_score = (double*)(h->d_log + l.taken_score);
+  } else if (log) {
     cap = (int)std::min((size_t)cap, std::max((size_t)1, LOG_BUDGET / ((size_t)11 * max_turns)));
     const layout::RolloutLog l = layout::rollout_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal);
     HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
@@ -1868,7 +1909,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
       p1[i] = mm.p1;
       p2[i] = mm.p2;
     }
-    rc = rollout_batch(h, base, n, min_row, max_turns, seeds.data(), decks.data(), p1.data(), p2.data(), log, dlog);
+    rc = rollout_batch(h, base, n, min_row, max_turns, seeds.data(), decks.data(), p1.data(), p2.data(), log, dlog, ex ? &xc : nullptr);
     if (rc) return rc;
   }
   std::vector<int32_t> counts((size_t)n_individuals * 3);
@@ -1901,6 +1942,22 @@ int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_indivi
   if (!log || !log->action) return bad_arg(h, "monsoon_rollout_logged", "log and log->action are required");
   return rollout_impl(h, "monsoon_rollout_logged", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
                       max_turns, out_counts, out_results, out_steps, log);
+}
+
+// monsoon_rollout_logged's call with an exploration rule.  A rule that never explores still goes through k_play_explore
+// where one of xlog's arrays is asked for (the kernel fills them: greedy = action, taken_score = score on decisions);
+// without any it is the logged call itself.
+int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                            const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                            int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_explore* ex, const monsoon_explore_log* xlog) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_explore", "log and log->action are required");
+  if (ex && (ex->sides & ~3u)) return bad_arg(h, "monsoon_rollout_explore", "sides holds a bit above bit 1");
+  static const monsoon_explore never = {0u, 0u, 0u, 0};
+  const bool wants = xlog && (xlog->greedy || xlog->explored || xlog->taken_score);
+  const monsoon_explore* rule = (ex && ex->threshold) ? ex : wants ? &never : nullptr;
+  return rollout_impl(h, "monsoon_rollout_explore", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
+                      max_turns, out_counts, out_results, out_steps, log, rule, xlog);
 }
 
 // Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.

@@ -10,32 +10,67 @@ MATCH_DTYPE = np.dtype([("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", 
 LOG_BUDGET = 256 << 20   # bytes of device log a batch of monsoon_rollout_logged may take (include/monsoon.h)
 
 
+def explore_entry_bytes(scores=True, n_legal=True, greedy=True, explored=True, taken_score=True):
+    """Bytes of device log one entry of monsoon_rollout_explore takes, by the arrays asked for (action always): 1 .. 21."""
+    return 1 + 8 * bool(scores) + 2 * bool(n_legal) + bool(greedy) + bool(explored) + 8 * bool(taken_score)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+class Explore:
+    """The exploration rule of a logged rollout (monsoon_explore, include/monsoon.h): a heuristic decision of a side in
+    `sides` ("first", "second", "both") at committed-step index k (k < until_step where until_step > 0) commits a
+    uniformly drawn legal action instead of its arg-max with probability eps.  The draws are hash32(seed, match seed, k, .):
+    game_log.explore_draws recomputes them."""
+    SIDES = {"first": 1, "second": 2, "both": 3}
+
+    def __init__(self, eps, seed, sides="both", until_step=0):
+        if not 0.0 <= eps <= 1.0:   # (a NaN fails it too)
+            raise ValueError(f"Explore: eps must lie in [0, 1], got {eps!r}")
+        if sides not in self.SIDES:
+            raise ValueError(f"Explore: sides is one of {tuple(self.SIDES)}, got {sides!r}")
+        self.eps, self.seed, self.sides, self.until_step = float(eps), int(seed) & 0xFFFFFFFF, sides, int(until_step)
+        self.threshold = min(int(eps * 2**32), 0xFFFFFFFF)   # a decision explores iff draw0 < threshold
+        self.side_bits = self.SIDES[sides]
+
+    def may_explore(self, side, k):
+        """The two conditions of the rule that are not the draw: the side's bit and the step limit (numpy or scalars)."""
+        return (((self.side_bits >> side) & 1) != 0) & ((self.until_step <= 0) | (k < self.until_step))
+
+    def c_struct(self):
+        return _lib.Explore(self.seed, self.threshold, self.side_bits, self.until_step)
 
 
 class RolloutLog:
     """What a logged rollout played (monsoon_rollout_logged): entry k of row i is game i's k-th committed step.
     action uint8[n][max_turns] (255 behind the last step), score float64[n][max_turns] or None (the decision's best score;
     NaN for a step of the scripted bot and behind the last step), n_legal int16[n][max_turns] or None (legal actions of
-    the decision; 0 for a bot step and behind), steps int32[n] = the entries of each row."""
+    the decision; 0 for a bot step and behind), steps int32[n] = the entries of each row.
+    A rollout with an Explore rule (monsoon_rollout_explore) adds greedy uint8[n][max_turns] (the decision's arg-max action:
+    the teacher's label where `action` was explored; 255 for a bot step and behind), explored uint8[n][max_turns] (1 = the
+    decision's draw said "explore") and taken_score float64[n][max_turns] (score of the committed action; NaN for a bot
+    step and behind); None otherwise."""
 
-    def __init__(self, action, score, n_legal, steps):
+    def __init__(self, action, score, n_legal, steps, greedy=None, explored=None, taken_score=None):
         self.action, self.score, self.n_legal, self.steps = action, score, n_legal, steps
+        self.greedy, self.explored, self.taken_score = greedy, explored, taken_score
 
     @classmethod
-    def empty(cls, n, max_turns, scores=True, n_legal=True):
-        """n rows of padding."""
+    def empty(cls, n, max_turns, scores=True, n_legal=True, explore=False):
+        """n rows of padding; explore: with the three arrays of an exploring rollout."""
         return cls(np.full((n, max_turns), 255, dtype=np.uint8), np.full((n, max_turns), np.nan) if scores else None,
-                   np.zeros((n, max_turns), dtype=np.int16) if n_legal else None, np.zeros(n, dtype=np.int32))
+                   np.zeros((n, max_turns), dtype=np.int16) if n_legal else None, np.zeros(n, dtype=np.int32),
+                   np.full((n, max_turns), 255, dtype=np.uint8) if explore else None,
+                   np.zeros((n, max_turns), dtype=np.uint8) if explore else None, np.full((n, max_turns), np.nan) if explore else None)
 
     def put(self, rows, other):
         """Rows `rows` become the rows of `other` (a log of len(rows) games with the same arrays)."""
         self.action[rows], self.steps[rows] = other.action, other.steps
-        if self.score is not None:
-            self.score[rows] = other.score
-        if self.n_legal is not None:
-            self.n_legal[rows] = other.n_legal
+        for name in ("score", "n_legal", "greedy", "explored", "taken_score"):
+            if getattr(self, name) is not None:
+                getattr(self, name)[rows] = getattr(other, name)
 
 
 class BatchEngine:
@@ -314,11 +349,15 @@ class BatchEngine:
         won), else p2 (a win = SECOND won); results stay FIRST / SECOND, steps count both sides' committed steps."""
         return self._rollout("monsoon_rollout_vs_expert", weights, matches, deck_pairs, max_turns, want_results)
 
-    def rollout_logged(self, weights, matches, deck_pairs, max_turns, scores=True, n_legal=True):
+    def rollout_logged(self, weights, matches, deck_pairs, max_turns, scores=True, n_legal=True, explore=None):
         """monsoon_rollout_logged: rollout_vs_expert (the bot's rows included) that also writes down every committed step.
-        Returns (counts, results, steps, log), log a RolloutLog whose score / n_legal are None where not asked for."""
-        log = RolloutLog.empty(len(matches), max_turns, scores, n_legal)
-        return self._rollout("monsoon_rollout_logged", weights, matches, deck_pairs, max_turns, True, log) + (log,)
+        Returns (counts, results, steps, log), log a RolloutLog whose score / n_legal are None where not asked for.
+        explore = an Explore: monsoon_rollout_explore, the same call whose heuristic decisions may commit a drawn legal
+        action; the log also carries greedy, explored and taken_score, and the counts describe the games that were played --
+        they are not fitness."""
+        log = RolloutLog.empty(len(matches), max_turns, scores, n_legal, explore is not None)
+        entry = "monsoon_rollout_logged" if explore is None else "monsoon_rollout_explore"
+        return self._rollout(entry, weights, matches, deck_pairs, max_turns, True, log, explore) + (log,)
 
     @staticmethod
     def _rollout_args(weights, matches, deck_pairs):
@@ -332,9 +371,9 @@ class BatchEngine:
             m = arr
         return weights, m, deck_pairs
 
-    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results, log=None):
+    def _rollout(self, entry, weights, matches, deck_pairs, max_turns, want_results, log=None, explore=None):
         """One rollout entry of the library.  log: the RolloutLog that monsoon_rollout_logged fills, one row per match (its
-        steps are the call's steps)."""
+        steps are the call's steps); explore: the Explore of monsoon_rollout_explore, which fills the log's further arrays."""
         weights, m, deck_pairs = self._rollout_args(weights, matches, deck_pairs)
         n_ind = weights.shape[0]
         counts = np.zeros((n_ind, 3), dtype=np.int32)
@@ -344,7 +383,12 @@ class BatchEngine:
         if log is not None:
             c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
             extra = (ctypes.byref(c_log),)
-            batch = min(batch, max(1, LOG_BUDGET // (11 * max_turns)))   # a logged call's batches are cut by the log's budget too
+            entry_bytes = 11   # a logged call's batches are cut by the log's budget too ...
+            if explore is not None:   # ... an exploring call's by the arrays it asks for (include/monsoon.h)
+                c_ex, c_xlog = explore.c_struct(), _lib.ExploreLog(_ptr(log.greedy), _ptr(log.explored), _ptr(log.taken_score))
+                extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog))
+                entry_bytes = explore_entry_bytes(log.score is not None, log.n_legal is not None)
+            batch = min(batch, max(1, LOG_BUDGET // (entry_bytes * max_turns)))
         self._ck(getattr(self.lib, entry)(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
                                           max_turns, _ptr(counts), _ptr(results), _ptr(steps), *extra), entry)
         self.n = len(m) - ((len(m) - 1) // batch) * batch   # the handle now holds the last batch of the schedule

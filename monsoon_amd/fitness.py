@@ -313,14 +313,15 @@ class FitnessEvaluator:
         self.last_rollout = (results, steps, faults)
         return counts
 
-    def logged_games(self, weights, matches, deck_pairs=None):
+    def logged_games(self, weights, matches, deck_pairs=None, explore=None):
         """The games of a schedule with their logs, on this evaluator's engines (game_log.logged_rollout): what a
-        champion played, step by step.  deck_pairs None: config.deck on both sides.  Returns (counts, results, steps,
-        faults, log); the evaluator's statistics are left alone."""
+        champion played, step by step.  deck_pairs None: config.deck on both sides.  explore = an engine.Explore: the
+        games leave the champion's line where its draws say so, and the log keeps the champion's choice (log.greedy).
+        Returns (counts, results, steps, faults, log); the evaluator's statistics are left alone."""
         from .game_log import logged_rollout
         if deck_pairs is None:
             deck_pairs = mirrored_pair(self.config.deck)
-        return logged_rollout(self._engine, np.asarray(weights, dtype=np.float64), np.asarray(matches), deck_pairs, self.config.max_turns)
+        return logged_rollout(self._engine, np.asarray(weights, dtype=np.float64), np.asarray(matches), deck_pairs, self.config.max_turns, explore)
 
     def _deck_source(self):
         """Where this evaluator's decks come from: its DeckEvolutionConfig, else config.deck (a DECKS key or RANDOM_DECK)."""

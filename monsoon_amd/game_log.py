@@ -5,27 +5,44 @@ FitnessEvaluator.logged_games is its entry over an evaluator's own engines; repl
 step interface and yields the (state, action) pairs a learner wants; dataset / dataset_batches / step_sides play them
 again on the device (monsoon_replay_logged_dev), games with the scripted bot included, into torch tensors of rows; with a
 candidate column (CANDIDATE_COLUMNS) every row also carries the afterstates of its state (monsoon_replay_logged_after_dev),
-which candidates / candidate_mask hand to vec_env.select_actions and to a learner over afterstate features.
+which candidates / candidate_mask hand to vec_env.select_actions and to a learner over afterstate features.  A rollout
+with an engine.Explore rule logs games that leave the champion's line; its log keeps the arg-max of every decision
+(greedy) and which decisions explored, explore_draws recomputes the draws, and dataset hands both out as row columns
+(LOG_COLUMNS).
 """
 import numpy as np
 
 from . import _lib
 from .engine import RolloutLog
-from .fitness import _ladder, bot_plays
+from .fitness import _ladder, bot_plays, hash32_array
 
 
-def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns):
+def explore_draws(explore, match_seeds, k, n_legal):
+    """The draws of monsoon_rollout_explore for decisions at committed-step index k of matches with the seeds match_seeds
+    over n_legal legal actions (broadcastable integer arrays): (explores bool, rank int64) -- explores = draw0 <
+    explore.threshold, rank = the position in the ascending legal list that an exploring decision commits.  Only the draw
+    is tested: whether the side may explore and the step limit (Explore.may_explore) are the caller's to apply."""
+    seeds, k, n_legal = np.broadcast_arrays(np.asarray(match_seeds, dtype=np.uint64), np.asarray(k, dtype=np.uint64), np.asarray(n_legal, dtype=np.uint64))
+    draw0, draw1 = hash32_array(explore.seed, seeds, k, 0), hash32_array(explore.seed, seeds, k, 1)
+    return draw0 < np.uint32(explore.threshold), ((draw1.astype(np.uint64) * n_legal) >> np.uint64(32)).astype(np.int64)
+
+
+def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, explore=None):
     """A schedule played on the smallest record each game needs, with its log.  engine_for_tier(tier) is the engine of a
     record (0 standard, 1 extended, 2 large): anything with BatchEngine's rollout_logged and rollout_faults.  The rule is
     fitness.tiered_rollout's, the same function (fitness._ladder): a deck pair holding ua20 / b005 starts on the extended
     record, a game that ends on a limit of its record (fitness.record_limited) is played again on the next larger one, and
     its rows -- the log's among them -- are replaced.  An engine is handed only the deck pairs its sub-schedule names.
+    explore = an engine.Explore: every tier plays with that rule (the draws are keyed by the match's seed and the step, so a
+    game played again on a larger record explores as it did on the smaller one) and the log carries greedy, explored and
+    taken_score; the counts then describe explored games, not fitness.
     Returns (counts[n_rows][3], results, steps, faults, log)."""
-    log = RolloutLog.empty(len(matches), max_turns)
+    log = RolloutLog.empty(len(matches), max_turns, explore=explore is not None)
+    how = {} if explore is None else {"explore": explore}
 
     def play(t, sub, sub_pairs):
         eng = engine_for_tier(t)
-        c, r, s, lg = eng.rollout_logged(weights, sub, sub_pairs, max_turns)
+        c, r, s, lg = eng.rollout_logged(weights, sub, sub_pairs, max_turns, **how)
         return c, r, s, eng.rollout_faults(len(sub)), lg
     return _ladder(play, len(weights), matches, deck_pairs, put=log.put)[:4] + (log,)
 
@@ -68,6 +85,9 @@ def replay(engine, matches, deck_pairs, log):
 COLUMNS = {"obs": ("int32", (27, 5, 4)), "legal": ("uint8", (156,)), "obs_raises": ("uint8", ()), "to_play": ("uint8", ()),
            "action": ("uint8", ()), "bot": ("uint8", ()), "game": ("int32", ()), "step": ("int32", ()), "state_hash": ("int64", ())}
 ROW_BYTES = {"obs": 2160, "legal": 156, "obs_raises": 1, "to_play": 1, "action": 1, "bot": 1, "game": 4, "step": 4, "state_hash": 8}
+# ... those gathered on the host from the arrays of an exploring rollout's log at the kept entries (no replay involved):
+# greedy is the teacher's label of a row whose action was explored, explored marks such rows
+LOG_COLUMNS = {"greedy": ("uint8", ()), "explored": ("uint8", ())}
 # ... and of monsoon_replay_after, "K" = max_after: the candidates the row's choice was made among, entry k the k-th legal
 # action in ascending order.  Naming one of them turns the look-ahead on; _CANDIDATE_BASE comes along, as action does.
 CANDIDATE_COLUMNS = {"n_legal": ("int32", ()), "chosen": ("int16", ()), "after_action": ("uint8", ("K",)), "after_status": ("uint8", ("K",)),
@@ -122,9 +142,9 @@ def outcome(results, game, to_play):
 
 def _want(columns):
     columns = tuple(columns)
-    bad = [c for c in columns if c not in COLUMNS and c not in CANDIDATE_COLUMNS]
+    bad = [c for c in columns if c not in COLUMNS and c not in CANDIDATE_COLUMNS and c not in LOG_COLUMNS]
     if bad:
-        raise ValueError(f"unknown column(s) {bad}: choose from {tuple(COLUMNS) + tuple(CANDIDATE_COLUMNS)}")
+        raise ValueError(f"unknown column(s) {bad}: choose from {tuple(COLUMNS) + tuple(CANDIDATE_COLUMNS) + tuple(LOG_COLUMNS)}")
     if "action" not in columns:
         columns += ("action",)
     if any(c in CANDIDATE_COLUMNS for c in columns):
@@ -146,7 +166,7 @@ def _tensors(engine, names, cap, max_after=0):
     dev = torch.device("cuda", engine.device)
     out = {}
     for c in names:
-        dt, shape = COLUMNS[c] if c in COLUMNS else CANDIDATE_COLUMNS[c]
+        dt, shape = COLUMNS[c] if c in COLUMNS else LOG_COLUMNS[c] if c in LOG_COLUMNS else CANDIDATE_COLUMNS[c]
         shape = tuple(max_after if d == "K" else d for d in shape)
         out[c] = torch.empty((max(int(cap), 1),) + shape, dtype=getattr(torch, dt), device=dev)
     return out
@@ -161,6 +181,30 @@ def _replay_into(engine, tensors, matches, deck_pairs, action, steps, keep, max_
     if max_after:
         after = _lib.ReplayAfter(**{_AFTER_FIELD[c]: t.data_ptr() for c, t in tensors.items() if c in CANDIDATE_COLUMNS})
     return engine.replay_logged(matches, deck_pairs, action, steps, rows, tensors["action"].shape[0], keep, after, max_after)
+
+
+def _log_columns(log, names):
+    """The LOG_COLUMNS among `names`; ValueError where the log does not have their arrays."""
+    want = [c for c in names if c in LOG_COLUMNS]
+    missing = [c for c in want if getattr(log, c, None) is None]
+    if missing:
+        raise ValueError(f"column(s) {missing} need the log of a rollout with an Explore rule (rollout_logged(..., explore=))")
+    return want
+
+
+def _gather_log(tensors, log, want, steps, keep, a=0, b=None):
+    """Fill the LOG_COLUMNS `want` of `tensors` from the arrays of games [a, b) of `log` at the kept entries, in row order
+    (match order, then entry order)."""
+    import torch
+    if not want:
+        return
+    steps = np.asarray(steps, dtype=np.int64)
+    sel = np.arange(log.action.shape[1])[None, :] < steps[:, None]
+    if keep is not None:
+        sel &= np.asarray(keep)[:, :sel.shape[1]] != 0
+    for c in want:
+        vals = np.ascontiguousarray(getattr(log, c)[a:b][sel])   # (boolean indexing is row-major: the documented row order)
+        tensors[c][:len(vals)] = torch.as_tensor(vals, device=tensors[c].device)
 
 
 def _columns_for(columns, results):
@@ -209,6 +253,11 @@ def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS),
     stopped early read action 255 from the stop on; their other columns are unspecified.  results int8[n] (the rollout's)
     adds outcome int8[S]: +1 / 0 / -1 from the side to play.
 
+    Over the log of a rollout with an Explore rule the names of LOG_COLUMNS are accepted too: greedy uint8[S], the arg-max
+    action of the row's decision (255 on a bot step) -- the teacher's label where `action` was explored -- and explored
+    uint8[S]; both are gathered on the host from the log's arrays at the kept entries, in row order.  The replay itself
+    takes an explored action as it takes any legal one.
+
     A name of CANDIDATE_COLUMNS in `columns` turns the look-ahead on (monsoon_replay_logged_after_dev): the row also carries
     the successor of every legal action of its state, K = max_after (1..156) entries, entry k the k-th legal action in
     ascending order, in the meaning of VecEnv.afterstates -- n_legal int32[S] (the full count, also beyond K), chosen
@@ -231,8 +280,10 @@ def dataset(engine, matches, deck_pairs, log, keep=None, columns=tuple(COLUMNS),
     _, total = row_bases(log.steps, keep)
     names = _columns_for(columns, results)
     k_after = _max_after(names, max_after)
+    from_log = _log_columns(log, names)
     tensors = _tensors(engine, names, total, k_after)
     n_rows, status, replayed, fault = _replay_into(engine, tensors, matches, deck_pairs, log.action, log.steps, keep, k_after)
+    _gather_log(tensors, log, from_log, log.steps, keep)
     return _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
 
 
@@ -251,10 +302,12 @@ def dataset_batches(engine, matches, deck_pairs, log, max_rows, keep=None, colum
     cap = max((int(counts[a:b].sum()) for a, b in cuts), default=0)
     names = _columns_for(columns, results)
     k_after = _max_after(names, max_after)
+    from_log = _log_columns(log, names)
     tensors = _tensors(engine, names, cap, k_after)
     for a, b in cuts:
-        n_rows, status, replayed, fault = _replay_into(engine, tensors, matches[a:b], deck_pairs, log.action[a:b], log.steps[a:b],
-                                                        None if keep is None else np.asarray(keep)[a:b], k_after)
+        keep_ab = None if keep is None else np.asarray(keep)[a:b]
+        n_rows, status, replayed, fault = _replay_into(engine, tensors, matches[a:b], deck_pairs, log.action[a:b], log.steps[a:b], keep_ab, k_after)
+        _gather_log(tensors, log, from_log, log.steps[a:b], keep_ab, a, b)
         if "game" in tensors:
             tensors["game"][:n_rows] += a
         item = _hand_out(tensors, columns, n_rows, results, status, replayed, fault)
