@@ -560,6 +560,46 @@ int monsoon_env_step_dev(monsoon_t* h, const uint8_t* actions_dev);
  * [0, n_individuals) or an n different from the loaded env's returns MONSOON_ERR_ARG.  Synchronises. */
 int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_individuals, const int32_t* rows, int32_t n);
 
+/* Epsilon-greedy heuristic opponents, epsilon per slot: the env's form of monsoon_rollout_explore's rule.
+ *
+ * Take a decision of slot i's heuristic opponent over n_legal >= 1 actions.  Let k be the number of steps the episode has
+ * committed so far, the agent's and the opponent's together (the count max_steps is compared with), and
+ * s = seed0[i] + episode[i] * seed_stride (mod 2^32) the seed of the slot's current episode, as the slot holds seed0, its
+ * episode count and the stride at that moment.  With hash32 of monsoon_amd/fitness.py,
+ *     draw0 = hash32(ex.seed, s, k, 0)      draw1 = hash32(ex.seed, s, k, 1)      r = ((uint64_t)draw1 * n_legal) >> 32
+ * the decision EXPLORES when (until_step <= 0 || k < until_step) and draw0 < thresholds[i]: it then commits the r-th action
+ * of the ascending legal list instead of the arg-max.  The arg-max still runs over all candidates; every legal action is
+ * stepped exactly once (monsoon_debug_counters word 16 counts as before); the commit re-executes nothing: the committed
+ * successor is the taken candidate's look-ahead record, and a fault or a raising observation of the taken candidate ends the
+ * episode by the env's rules exactly as for the arg-max winner.  No draw touches the game's numpy stream.  The 64-decision
+ * guard (fault 28) is unchanged.  Consequences: a rewind (monsoon_env_load_dev into the slot the entry came from) explores
+ * exactly as the first run did; a fork into slots with other seed0 explores differently per slot (Monte-Carlo playouts from
+ * a snapshot); two slots with equal seed0 share their draws.
+ *
+ * Which kernel plays the opponent is decided at monsoon_env_reset, so that a captured step never changes kernels: if the
+ * handle holds a rule when an opponent-2 env is reset, every step of that env launches the exploring kernel where it
+ * would launch the plain one (still seven launches on one stream); otherwise the env plays exactly as without this call.
+ * The rule's two words and the n thresholds live in device buffers that are allocated by the first call (for max_games
+ * slots) and never moved.  A call validates, copies them behind everything already enqueued on the handle's stream and
+ * synchronises; it takes effect from the next decision, also under a captured step: the graph holds the addresses, not the
+ * contents.  All thresholds 0 plays the non-exploring env bit for bit: that is how an env is armed for later use.
+ *
+ * thresholds: HOST uint32[n]; 0 = never, 0xFFFFFFFF = all but one draw in 2^32.  ex == NULL clears the rule (thresholds
+ * and n are not read); MONSOON_ERR_STATE while an env that was reset with a rule is loaded.  MONSOON_ERR_STATE also when an
+ * opponent-2 env that was reset WITHOUT a rule is loaded.  MONSOON_ERR_ARG: NULL thresholds with a non-NULL ex, n <= 0,
+ * n > max_games, an n that differs from the loaded env's; monsoon_env_reset with opponent 2 and a rule whose n differs from
+ * the reset's n returns MONSOON_ERR_ARG too.  Opponents 0 and 1 ignore the rule. */
+typedef struct {
+  uint32_t seed;        /* names the stream of exploration draws */
+  int32_t  until_step;  /* only decisions at episode step index k < until_step explore; <= 0 = no limit */
+} monsoon_env_explore;
+int monsoon_env_set_opponent_explore(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds, int32_t n);
+/* DEVICE uint32[n] -> out_dev: the decisions of slot i's opponent whose draw said "explore", since monsoon_env_reset (which
+ * zeroes them; like monsoon_debug_counters words 6 / 7 / 16 they are neither saved nor restored by snapshots).  One
+ * device-to-device copy on the handle's stream: asynchronous, no allocation or synchronisation, capturable.
+ * MONSOON_ERR_STATE without a loaded env or when the env has no rule, MONSOON_ERR_ARG for a NULL out_dev. */
+int monsoon_env_opponent_explored_dev(monsoon_t* h, void* out_dev);
+
 /* Schedule mode: the third source of episode decks, beside the reset decks and the pool.  The handle keeps ONE deck schedule
  * in a device buffer that is allocated by the first call and never moved while an env is loaded.  monsoon_env_reset with
  * decks == NULL and pool_n == 0 plays schedule mode if the handle holds a schedule (MONSOON_ERR_ARG otherwise); with decks

@@ -74,6 +74,10 @@ class Explore(ctypes.Structure):        # monsoon_explore: the exploration rule 
     _fields_ = [("seed", ctypes.c_uint32), ("threshold", ctypes.c_uint32), ("sides", ctypes.c_uint32), ("until_step", ctypes.c_int32)]
 
 
+class EnvExplore(ctypes.Structure):     # monsoon_env_explore: the rule of monsoon_env_set_opponent_explore (thresholds travel beside it)
+    _fields_ = [("seed", ctypes.c_uint32), ("until_step", ctypes.c_int32)]
+
+
 class ExploreLog(ctypes.Structure):     # monsoon_explore_log: caller-owned host buffers (NULL = not wanted)
     _fields_ = [(name, ctypes.c_void_p) for name in ("greedy", "explored", "taken_score")]
 
@@ -163,6 +167,8 @@ SIGNATURES = {
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_step_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
+    "monsoon_env_set_opponent_explore": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvExplore), ctypes.c_void_p, ctypes.c_int32]),
+    "monsoon_env_opponent_explored_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_set_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule)]),
     "monsoon_env_decks_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_reseed_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),

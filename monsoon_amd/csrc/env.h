@@ -44,4 +44,11 @@ struct EnvOppOps : KernelOps {
 };
 const EnvOppOps* monsoon_env_opp_ops();
 
+// k_env_opp_explore<U, W> (env_opp_explore.hip): the same turn, epsilon-greedy by the rule the handle holds
+// (kernels.h EnvExplore).  The host picks one of the two tables at monsoon_env_reset.
+struct EnvOppExploreOps : KernelOps {
+  void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list, EnvExplore ee);
+};
+const EnvOppExploreOps* monsoon_env_opp_explore_ops();
+
 }  // namespace msbk

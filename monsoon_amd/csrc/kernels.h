@@ -3,7 +3,7 @@
 // them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, env_opp.hip and env_after.hip hold one
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, env_opp.hip, env_opp_explore.hip and env_after.hip hold one
 // further instantiation each, replay_log.hip one of the rules core without the decision loop; monsoon_hip.hip holds the
 // API kernels and the host side.
 //
@@ -381,6 +381,29 @@ struct ExploreTake {
   int r = -1, a = 0;
   double s = 0.0;
 };
+// What play_game<U, true, false, false, true> needs beyond the EnvPolicy (k_env_opp_explore, env_opp_explore.hip;
+// include/monsoon.h monsoon_env_set_opponent_explore): an argument of that kernel alone, as EnvSched is of its kernel --
+// EnvDev, EnvPolicy, PlayExplore and ExploreTake keep their layout.  The rule and the thresholds are device words that the
+// host rewrites between steps, so every decision reads them anew (a captured step holds the addresses, not the contents).
+struct EnvExplore {
+  const uint32_t* rule;         // [2]: the exploration seed, until_step (int32)
+  const uint32_t* thresholds;   // [n]: slot g's opponent explores iff draw0 < thresholds[g]
+  uint32_t* explored;           // [n]: decisions whose draw said "explore", since monsoon_env_reset
+  const uint32_t* seed0;        // [n] (EnvDev's): the episode seed is seed0[g] + episode[g] * stride ...
+  const int32_t* episode;       // [n] ... as env.inc env_seed computes it
+  uint32_t stride;
+};
+// explore_rank for slot g's opponent at committed step k of its episode.  g is wave-uniform and so is every word loaded here;
+// readfirstlane says so to the compiler.
+__device__ MSB_INL int env_explore_rank(const EnvExplore& ee, const int g, const int k, const int n_legal) {
+  const int until_step = __builtin_amdgcn_readfirstlane((int)ee.rule[1]);
+  if ((until_step > 0 && k >= until_step) || n_legal <= 0) return -1;
+  const uint32_t seed = (uint32_t)__builtin_amdgcn_readfirstlane((int)ee.rule[0]);
+  const uint32_t threshold = (uint32_t)__builtin_amdgcn_readfirstlane((int)ee.thresholds[g]);
+  const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ee.seed0[g] + (uint32_t)ee.episode[g] * ee.stride));
+  if (explore_hash32(seed, s, (uint32_t)k, 0u) >= threshold) return -1;
+  return (int)(((unsigned long long)explore_hash32(seed, s, (uint32_t)k, 1u) * (unsigned)n_legal) >> 32);
+}
 __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, const int g, const int lane, const int k, const int greedy,
                                     const int explored, const double taken_score) {
   if (lane == 0 && k < lg.stride) {
@@ -401,7 +424,8 @@ __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, co
 // expert_action() and, unless that raised, step() on column 0 -- the current record's image with the stream window
 // attached -- and column 0 is then "the best successor" that the commit takes over.
 // LOG = true (k_play_log, play_log.hip; with VS = true): every committed step is written down in `lg`.
-// EXPLORE = true (k_play_explore, play_explore.hip; with LOG = true): a decision whose draw says so (explore_rank) commits
+// EXPLORE = true (k_play_explore, play_explore.hip, with LOG = true; k_env_opp_explore, env_opp_explore.hip, with ENV = true
+// and the draw of env_explore_rank from `ee`): a decision whose draw says so (explore_rank) commits
 // the r-th legal action (xt->r) instead of the arg-max.  Everything new is wave-uniform: the pass that holds rank r takes
 // lane r - base -- its record into v_best, its fault and feature flag, its features into wf[20..29], its score -- and on
 // such a decision the running arg-max moves run_a / run_s only, so v_best is written exactly once, in whichever pass.
@@ -444,8 +468,8 @@ __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, co
 template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
-                                  ExploreTake* const xt = nullptr) {
-  static_assert(!EXPLORE || (LOG && !ENV), "the exploring form is a logging rollout");
+                                  ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr) {
+  static_assert(!EXPLORE || (LOG && !ENV) || (ENV && !VS && !LOG), "the exploring form is a logging rollout or the env's opponent");
   typedef PlayLds<U> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -566,7 +590,9 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     int cfault = 0;
     int feat_ok = 0;                  // wf[20..29] holds the features of the best successor so far
     int la_fault = 0;                 // first build-limit fault a look-ahead of this decision hit
-    if constexpr (EXPLORE)
+    if constexpr (EXPLORE && ENV)
+      xt->r = env_explore_rank(*ee, g, meta.steps, n_legal);
+    else if constexpr (EXPLORE)
       xt->r = explore_rank(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
                         meta.steps, n_legal);
     for (int base = 0; base < n_legal; base += U) {
@@ -689,17 +715,20 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         if (xt->r >= base && xt->r < base + U) {   // (uniform) the pass that holds the explored rank: lane r - base is what the commit takes
           const int wl = __builtin_amdgcn_readfirstlane(xt->r - base);   // (< n_act: xt->r < n_legal)
           xt->a = __builtin_amdgcn_readlane(a, wl);
-          const unsigned long long sb = (unsigned long long)__double_as_longlong(s);
-          xt->s = __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sb >> 32), wl) << 32) |
-                                                    (unsigned)__builtin_amdgcn_readlane((int)(unsigned)sb, wl)));
+          if constexpr (LOG) {   // (the committed action's score is the log's)
+            const unsigned long long sb = (unsigned long long)__double_as_longlong(s);
+            xt->s = __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(sb >> 32), wl) << 32) |
+                                                      (unsigned)__builtin_amdgcn_readlane((int)(unsigned)sb, wl)));
+          }
           MSB_TAKE_LANE(wl)
         }
       }
       PROF_MARK(6);   // argmax + new best into registers
     }
     MSB_COMMIT_BEST()
-    if constexpr (EXPLORE) {   // the log keeps the arg-max next to what was committed
-      log_explore(ex, lg, g, lane, meta.steps, run_a, xt->r >= 0, xt->r >= 0 ? xt->s : run_s);
+    if constexpr (EXPLORE) {   // the log keeps the arg-max next to what was committed; the env counts the slot's explored decisions
+      if constexpr (LOG) log_explore(ex, lg, g, lane, meta.steps, run_a, xt->r >= 0, xt->r >= 0 ? xt->s : run_s);
+      else if (xt->r >= 0 && lane == 0) atomicAdd(&ee->explored[g], 1u);   // (one wavefront plays a slot: no contention; nothing waits for it)
       if (xt->r >= 0) run_a = xt->a;   // (run_s stays the decision's best score)
     }
     if constexpr (LOG) log_step(lg, g, lane, meta.steps, run_a, run_s, n_legal);
@@ -768,7 +797,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
-// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_replay_log, k_env_opp): `mine` / `other` are this launch's counter
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_replay_log, k_env_opp, k_env_opp_explore): `mine` / `other` are this launch's counter
 // set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
 // nothing for it leaves before enter(), which runs once ahead of the first game.
 template <class Enter, class Play>

@@ -750,6 +750,13 @@ struct monsoon {
   int opp_w_cap = 0;          // rows allocated
   int opp_n = 0;              // slots the last monsoon_env_set_opponents gave rows for (0 = never called)
   int opp_grid = 0;           // k_env_opp's grid: resident wavefronts, at most the slots (queried at reset)
+  // the opponent's exploration rule (monsoon_env_set_opponent_explore): two buffers sized by max_games, allocated by the
+  // first call and never moved (a captured step points to them; nothing outgrows them, so `mem` frees them at destroy)
+  uint32_t* d_opp_ex = nullptr;         // the rule's two words, then from word OPP_EX_RULE_WORDS on thresholds[max_games]
+  uint32_t* d_opp_explored = nullptr;   // [max_games]: explored decisions per slot of the loaded env
+  int opp_ex_n = 0;                     // slots the held rule has thresholds for, 0 = the handle holds no rule
+  bool env_explore = false;             // the loaded opponent-2 env was reset with a rule: its steps launch k_env_opp_explore
+  EnvExplore env_ex = {};               // ... with this argument
   int after_grid = 0;         // k_env_after's grid (monsoon_env_afterstates_dev), likewise
   int after_waves = 0;        // resident wavefronts of k_env_after (queried once per handle)
   int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
@@ -2268,12 +2275,17 @@ void* monsoon_stream(monsoon_t* h) {
 // The heuristic opponent's turn for the slots of list `list`, then their views: two launches, no synchronisation.
 // k_env_opp reads the env's weight table through its own DevBuffers copy (monsoon_upload_weights' table is not touched).
 static int launch_env_opp(monsoon_t* h, int n, int list) {
-  const EnvOppOps* o = monsoon_env_opp_ops();
   DevBuffers ob = h->b;
   ob.weights = h->d_opp_w;
   ob.scores = nullptr;
   ob.best = nullptr;
-  o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list);
+  if (h->env_explore) {   // (settled at monsoon_env_reset: a captured step never changes kernels)
+    const EnvOppExploreOps* o = monsoon_env_opp_explore_ops();
+    o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list, h->env_ex);
+  } else {
+    const EnvOppOps* o = monsoon_env_opp_ops();
+    o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list);
+  }
   LAUNCH_LANES(h, k_env_after_opp, n, h->b, h->env, list);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;
@@ -2303,6 +2315,57 @@ int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_ind
   else HIP_TRY(h, hipMemsetAsync(h->d_opp + l.rows, 0, (size_t)n * 4, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->opp_n = n;
+  return MONSOON_OK;
+}
+
+// The rule's words and thresholds reach the device behind everything enqueued on the handle's stream; the kernel reads
+// them at every decision, so they hold from the next decision on, also under a captured step.
+constexpr int OPP_EX_RULE_WORDS = 16;   // thresholds start 64 bytes behind the rule's two words
+int monsoon_env_set_opponent_explore(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds, int32_t n) {
+  if (!h) return MONSOON_ERR_ARG;
+  const bool opp2 = h->env_on && h->env.opponent == 2;
+  if (!ex) {
+    if (opp2 && h->env_explore) {
+      h->err = "monsoon_env_set_opponent_explore: an env that was reset with a rule is loaded: its rule can be replaced (all thresholds 0 = silent), not cleared";
+      return MONSOON_ERR_STATE;
+    }
+    h->opp_ex_n = 0;
+    return MONSOON_OK;
+  }
+  if (!thresholds || n <= 0 || n > h->cfg.max_games) return bad_arg(h, "monsoon_env_set_opponent_explore", "bad argument (thresholds, 1 <= n <= max_games)");
+  if (opp2 && !h->env_explore) {
+    h->err = "monsoon_env_set_opponent_explore: the loaded opponent-2 env was reset without a rule (set the rule, all thresholds 0 if need be, before monsoon_env_reset)";
+    return MONSOON_ERR_STATE;
+  }
+  if (opp2 && n != h->env_n) return bad_arg(h, "monsoon_env_set_opponent_explore", "n differs from the loaded env's");
+  HIP_TRY(h, bind_device(h));
+  if (!h->d_opp_ex) {
+    HIP_TRY(h, h->mem.alloc(&h->d_opp_ex, ((size_t)OPP_EX_RULE_WORDS + (size_t)h->cfg.max_games) * 4));
+    HIP_TRY(h, hipMemsetAsync(h->d_opp_ex, 0, ((size_t)OPP_EX_RULE_WORDS + (size_t)h->cfg.max_games) * 4, h->stream));
+  }
+  if (!h->d_opp_explored) {
+    HIP_TRY(h, h->mem.alloc(&h->d_opp_explored, (size_t)h->cfg.max_games * 4));
+    HIP_TRY(h, hipMemsetAsync(h->d_opp_explored, 0, (size_t)h->cfg.max_games * 4, h->stream));
+  }
+  const uint32_t rule[2] = {ex->seed, (uint32_t)ex->until_step};
+  HIP_TRY(h, hipMemcpyAsync(h->d_opp_ex, rule, sizeof(rule), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_opp_ex + OPP_EX_RULE_WORDS, thresholds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  h->opp_ex_n = n;
+  return MONSOON_OK;
+}
+
+// One device-to-device copy on the handle's stream: no allocation or synchronisation (graph-capturable).
+int monsoon_env_opponent_explored_dev(monsoon_t* h, void* out_dev) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (int rc = require_env(h, "monsoon_env_opponent_explored_dev")) return rc;
+  if (!(h->env.opponent == 2 && h->env_explore)) {
+    h->err = "monsoon_env_opponent_explored_dev: the loaded env has no exploration rule (monsoon_env_set_opponent_explore before monsoon_env_reset)";
+    return MONSOON_ERR_STATE;
+  }
+  if (!out_dev) return bad_arg(h, "monsoon_env_opponent_explored_dev", "out_dev is NULL");
+  HIP_TRY(h, bind_device(h));
+  HIP_TRY(h, hipMemcpyAsync(out_dev, h->d_opp_explored, (size_t)h->env_n * 4, hipMemcpyDeviceToDevice, h->stream));
   return MONSOON_OK;
 }
 
@@ -2389,6 +2452,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
   else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
   else if (cfg->opponent == 2 && h->opp_n && h->opp_n != n) bad = "n differs from the n of monsoon_env_set_opponents";
+  else if (cfg->opponent == 2 && h->opp_ex_n && h->opp_ex_n != n) bad = "n differs from the n of monsoon_env_set_opponent_explore";
   if (bad) return bad_arg(h, "monsoon_env_reset", bad);
   if (cfg->opponent == 2 && !h->opp_n) {
     h->err = "monsoon_env_reset: opponent 2 needs monsoon_env_set_opponents first";
@@ -2432,6 +2496,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   v.opp_count = nullptr;
   v.opp_pop = nullptr;
   v.opp_lookahead = nullptr;
+  h->env_explore = false;
   h->env_sched = EnvSched{};
   if (by_schedule) {
     h->env_sched = EnvSched{(const monsoon_deck_schedule*)h->d_sched, h->d_mt_init, (uint32_t*)(h->d_sched + sizeof(monsoon_deck_schedule))};
@@ -2444,7 +2509,13 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     v.opp_lookahead = (uint32_t*)(h->d_opp + ol.lookahead);
     v.opp_count = (int32_t*)(h->d_opp + ol.count);
     v.opp_pop = (int*)(h->d_opp + ol.pop);
-    const EnvOppOps* o = monsoon_env_opp_ops();
+    // with a rule in the handle every step of this env launches k_env_opp_explore where it would launch k_env_opp
+    h->env_explore = h->opp_ex_n != 0;
+    const KernelOps* o = h->env_explore ? (const KernelOps*)monsoon_env_opp_explore_ops() : (const KernelOps*)monsoon_env_opp_ops();
+    if (h->env_explore) {
+      h->env_ex = EnvExplore{h->d_opp_ex, h->d_opp_ex + OPP_EX_RULE_WORDS, h->d_opp_explored, v.seed0, v.episode, v.stride};
+      HIP_TRY(h, hipMemsetAsync(h->d_opp_explored, 0, (size_t)n * 4, h->stream));
+    }
     int waves = 0;
     rc = resident_waves(h, o->occupancy, o->lds_bytes, 4096, &waves);
     if (rc) return rc;

@@ -270,6 +270,22 @@ class BatchEngine:
             rows = np.ascontiguousarray(rows, dtype=np.int32)
         self._ck(self.lib.monsoon_env_set_opponents(self.h, _ptr(weights), len(weights), _ptr(rows), int(n)), "monsoon_env_set_opponents")
 
+    def env_set_opponent_explore(self, seed, until_step, thresholds):
+        """monsoon_env_set_opponent_explore: the rule's seed and until_step, host thresholds[n] uint32 (slot i's opponent
+        explores iff its draw0 < thresholds[i]); thresholds None clears the rule.  Synchronises."""
+        if thresholds is None:
+            self._ck(self.lib.monsoon_env_set_opponent_explore(self.h, None, None, 0), "monsoon_env_set_opponent_explore")
+            return
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        ex = _lib.EnvExplore(int(seed) & 0xFFFFFFFF, int(until_step))
+        self._ck(self.lib.monsoon_env_set_opponent_explore(self.h, ctypes.byref(ex), _ptr(thresholds), len(thresholds)),
+                 "monsoon_env_set_opponent_explore")
+
+    def env_opponent_explored(self, out_ptr):
+        """monsoon_env_opponent_explored_dev: the explored decisions of every slot's opponent since the env's reset,
+        uint32[n], into device memory at out_ptr (asynchronous on the handle's stream)."""
+        self._ck(self.lib.monsoon_env_opponent_explored_dev(self.h, ctypes.c_void_p(out_ptr)), "monsoon_env_opponent_explored_dev")
+
     def debug_counters(self):
         """monsoon_debug_counters: the 192 raw counter words as uint64 (include/monsoon.h; synchronises)."""
         out = np.zeros(192, dtype=np.uint64)

@@ -5,6 +5,8 @@ legal_actions, reset, expert_agent as the opponent), each an endless sequence of
 `step` is three kernel launches on the handle's stream -- legality check, step, the scripted bot's turn, end of episode,
 re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.  The
 opponent can also be the reference's HeuristicAgent with GA weights ("heuristic": seven launches per step).
+`OpponentExplore` makes that opponent epsilon-greedy with an epsilon per slot (`reset(opponent_explore=...)`,
+`set_opponent_explore` between steps, `opponent_explored` for the counts, `opponent_explore_draws` for the draws).
 `snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device.
 Episode decks come from the reset decks, from a pool, or from a deck schedule (`reset(deck_schedule=...)`: the GA's
 exploit / explore / balance curriculum, drawn on the device per episode; `set_deck_schedule` moves its generation).
@@ -17,6 +19,7 @@ import numpy as np
 
 from ._lib import EnvAfter, EnvConfig, EnvViews, MonsoonError
 from .engine import BatchEngine
+from .fitness import hash32_array
 
 OPPONENTS = {"none": 0, "expert": 1, "heuristic": 2}
 
@@ -52,6 +55,34 @@ def select_actions(after, values):
     out = action.gather(1, first[:, None])[:, 0]
     out = torch.where(best.any(dim=1), out, torch.full_like(out, 155))
     return torch.where(n_legal == 0, torch.full_like(out, 255), out)
+
+
+class OpponentExplore:
+    """The exploration rule of a VecEnv's heuristic opponents (monsoon_env_explore and its thresholds, include/monsoon.h):
+    a decision of slot i's opponent at step index k of its episode (k < until_step where until_step > 0) commits a uniformly
+    drawn legal action instead of its arg-max with probability eps[i].  eps is a scalar (every slot) or one value per slot;
+    threshold = min(int(eps * 2**32), 0xFFFFFFFF) as engine.Explore's.  The draws are hash32(seed, episode seed, k, .):
+    opponent_explore_draws recomputes them."""
+
+    def __init__(self, eps, seed, until_step=0):
+        e = np.asarray(eps, dtype=np.float64)
+        if e.ndim > 1 or not ((e >= 0.0) & (e <= 1.0)).all():   # (a NaN fails it too)
+            raise ValueError(f"OpponentExplore: eps is a scalar or [n] with every value in [0, 1], got {eps!r}")
+        self.eps, self.seed, self.until_step = e, int(seed) & 0xFFFFFFFF, int(until_step)
+
+    def thresholds(self, n):
+        """uint32 [n]: slot i's opponent explores iff its draw0 < thresholds[i]."""
+        if self.eps.ndim == 1 and self.eps.shape != (n,):
+            raise ValueError(f"OpponentExplore: eps holds {len(self.eps)} values, the env {n} slots")
+        e = np.broadcast_to(self.eps, (n,))
+        return np.minimum(np.floor(e * 2.0**32), float(0xFFFFFFFF)).astype(np.uint32)   # (eps * 2**32 is exact: int() of it floors)
+
+
+def opponent_explore_draws(seed, episode_seeds, k):
+    """The draws of the exploring opponent for decisions at step index k of episodes with the seeds episode_seeds
+    (seed0[i] + episode[i] * seed_stride mod 2**32), broadcast together -> (draw0, draw1) uint32: the decision explores iff
+    draw0 < the slot's threshold (and k is below until_step) and then commits legal action number (draw1 * n_legal) >> 32."""
+    return hash32_array(seed, episode_seeds, k, 0), hash32_array(seed, episode_seeds, k, 1)
 
 
 class EnvSnapshot:
@@ -93,6 +124,9 @@ class VecEnv:
         self.n = 0
         self.views = None
         self._heuristic = False   # an opponent-2 env is loaded
+        self._explore = False     # ... that was reset with an exploration rule
+        self._rows = None         # the rows last given to set_opponents / reset (None = row 0 for every slot)
+        self._explored = None     # opponent_explored()'s tensor
         self._after = {}          # obs -> ((n, K), tensors, _lib.EnvAfter): the latest shape per obs flag, reused until it changes
         self._schedule = None     # the deck_schedule given to reset (a DeckEvolutionConfig or a dict) while a schedule-mode env is loaded
         self._decks = None        # decks()' tensor
@@ -123,7 +157,7 @@ class VecEnv:
         return views
 
     def reset(self, seed0, decks=None, factions=None, opponent="none", agent_side=0, max_steps=0, pool=None, seed_stride=0,
-              opponent_weights=None, opponent_rows=None, deck_schedule=None, generation=None):
+              opponent_weights=None, opponent_rows=None, deck_schedule=None, generation=None, opponent_explore=None):
         """Episode 0 of every slot: slot i plays seed0[i] with decks[i] ([n][2][12] or one [2][12] pair for all) and
         factions[i]; episode k then starts from seed0[i] + k * seed_stride (0 = n).  pool (12..128 card indices) draws
         fresh decks for every episode instead (decks must be None).  opponent "expert" puts the reference's scripted bot on
@@ -139,7 +173,12 @@ class VecEnv:
         starts; set_deck_schedule moves the generation between steps; decks() tells what every slot is playing.  Factions
         stay those of `factions` (episode 0 only, as ever).  Every faction's pool holds ua20 and Shadowfen's b005, so a
         schedule made from a config needs VecEnv(extended=1) once it draws (explore and balance phases): on the standard
-        build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised."""
+        build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised.
+
+        opponent_explore (an OpponentExplore; opponent "heuristic" only) makes the opponents epsilon-greedy from the first
+        decision on, and lets set_opponent_explore retune them between steps -- eps 0 everywhere arms the env for that and
+        plays the plain opponent bit for bit until then.  Without it the env plays the plain opponent's kernel and
+        set_opponent_explore raises."""
         if opponent not in OPPONENTS:
             raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
         seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
@@ -158,8 +197,13 @@ class VecEnv:
             opp = self._opponents(opponent_weights, opponent_rows, n)
             if self._heuristic and self.n != n:
                 raise ValueError(f"a VecEnv with a heuristic opponent keeps its {self.n} slots: open another VecEnv for {n}")
-        elif opponent_weights is not None or opponent_rows is not None:
-            raise ValueError('opponent_weights / opponent_rows need opponent="heuristic"')
+        elif opponent_weights is not None or opponent_rows is not None or opponent_explore is not None:
+            raise ValueError('opponent_weights / opponent_rows / opponent_explore need opponent="heuristic"')
+        thresholds = None
+        if opponent_explore is not None:
+            if not isinstance(opponent_explore, OpponentExplore):
+                raise ValueError("opponent_explore must be an OpponentExplore")
+            thresholds = opponent_explore.thresholds(n)
         cfg = EnvConfig()
         cfg.opponent = OPPONENTS[opponent]
         cfg.agent_side = int(agent_side)
@@ -179,12 +223,20 @@ class VecEnv:
         with self._after_torch_stream():
             if opp is not None:
                 self.engine.env_set_opponents(opp[0], opp[1], n)
+            if opp is not None:
+                if thresholds is not None:
+                    self.engine.env_set_opponent_explore(opponent_explore.seed, opponent_explore.until_step, thresholds)
+                elif self._explore:   # the loaded env holds the handle's rule: it cannot be cleared, silent is the same play
+                    self.engine.env_set_opponent_explore(0, 0, np.zeros(n, dtype=np.uint32))
             self._heuristic = False
             self._schedule = None
             if sched is not None:
                 self.engine.env_set_schedule(sched)
             self.engine.env_reset(cfg, views, seed0, decks, factions)
             self._heuristic = opp is not None
+            if opp is not None:
+                self._explore = thresholds is not None or self._explore
+                self._rows = opp[1]
             self._schedule = deck_schedule
         return self.views
 
@@ -224,6 +276,43 @@ class VecEnv:
         w, r = self._opponents(weights, rows, self.n)
         with self._after_torch_stream():
             self.engine.env_set_opponents(w, r, self.n)
+        self._rows = r
+
+    def eps_by_row(self, eps_rows):
+        """A per-individual epsilon [k] -> the per-slot values [n] for OpponentExplore, through the rows last given to
+        set_opponents / reset (slot i gets eps_rows[rows[i]]; no rows = row 0 for every slot)."""
+        e = np.asarray(eps_rows, dtype=np.float64)
+        if e.ndim != 1 or len(e) == 0:
+            raise ValueError(f"eps_rows must be [k], got {np.shape(eps_rows)}")
+        rows = np.zeros(self.n, dtype=np.int64) if self._rows is None else np.asarray(self._rows, dtype=np.int64)
+        if len(rows) and rows.max() >= len(e):
+            raise ValueError(f"eps_rows holds {len(e)} values, the slots play rows up to {int(rows.max())}")
+        return e[rows]
+
+    def set_opponent_explore(self, opponent_explore):
+        """Retune the exploring opponents between steps (monsoon_env_set_opponent_explore): the OpponentExplore's seed,
+        until_step and per-slot epsilons (eps_by_row makes them from per-individual ones) apply from the next decision; a
+        captured step graph stays valid.  Needs reset(opponent="heuristic", opponent_explore=...) first (MonsoonError).
+        Synchronises the env's stream."""
+        if not (self._heuristic and self._explore):
+            raise MonsoonError('VecEnv.set_opponent_explore needs reset(opponent="heuristic", opponent_explore=...) first')
+        if not isinstance(opponent_explore, OpponentExplore):
+            raise ValueError("opponent_explore must be an OpponentExplore")
+        thresholds = opponent_explore.thresholds(self.n)
+        with self._after_torch_stream():
+            self.engine.env_set_opponent_explore(opponent_explore.seed, opponent_explore.until_step, thresholds)
+
+    def opponent_explored(self):
+        """The decisions of every slot's opponent whose draw said "explore", since reset (monsoon_env_opponent_explored_dev):
+        an int32 CUDA tensor [n], allocated on the first call per n and overwritten in place by every later one (a later
+        call allocates nothing and can be captured).  Stream ordering as in step."""
+        import torch
+        if not (self._heuristic and self._explore):
+            raise MonsoonError('VecEnv.opponent_explored needs reset(opponent="heuristic", opponent_explore=...) first')
+        if self._explored is None or self._explored.shape[0] != self.n:
+            self._explored = torch.zeros(self.n, dtype=torch.int32, device=torch.device("cuda", self.device))
+        self._on_env_stream(lambda: self.engine.env_opponent_explored(self._explored.data_ptr()))
+        return self._explored
 
     @staticmethod
     def _schedule_params(deck_schedule, generation):
@@ -411,4 +500,4 @@ class VecEnv:
         return self.engine.state_hash()
 
 
-__all__ = ["VecEnv", "EnvSnapshot", "OPPONENTS", "MonsoonError", "select_actions"]
+__all__ = ["VecEnv", "EnvSnapshot", "OpponentExplore", "opponent_explore_draws", "OPPONENTS", "MonsoonError", "select_actions"]
