@@ -141,6 +141,17 @@ int monsoon_debug_op(monsoon_t* h, int32_t idx, const int32_t* op, int32_t n_op,
  * Re-seeds the stream buffers of game slot 0. */
 int monsoon_debug_kat(monsoon_t* h, int32_t kind, uint32_t seed, int32_t n, const void* in, void* out);
 
+/* Known-answer entry of the sampler of monsoon_rollout_sample (below), no game involved: row i is a decision with the
+ * legal list of ranks 0 .. n_legal[i] - 1 (1 .. 156), scores[i][j] the j-th action's score (double[m][156], entries behind
+ * n_legal[i] are not read), best[i], inv_temperature[i] and draw1[i].  Per row: out_rank[i] = j* (-1 where total == 0),
+ * out_total[i] = the sum of the weights, out_weight[i] = w_{j*} (0 where total == 0).  Computed by the device function the
+ * rollout kernel calls, one wavefront per row.  1 <= m <= 65536; MONSOON_ERR_ARG for a null pointer, an m or an n_legal
+ * out of range.  The values of best and inv_temperature are not checked: this entry is how their corner cases are put to
+ * the device. */
+int monsoon_debug_sample_kat(monsoon_t* h, int32_t m, const double* scores, const int32_t* n_legal, const double* best,
+                             const double* inv_temperature, const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total,
+                             uint32_t* out_weight);
+
 /* Debugging aid: the raw HBM record of game idx (monsoon_amd/csrc/state.h layout); buf must hold 4096 bytes. */
 int monsoon_debug_raw(monsoon_t* h, int32_t idx, uint8_t* buf, int32_t* len);
 
@@ -283,6 +294,65 @@ int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_indiv
                             int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                             int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log,
                             const monsoon_explore* ex, const monsoon_explore_log* xlog);
+
+/* A logged rollout whose heuristic decisions may SAMPLE: softmax over the decision's scores with a temperature.
+ * WHEN a decision leaves its arg-max is monsoon_rollout_explore's rule word for word -- the side's bit in sm->rule.sides,
+ * until_step, draw0 = hash32(seed, match.seed, k, 0) < threshold, draw1 = hash32(seed, match.seed, k, 1) -- only WHAT it
+ * commits instead changes.  Let s_j be the score of the j-th action of the ascending legal list (what monsoon_decide
+ * reports in out_scores: 0.0 for a look-ahead that raised or faulted) and best the decision's best score (log->score):
+ *
+ *   x_j   = (s_j - best) * inv_temperature      two operations, each rounded once; inv_temperature = 1.0 / T, the caller's
+ *   w_j   = weight24(x_j)                       uint32 in [0, 2**24]
+ *   total = sum_j w_j                           <= 156 * 2**24 < 2**32: exact, whatever the order
+ *   r     = ((uint64_t)draw1 * total) >> 32     in [0, total)
+ *   j*    = the smallest j with w_0 + ... + w_j > r
+ *
+ * weight24(x) = floor(exp(x) * 2**24), computed without a library exponential and with no term contracted into an fma
+ * (monsoon_amd/csrc/sample_weight.h; monsoon_amd/game_log.py sample_weights is the same function in numpy, bit for bit):
+ *
+ *   if !(x >= -32.0) return 0                   also NaN and -inf
+ *   n = floor(x * 0x1.71547652b82fep+0 + 0.5)
+ *   r = (x - n * 0x1.62e42feep-1) - n * 0x1.a39ef35793c76p-33
+ *   p = c10; for k = 9 .. 0: p = p * r + c_k    c_k = the double nearest 1 / k!
+ *   return (uint32) floor(ldexp(p, (int)n + 24))
+ *
+ * weight24(0) = 2**24: the arg-max weighs 2**24 and so does every action tied with it, so total >= 2**24 whenever best is
+ * a finite number.  TIES: actions tied for the best score share the probability equally -- a sampling decision may commit
+ * an action other than the arg-max whose score equals the best one; that is the rule's meaning, not an accident.
+ * total == 0 happens only when best is NaN or infinite: the decision commits its arg-max, explored is still 1 (the draw
+ * said so), weight_total and taken_weight are 0.
+ * What does not change from monsoon_rollout_explore: the arg-max runs over all candidates; log->score is the best score,
+ * log->action what was committed; xlog->greedy, explored and taken_score mean what they mean there; a committed
+ * candidate's fault or raising observation ends the game as a draw with that code; no draw touches the game's numpy
+ * stream; a game's draws depend on its seed and step alone, not on the batch or the record build; THE COUNTS OF SUCH A
+ * CALL ARE NOT FITNESS.
+ * What does change: the choice is known only after the last look-ahead, so a decision that samples an action other than
+ * its arg-max steps that action once more from the parent record (bit-identical to its look-ahead: the clone carries the
+ * stream window).  lookahead_steps keeps counting n_legal per decision: A SAMPLING DECISION EXECUTES ONE STEP MORE THAN
+ * IT COUNTS (none where it drew its arg-max).
+ * slog (may be NULL, each array may be NULL) adds per entry weight_total = total and taken_weight = w of the committed
+ * action.  BEHAVIOUR PROBABILITY: taken_weight / weight_total is the probability of the committed action GIVEN THAT THE
+ * DECISION SAMPLED.  For a learner that weights off-policy: a decision of a side and step the rule covers samples with
+ * probability eps = threshold / 2**32, so the behaviour policy gave the committed action a
+ *   mu(a) = (1 - eps) * [a == greedy] + eps * taken_weight / weight_total     where explored == 1 and weight_total > 0,
+ * and for an entry with explored == 0 (action == greedy) mu(a) = (1 - eps) + eps * p_greedy, whose p_greedy the log does
+ * not carry (weight_total is 0 there); with eps == 1 every covered decision sampled and mu is the ratio itself.
+ * sm == NULL or sm->rule.threshold == 0: no decision samples and every output of monsoon_rollout_logged is what that
+ * call writes, bit for bit; greedy == action, explored == 0, taken_score == score on decisions, both weights 0.
+ * Device log: an entry takes B = monsoon_rollout_explore's bytes + 4 [weight_total] + 4 [taken_weight], 1 .. 29, counting
+ * the arrays asked for, and a call plays min(max_games, max(1, 256 MiB / (B * max_turns))) games per batch.  The call
+ * also keeps the handle's score table ([max_games][156] doubles, monsoon_decide's) on the device: the kernel parks a
+ * decision's scores there.  The kernel is one more instantiation of the decision loop at the build's default variant
+ * (k_play_sample).
+ * MONSOON_ERR_ARG with nothing launched: whatever monsoon_rollout_explore refuses, and an inv_temperature that is NaN,
+ * infinite or <= 0. */
+typedef struct { monsoon_explore rule; double inv_temperature; } monsoon_sample;    /* inv_temperature finite and > 0 */
+typedef struct { uint32_t* weight_total; uint32_t* taken_weight; } monsoon_sample_log; /* HOST [n_matches][max_turns], each may be NULL;
+                                                                                         0 for a bot step, a decision that did not sample, and behind */
+int monsoon_rollout_sample(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                           int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
+                           int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log,
+                           const monsoon_sample* sm, const monsoon_explore_log* xlog, const monsoon_sample_log* slog);
 
 /* Logged games played again on the device into the (state, action) rows a learner trains on: one row per kept log entry,
  * holding the state BEFORE that entry's step.  No decision is recomputed: every entry costs one committed step.

@@ -82,6 +82,14 @@ class ExploreLog(ctypes.Structure):     # monsoon_explore_log: caller-owned host
     _fields_ = [(name, ctypes.c_void_p) for name in ("greedy", "explored", "taken_score")]
 
 
+class Sample(ctypes.Structure):         # monsoon_sample: the rule of monsoon_rollout_sample (when, as Explore; what, by the temperature)
+    _fields_ = [("rule", Explore), ("inv_temperature", ctypes.c_double)]
+
+
+class SampleLog(ctypes.Structure):      # monsoon_sample_log: caller-owned host buffers (NULL = not wanted)
+    _fields_ = [(name, ctypes.c_void_p) for name in ("weight_total", "taken_weight")]
+
+
 class ReplayRows(ctypes.Structure):     # monsoon_replay_rows: caller-owned device buffers (NULL = not wanted, except action)
     _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "legal", "obs_raises", "to_play", "action", "bot", "game", "step",
                                                       "state_hash")]
@@ -136,6 +144,11 @@ SIGNATURES = {
                                                ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.POINTER(RolloutLog), ctypes.POINTER(Explore),
                                                ctypes.POINTER(ExploreLog)]),
+    "monsoon_rollout_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(RolloutLog), ctypes.POINTER(Sample),
+                                              ctypes.POINTER(ExploreLog), ctypes.POINTER(SampleLog)]),
+    "monsoon_debug_sample_kat": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 8),
     "monsoon_replay_logged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.POINTER(ReplayRows), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),

@@ -132,6 +132,32 @@ inline ExploreLog explore_log(size_t entries, bool score, bool n_legal, bool gre
   l.total = at;
   return l;
 }
+// d_log of monsoon_rollout_sample: the exploring call's arrays and the two the sampling kernel adds, by falling element
+// size; an array the caller does not ask for takes no room.  sample_entry_bytes is what one entry takes (1 .. 29).
+struct SampleLog { size_t score, taken_score, weight_total, taken_weight, n_legal, action, greedy, explored, total; };   // f64 | f64 | u32 | u32 | i16 | u8 | u8 | u8
+constexpr size_t sample_entry_bytes(bool score, bool n_legal, bool greedy, bool explored, bool taken_score, bool weight_total, bool taken_weight) {
+  return explore_entry_bytes(score, n_legal, greedy, explored, taken_score) + (weight_total ? 4 : 0) + (taken_weight ? 4 : 0);
+}
+inline SampleLog sample_log(size_t entries, bool score, bool n_legal, bool greedy, bool explored, bool taken_score, bool weight_total,
+                            bool taken_weight) {
+  SampleLog l;
+  size_t at = 0;
+  const auto field = [&](bool on, size_t bytes) {
+    const size_t off = on ? at : NONE;
+    if (on) at += entries * bytes;
+    return off;
+  };
+  l.score = field(score, 8);
+  l.taken_score = field(taken_score, 8);
+  l.weight_total = field(weight_total, 4);
+  l.taken_weight = field(taken_weight, 4);
+  l.n_legal = field(n_legal, 2);
+  l.action = field(true, 1);
+  l.greedy = field(greedy, 1);
+  l.explored = field(explored, 1);
+  l.total = at;
+  return l;
+}
 // games per batch of a logged call: as many as `budget` bytes of device log hold, one at least, max_games at most
 constexpr size_t log_batch_cap(size_t max_games, size_t budget, size_t entry_bytes, size_t max_turns) {
   return budget / (entry_bytes * max_turns) < 1 ? 1 : budget / (entry_bytes * max_turns) < max_games ? budget / (entry_bytes * max_turns) : max_games;

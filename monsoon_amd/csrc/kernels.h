@@ -3,7 +3,7 @@
 // them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, env_opp.hip, env_opp_explore.hip and env_after.hip hold one
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, play_sample.hip, env_opp.hip, env_opp_explore.hip and env_after.hip hold one
 // further instantiation each, replay_log.hip one of the rules core without the decision loop; monsoon_hip.hip holds the
 // API kernels and the host side.
 //
@@ -39,6 +39,7 @@
 #include "coop_draw.h"
 #include "coop_legal.h"
 #include "pass_glue.h"
+#include "sample_weight.h"
 
 namespace msbk {
 using namespace msb;
@@ -414,6 +415,70 @@ __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, co
   }
 }
 
+// What play_game<.., SAMPLE = true> needs beyond the PlayLog and the PlayExplore (k_play_sample, play_sample.hip;
+// include/monsoon.h monsoon_rollout_sample): the inverse temperature and the two further log arrays (rows like the
+// PlayLog's, each may be null).  An argument of that kernel alone; play_game sees a pointer to it.
+struct PlaySample {
+  double inv_temperature;
+  uint32_t* weight_total;   // [n][stride] sum of the decision's weights
+  uint32_t* taken_weight;   // [n][stride] weight of the committed action
+};
+// The draw of a sampling decision over the actions in the masks (bit l of m_i = action 64 i + l, whose score is sc[64 i + l]),
+// by the whole wavefront: lane l takes actions l, l + 64 and l + 128, w = weight24((score - best) * inv_t) where the
+// action is legal and 0 elsewhere, an inclusive integer scan across the wave in ascending action order, r = (draw1 * total)
+// >> 32, and the first action whose prefix exceeds r (a ballot) -- its weight is not 0, because the prefix before it does
+// not exceed r.  Everything is integer from the weights on, so no order of summation is imposed.  total == 0 (best is NaN
+// or infinite): pos = -1.  All arguments but `lane` are wave-uniform and so is the result.
+struct SamplePick {
+  int pos;
+  uint32_t total, w;
+};
+__device__ MSB_INL SamplePick sample_pick(const double* sc, const uint64_t m0, const uint64_t m1, const uint64_t m2, const double best,
+                                          const double inv_t, const uint32_t draw1, const int lane) {
+  const uint64_t m[3] = {m0, m1, m2};
+  uint32_t w[3], p[3];
+  uint32_t before = 0u;
+  _Pragma("unroll") for (int i = 0; i < 3; i++) {
+    w[i] = 0u;
+    if ((m[i] >> lane) & 1ull) w[i] = weight24((sc[64 * i + lane] - best) * inv_t);
+    uint32_t q = w[i];
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t t = __shfl_up(q, off);
+      if (lane >= off) q += t;
+    }
+    p[i] = before + q;
+    before = (uint32_t)__builtin_amdgcn_readlane((int)p[i], 63);
+  }
+  const uint32_t total = before;   // <= 156 * 2**24
+  if (total) {
+    const uint32_t r = (uint32_t)(((unsigned long long)draw1 * total) >> 32);   // in [0, total)
+    _Pragma("unroll") for (int i = 0; i < 3; i++) {
+      const unsigned long long bal = __ballot(p[i] > r);
+      if (bal) {
+        const int l = __builtin_ctzll(bal);
+        return SamplePick{64 * i + l, total, (uint32_t)__builtin_amdgcn_readlane((int)w[i], l)};
+      }
+    }
+  }
+  return SamplePick{-1, 0u, 0u};
+}
+// Does the decision at committed step k leave its arg-max (explore_rank's three conditions and draw0), and with which draw1.
+__device__ MSB_INL bool sample_draw(const PlayExplore& ex, const uint32_t match_seed, const int side, const int k, const int n_legal, uint32_t& draw1) {
+  draw1 = 0u;
+  if (!((ex.sides >> side) & 1u) || (ex.until_step > 0 && k >= ex.until_step) || n_legal <= 0) return false;
+  if (explore_hash32(ex.seed, match_seed, (uint32_t)k, 0u) >= ex.threshold) return false;
+  draw1 = explore_hash32(ex.seed, match_seed, (uint32_t)k, 1u);
+  return true;
+}
+__device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, const int g, const int lane, const int k, const uint32_t total,
+                                   const uint32_t taken) {
+  if (lane == 0 && k < lg.stride) {
+    const size_t at = (size_t)g * lg.stride + k;
+    if (sp.weight_total) sp.weight_total[at] = total;
+    if (sp.taken_weight) sp.taken_weight[at] = taken;
+  }
+}
+
 // Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
 // to the last; HBM sees one read and one write of it per call.
 // ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
@@ -429,6 +494,12 @@ __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, co
 // the r-th legal action (xt->r) instead of the arg-max.  Everything new is wave-uniform: the pass that holds rank r takes
 // lane r - base -- its record into v_best, its fault and feature flag, its features into wf[20..29], its score -- and on
 // such a decision the running arg-max moves run_a / run_s only, so v_best is written exactly once, in whichever pass.
+// SAMPLE = true (k_play_sample, play_sample.hip; with LOG = true and EXPLORE = false): the passes run as without a rule --
+// the arg-max and its record in v_best -- and every candidate's score also goes to the game's row of b.scores.  After the
+// last pass a decision whose draw says so (sample_draw) draws an action from the softmax over those scores (sample_pick)
+// and, unless that is the arg-max, steps it once more from the parent record on column 0 (the clone carries the stream
+// window, so the step is the look-ahead's bit for bit): that successor, its fault and no features are what the commit takes.
+// The decision's scalars live and die in that one block in front of the commit; `sp` is the kernel's.
 //
 // MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
@@ -465,11 +536,12 @@ __device__ MSB_INL void log_explore(const PlayExplore& ex, const PlayLog& lg, co
   if (feat_ok && lane < 10) wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl_ * 10 + lane]; \
   __syncthreads();                                                                                  \
   MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl_])
-template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false>
+template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false, bool SAMPLE = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
-                                  ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr) {
+                                  ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr, const PlaySample* const sp = nullptr) {
   static_assert(!EXPLORE || (LOG && !ENV) || (ENV && !VS && !LOG), "the exploring form is a logging rollout or the env's opponent");
+  static_assert(!SAMPLE || (LOG && !ENV && !EXPLORE), "the sampling form is a logging rollout with a rule of its own");
   typedef PlayLds<U> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -669,7 +741,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         }
       }
       if (active) {
-        if (!ENV && write_scores) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;
+        if constexpr (SAMPLE) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;   // (what the sampler reads after the last pass)
+        else if (!ENV && write_scores) b.scores[(size_t)g * MONSOON_NUM_ACTIONS + a] = s;
         my_fault = f ? f : (raises ? FAULT_INT_CARD : 0);
       }
       PROF_MARK(5);   // after-features + score
@@ -724,6 +797,40 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         }
       }
       PROF_MARK(6);   // argmax + new best into registers
+    }
+    if constexpr (SAMPLE) {
+      // column 0 is the current record again: the rule asks whose turn it is, and a sampled action is stepped from it
+      __syncthreads();
+      MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
+      __syncthreads();
+      uint32_t draw1, total = 0u, taken_w = 0u;
+      const bool on = sample_draw(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
+                                  meta.steps, n_legal, draw1);
+      int take = run_a;
+      double take_s = run_s;
+      if (on) {   // (uniform)
+        const double* row = b.scores + (size_t)g * MONSOON_NUM_ACTIONS;   // this decision's scores: the barriers above made them visible
+        const SamplePick pk = sample_pick(row, ls.mask[0], ls.mask[1], ls.mask[2], run_s, sp->inv_temperature, draw1, lane);
+        total = pk.total;   // (0: the best score is NaN or infinite, the decision commits its arg-max)
+        taken_w = pk.w;
+        if (pk.total && pk.pos != run_a) {   // (the arg-max's record is in v_best already: nothing to step)
+          take = pk.pos;
+          take_s = row[take];
+          int fs = 0;
+          if (lane == 0) {   // (the other lanes wait at the barrier, as in the bot's round)
+            ce.step(take);
+            fs = ce.fault();
+            if (!fs && ce.observation_raises()) fs = FAULT_INT_CARD;
+          }
+          __syncthreads();
+          cfault = __builtin_amdgcn_readfirstlane(fs);
+          feat_ok = 0;   // the next decision computes its "before" side
+          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U])
+        }
+      }
+      log_explore(ex, lg, g, lane, meta.steps, run_a, on, take_s);   // (greedy = the arg-max; run_s stays the decision's best score)
+      log_sample(*sp, lg, g, lane, meta.steps, total, taken_w);
+      run_a = take;
     }
     MSB_COMMIT_BEST()
     if constexpr (EXPLORE) {   // the log keeps the arg-max next to what was committed; the env counts the slot's explored decisions
@@ -797,7 +904,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
-// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_replay_log, k_env_opp, k_env_opp_explore): `mine` / `other` are this launch's counter
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_play_explore, k_play_sample, k_replay_log, k_env_opp, k_env_opp_explore): `mine` / `other` are this launch's counter
 // set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
 // nothing for it leaves before enter(), which runs once ahead of the first game.
 template <class Enter, class Play>
@@ -868,5 +975,15 @@ struct ExploreOps : KernelOps {
                PlayLog lg, PlayExplore ex);   // never split, like LogOps::play
 };
 const ExploreOps* monsoon_play_explore_ops();
+
+// k_play_sample<DEFAULT_U, DEFAULT_W> (play_sample.hip): k_play_log whose decisions may sample (PlayExplore's rule, PlaySample);
+// kat is k_sample_kat, sample_pick on caller-given rows (monsoon_debug_sample_kat), one wavefront per row.
+struct SampleOps : KernelOps {
+  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+               PlayLog lg, PlayExplore ex, PlaySample sp);   // never split, like LogOps::play
+  void (*kat)(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,
+              const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total, uint32_t* out_weight);
+};
+const SampleOps* monsoon_play_sample_ops();
 
 }  // namespace msbk

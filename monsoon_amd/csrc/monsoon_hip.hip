@@ -671,8 +671,8 @@ __global__ void k_ga_select(const double* fitness, int n, int* out_order) {
 // ================================================================================================
 // What launch_play launches: k_play of the handle's variant, k_play_vs (the kernel that knows the scripted bot, the
 // build's default variant), k_play_log (k_play_vs that writes every committed step into a log) or k_play_explore (k_play_log
-// whose decisions may explore).
-enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_EXPLORE = 3, PLAY_KINDS = 4 };
+// whose decisions may explore) or k_play_sample (k_play_log whose decisions may sample).
+enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_EXPLORE = 3, PLAY_SAMPLE = 4, PLAY_KINDS = 5 };
 
 // Device memory: everything the handle allocates is recorded in `mem` when it is allocated and freed from that record by
 // monsoon_destroy; the pointers below and in `b`, `env` and `env_sched` only refer to it.  Events and the split streams
@@ -1458,6 +1458,43 @@ int monsoon_debug_kat(monsoon_t* h, int32_t kind, uint32_t seed, int32_t n, cons
   return MONSOON_OK;
 }
 
+// sample_pick (kernels.h) on m caller-given rows: k_sample_kat of play_sample.hip, one wavefront per row.
+int monsoon_debug_sample_kat(monsoon_t* h, int32_t m, const double* scores, const int32_t* n_legal, const double* best,
+                             const double* inv_temperature, const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total,
+                             uint32_t* out_weight) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!scores || !n_legal || !best || !inv_temperature || !draw1 || !out_rank || !out_total || !out_weight || m <= 0 || m > 65536)
+    return bad_arg(h, "monsoon_debug_sample_kat", "bad argument");
+  for (int i = 0; i < m; i++)
+    if (n_legal[i] < 1 || n_legal[i] > MONSOON_NUM_ACTIONS) return bad_arg(h, "monsoon_debug_sample_kat", "n_legal of row " + std::to_string(i) + " out of range");
+  HIP_TRY(h, bind_device(h));
+  const size_t rows = (size_t)m;
+  DevOwner tmp;   // freed on return
+  double *d_scores = nullptr, *d_best = nullptr, *d_inv = nullptr;
+  int32_t *d_n = nullptr, *d_rank = nullptr;
+  uint32_t *d_draw = nullptr, *d_total = nullptr, *d_weight = nullptr;
+  HIP_TRY(h, tmp.alloc(&d_scores, rows * MONSOON_NUM_ACTIONS * 8));
+  HIP_TRY(h, tmp.alloc(&d_best, rows * 8));
+  HIP_TRY(h, tmp.alloc(&d_inv, rows * 8));
+  HIP_TRY(h, tmp.alloc(&d_n, rows * 4));
+  HIP_TRY(h, tmp.alloc(&d_draw, rows * 4));
+  HIP_TRY(h, tmp.alloc(&d_rank, rows * 4));
+  HIP_TRY(h, tmp.alloc(&d_total, rows * 4));
+  HIP_TRY(h, tmp.alloc(&d_weight, rows * 4));
+  HIP_TRY(h, hipMemcpy(d_scores, scores, rows * MONSOON_NUM_ACTIONS * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(d_best, best, rows * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(d_inv, inv_temperature, rows * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(d_n, n_legal, rows * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(d_draw, draw1, rows * 4, hipMemcpyHostToDevice));
+  monsoon_play_sample_ops()->kat(h->stream, m, d_scores, d_n, d_best, d_inv, d_draw, d_rank, d_total, d_weight);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(out_rank, d_rank, rows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(out_total, d_total, rows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(out_weight, d_weight, rows * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MONSOON_OK;
+}
+
 int monsoon_game_faults(monsoon_t* h, uint8_t* out) {
   int rc = check_ready(h);
   if (rc) return rc;
@@ -1618,20 +1655,24 @@ struct PlayCall {
   bool write_scores = false;     // every candidate's score goes to b.scores
   bool timed = false;            // an event pair of the handle round the call (kernel_ms)
   bool split = false;            // PLAY only (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below
-  const PlayLog* log = nullptr;  // PLAY_LOG and PLAY_EXPLORE (monsoon_rollout_logged / _explore): where every committed step is written
-  const PlayExplore* explore = nullptr;   // PLAY_EXPLORE only: the exploration rule, the batch's match seeds, the further log arrays
+  const PlayLog* log = nullptr;  // PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE (monsoon_rollout_logged / _explore / _sample): where every committed step is written
+  const PlayExplore* explore = nullptr;   // PLAY_EXPLORE and PLAY_SAMPLE: the exploration rule, the batch's match seeds, the further log arrays
+  const PlaySample* sample = nullptr;     // PLAY_SAMPLE only: the inverse temperature and the two weight arrays
 };
 
-// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG and PLAY_EXPLORE are never split.
+// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE are never split.
 static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
-  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG, explore = call.kind == PLAY_EXPLORE;
+  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG, explore = call.kind == PLAY_EXPLORE, sample = call.kind == PLAY_SAMPLE;
   bool timed = call.timed;
   if (h->bot_rows && call.kind == PLAY) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
   }
   const VariantOps* vp = vs ? monsoon_vs_expert_ops() : h->var;
-  const KernelOps* v = explore ? static_cast<const KernelOps*>(monsoon_play_explore_ops()) : log ? static_cast<const KernelOps*>(monsoon_play_log_ops()) : vp;
+  const KernelOps* v = sample    ? static_cast<const KernelOps*>(monsoon_play_sample_ops())
+                       : explore ? static_cast<const KernelOps*>(monsoon_play_explore_ops())
+                       : log     ? static_cast<const KernelOps*>(monsoon_play_log_ops())
+                                 : vp;
   const int lds = v->lds_bytes + g_lds_pad;
   int& grid_waves = h->grid_waves[call.kind];
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
@@ -1693,7 +1734,10 @@ static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
   }
   for (int s = 0; s < parts; s++) {
     const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
-    if (explore)   // (parts == 1)
+    if (sample)   // (parts == 1)
+      monsoon_play_sample_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log, *call.explore,
+                                      *call.sample);
+    else if (explore)   // (parts == 1)
       monsoon_play_explore_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log, *call.explore);
     else if (log)   // (parts == 1)
       monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log);
@@ -1795,6 +1839,10 @@ constexpr size_t LOG_BUDGET = (size_t)256 << 20;
 struct ExploreCall {
   const monsoon_explore_log* host;
   PlayExplore dev;
+  // a sampling call (monsoon_rollout_sample) on top: its further host arrays and its kernel's own argument
+  bool sample = false;
+  const monsoon_sample_log* shost = nullptr;
+  PlaySample sdev = {};
 };
 
 // Matches [base, base + n) of a rollout: load them, one launch plays the whole batch to the end, collect.  A batch without
@@ -1818,14 +1866,17 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
     if (dex.greedy) HIP_TRY(h, hipMemsetAsync(dex.greedy, 0xFF, cnt, h->stream));
     if (dex.explored) HIP_TRY(h, hipMemsetAsync(dex.explored, 0, cnt, h->stream));
     if (dex.taken_score) HIP_TRY(h, hipMemsetAsync(dex.taken_score, 0xFF, cnt * 8, h->stream));
+    if (xc->sdev.weight_total) HIP_TRY(h, hipMemsetAsync(xc->sdev.weight_total, 0, cnt * 4, h->stream));   // (both weights 0)
+    if (xc->sdev.taken_weight) HIP_TRY(h, hipMemsetAsync(xc->sdev.taken_weight, 0, cnt * 4, h->stream));
   }
   PlayCall call;
-  call.kind = xc ? PLAY_EXPLORE : log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
+  call.kind = xc && xc->sample ? PLAY_SAMPLE : xc ? PLAY_EXPLORE : log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
   call.max_turns = max_turns;
   call.rounds = max_turns + 1;
   call.timed = true;
   call.log = log ? &dlog : nullptr;
   call.explore = xc ? &dex : nullptr;
+  call.sample = xc && xc->sample ? &xc->sdev : nullptr;
   rc = launch_play(h, n, call);
   if (rc) return rc;
   hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
@@ -1840,6 +1891,10 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
     if (dex.greedy) HIP_TRY(h, hipMemcpyAsync(xc->host->greedy + row, dex.greedy, cnt, hipMemcpyDeviceToHost, h->stream));
     if (dex.explored) HIP_TRY(h, hipMemcpyAsync(xc->host->explored + row, dex.explored, cnt, hipMemcpyDeviceToHost, h->stream));
     if (dex.taken_score) HIP_TRY(h, hipMemcpyAsync(xc->host->taken_score + row, dex.taken_score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    if (xc->sdev.weight_total)
+      HIP_TRY(h, hipMemcpyAsync(xc->shost->weight_total + row, xc->sdev.weight_total, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    if (xc->sdev.taken_weight)
+      HIP_TRY(h, hipMemcpyAsync(xc->shost->taken_weight + row, xc->sdev.taken_weight, cnt * 4, hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return drain_timing(h);
@@ -1847,11 +1902,12 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
 
 // monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and
 // monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log);
-// monsoon_rollout_explore is the logged call with ex non-null (played by k_play_explore, xlog's arrays copied likewise)
+// monsoon_rollout_explore is the logged call with ex non-null (played by k_play_explore, xlog's arrays copied likewise),
+// monsoon_rollout_sample that call with sm non-null too (ex = &sm->rule; played by k_play_sample, slog's arrays likewise)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                         int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
                         int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr, const monsoon_explore* ex = nullptr,
-                        const monsoon_explore_log* xlog = nullptr) {
+                        const monsoon_explore_log* xlog = nullptr, const monsoon_sample* sm = nullptr, const monsoon_sample_log* slog = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
@@ -1880,7 +1936,27 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
   int cap = h->cfg.max_games;
   PlayLog dlog = {nullptr, nullptr, nullptr, max_turns};
   ExploreCall xc = {xlog, PlayExplore{}};
-  if (ex) {
+  if (sm) {   // (ex == &sm->rule)
+    const bool gr = xlog && xlog->greedy, xp = xlog && xlog->explored, ts = xlog && xlog->taken_score;
+    const bool wt = slog && slog->weight_total, tw = slog && slog->taken_weight;
+    cap = (int)layout::log_batch_cap((size_t)cap, LOG_BUDGET, layout::sample_entry_bytes(log->score, log->n_legal, gr, xp, ts, wt, tw), (size_t)max_turns);
+    const layout::SampleLog l = layout::sample_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal, gr, xp, ts, wt, tw);
+    HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
+    // the kernel parks every decision's scores in the game's row of the score table (monsoon_decide's, allocated on first use)
+    if (!h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
+    if (log->score) dlog.score = (double*)(h->d_log + l.score);
+    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
+    dlog.action = h->d_log + l.action;
+    xc.dev.seed = ex->seed, xc.dev.threshold = ex->threshold, xc.dev.sides = ex->sides, xc.dev.until_step = ex->until_step;
+    if (gr) xc.dev.greedy = h->d_log + l.greedy;
+    if (xp) xc.dev.explored = h->d_log + l.explored;
+    if (ts) xc.dev.taken_score = (double*)(h->d_log + l.taken_score);
+    xc.sample = true;
+    xc.shost = slog;
+    xc.sdev.inv_temperature = sm->inv_temperature;
+    if (wt) xc.sdev.weight_total = (uint32_t*)(h->d_log + l.weight_total);
+    if (tw) xc.sdev.taken_weight = (uint32_t*)(h->d_log + l.taken_weight);
+  } else if (ex) {
     const bool gr = xlog && xlog->greedy, xp = xlog && xlog->explored, ts = xlog && xlog->taken_score;
     cap = (int)layout::log_batch_cap((size_t)cap, LOG_BUDGET, layout::explore_entry_bytes(log->score, log->n_legal, gr, xp, ts), (size_t)max_turns);
     const layout::ExploreLog l = layout::explore_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal, gr, xp, ts);
@@ -1965,6 +2041,24 @@ int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_indiv
   const monsoon_explore* rule = (ex && ex->threshold) ? ex : wants ? &never : nullptr;
   return rollout_impl(h, "monsoon_rollout_explore", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
                       max_turns, out_counts, out_results, out_steps, log, rule, xlog);
+}
+
+// monsoon_rollout_explore's call with a sampling rule.  As there, a rule that never samples still goes through the kernel
+// where one of xlog's or slog's arrays is asked for (it fills them); without any it is the logged call itself.
+int monsoon_rollout_sample(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                           const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                           int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_sample* sm, const monsoon_explore_log* xlog,
+                           const monsoon_sample_log* slog) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_sample", "log and log->action are required");
+  if (sm && (sm->rule.sides & ~3u)) return bad_arg(h, "monsoon_rollout_sample", "sides holds a bit above bit 1");
+  if (sm && !(sm->inv_temperature > 0.0 && sm->inv_temperature < INFINITY))   // (a NaN fails the first test)
+    return bad_arg(h, "monsoon_rollout_sample", "inv_temperature must be finite and > 0");
+  static const monsoon_sample never = {{0u, 0u, 0u, 0}, 1.0};
+  const bool wants = (xlog && (xlog->greedy || xlog->explored || xlog->taken_score)) || (slog && (slog->weight_total || slog->taken_weight));
+  const monsoon_sample* rule = (sm && sm->rule.threshold) ? sm : wants ? &never : nullptr;
+  return rollout_impl(h, "monsoon_rollout_sample", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
+                      max_turns, out_counts, out_results, out_steps, log, rule ? &rule->rule : nullptr, xlog, rule, slog);
 }
 
 // Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.

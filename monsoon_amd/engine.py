@@ -15,6 +15,11 @@ def explore_entry_bytes(scores=True, n_legal=True, greedy=True, explored=True, t
     return 1 + 8 * bool(scores) + 2 * bool(n_legal) + bool(greedy) + bool(explored) + 8 * bool(taken_score)
 
 
+def sample_entry_bytes(scores=True, n_legal=True, greedy=True, explored=True, taken_score=True, weight_total=True, taken_weight=True):
+    """Bytes of device log one entry of monsoon_rollout_sample takes, by the arrays asked for (action always): 1 .. 29."""
+    return explore_entry_bytes(scores, n_legal, greedy, explored, taken_score) + 4 * bool(weight_total) + 4 * bool(taken_weight)
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
@@ -23,14 +28,26 @@ class Explore:
     """The exploration rule of a logged rollout (monsoon_explore, include/monsoon.h): a heuristic decision of a side in
     `sides` ("first", "second", "both") at committed-step index k (k < until_step where until_step > 0) commits a
     uniformly drawn legal action instead of its arg-max with probability eps.  The draws are hash32(seed, match seed, k, .):
-    game_log.explore_draws recomputes them."""
+    game_log.explore_draws recomputes them.
+    temperature = a finite T > 0 selects the sampling rule instead (monsoon_sample, monsoon_rollout_sample): such a decision
+    commits an action drawn from the softmax over its scores, exp((score - best) / T) in 24-bit integer weights
+    (game_log.sample_weights, game_log.sample_rank); inv_temperature = 1.0 / T is what the device multiplies by.  Actions
+    tied for the best score share the probability equally.  temperature=None is the uniform rule, unchanged in every bit."""
     SIDES = {"first": 1, "second": 2, "both": 3}
 
-    def __init__(self, eps, seed, sides="both", until_step=0):
+    def __init__(self, eps, seed, sides="both", until_step=0, temperature=None):
         if not 0.0 <= eps <= 1.0:   # (a NaN fails it too)
             raise ValueError(f"Explore: eps must lie in [0, 1], got {eps!r}")
         if sides not in self.SIDES:
             raise ValueError(f"Explore: sides is one of {tuple(self.SIDES)}, got {sides!r}")
+        self.temperature = self.inv_temperature = None
+        if temperature is not None:
+            if not 0.0 < temperature < float("inf"):   # (a NaN fails it too)
+                raise ValueError(f"Explore: temperature must be finite and > 0, got {temperature!r}")
+            self.temperature = float(temperature)
+            self.inv_temperature = 1.0 / self.temperature
+            if not self.inv_temperature < float("inf"):   # (a subnormal T)
+                raise ValueError(f"Explore: 1 / temperature is not finite for {temperature!r}")
         self.eps, self.seed, self.sides, self.until_step = float(eps), int(seed) & 0xFFFFFFFF, sides, int(until_step)
         self.threshold = min(int(eps * 2**32), 0xFFFFFFFF)   # a decision explores iff draw0 < threshold
         self.side_bits = self.SIDES[sides]
@@ -42,6 +59,15 @@ class Explore:
     def c_struct(self):
         return _lib.Explore(self.seed, self.threshold, self.side_bits, self.until_step)
 
+    @property
+    def samples(self):
+        """True for the sampling rule (a temperature), False for the uniform one."""
+        return self.inv_temperature is not None
+
+    def c_sample(self):
+        """monsoon_sample of the sampling rule."""
+        return _lib.Sample(self.c_struct(), self.inv_temperature)
+
 
 class RolloutLog:
     """What a logged rollout played (monsoon_rollout_logged): entry k of row i is game i's k-th committed step.
@@ -51,24 +77,41 @@ class RolloutLog:
     A rollout with an Explore rule (monsoon_rollout_explore) adds greedy uint8[n][max_turns] (the decision's arg-max action:
     the teacher's label where `action` was explored; 255 for a bot step and behind), explored uint8[n][max_turns] (1 = the
     decision's draw said "explore") and taken_score float64[n][max_turns] (score of the committed action; NaN for a bot
-    step and behind); None otherwise."""
+    step and behind); None otherwise.
+    A rollout with a sampling rule (Explore(temperature=), monsoon_rollout_sample) adds to those weight_total
+    uint32[n][max_turns] (the sum of the decision's 24-bit softmax weights) and taken_weight uint32[n][max_turns] (the weight
+    of the committed action); both 0 for a bot step, a decision that did not sample, and behind; None otherwise."""
 
-    def __init__(self, action, score, n_legal, steps, greedy=None, explored=None, taken_score=None):
+    def __init__(self, action, score, n_legal, steps, greedy=None, explored=None, taken_score=None, weight_total=None, taken_weight=None):
         self.action, self.score, self.n_legal, self.steps = action, score, n_legal, steps
         self.greedy, self.explored, self.taken_score = greedy, explored, taken_score
+        self.weight_total, self.taken_weight = weight_total, taken_weight
 
     @classmethod
-    def empty(cls, n, max_turns, scores=True, n_legal=True, explore=False):
-        """n rows of padding; explore: with the three arrays of an exploring rollout."""
+    def empty(cls, n, max_turns, scores=True, n_legal=True, explore=False, sample=False):
+        """n rows of padding; explore: with the three arrays of an exploring rollout; sample: with those and the two of a
+        sampling one."""
+        explore = explore or sample
         return cls(np.full((n, max_turns), 255, dtype=np.uint8), np.full((n, max_turns), np.nan) if scores else None,
                    np.zeros((n, max_turns), dtype=np.int16) if n_legal else None, np.zeros(n, dtype=np.int32),
                    np.full((n, max_turns), 255, dtype=np.uint8) if explore else None,
-                   np.zeros((n, max_turns), dtype=np.uint8) if explore else None, np.full((n, max_turns), np.nan) if explore else None)
+                   np.zeros((n, max_turns), dtype=np.uint8) if explore else None, np.full((n, max_turns), np.nan) if explore else None,
+                   np.zeros((n, max_turns), dtype=np.uint32) if sample else None, np.zeros((n, max_turns), dtype=np.uint32) if sample else None)
+
+    def taken_prob(self):
+        """float64[n][max_turns]: taken_weight / weight_total, the probability the softmax gave the committed action GIVEN
+        that the decision sampled; NaN where weight_total == 0 (a bot step, a decision that did not sample, behind the last
+        step).  With eps < 1 the behaviour policy is the mixture include/monsoon.h spells out (monsoon_rollout_sample)."""
+        if self.weight_total is None or self.taken_weight is None:
+            raise ValueError("taken_prob needs the log of a rollout with a sampling rule (Explore(temperature=))")
+        out = np.full(self.weight_total.shape, np.nan)
+        np.divide(self.taken_weight, self.weight_total, out=out, where=self.weight_total != 0)
+        return out
 
     def put(self, rows, other):
         """Rows `rows` become the rows of `other` (a log of len(rows) games with the same arrays)."""
         self.action[rows], self.steps[rows] = other.action, other.steps
-        for name in ("score", "n_legal", "greedy", "explored", "taken_score"):
+        for name in ("score", "n_legal", "greedy", "explored", "taken_score", "weight_total", "taken_weight"):
             if getattr(self, name) is not None:
                 getattr(self, name)[rows] = getattr(other, name)
 
@@ -241,6 +284,22 @@ class BatchEngine:
         self._ck(self.lib.monsoon_debug_kat(self.h, kind, int(seed) & 0xFFFFFFFF, n, _ptr(inp), _ptr(out)), "monsoon_debug_kat")
         return out
 
+    def debug_sample_kat(self, scores, n_legal, best, inv_temperature, draw1):
+        """monsoon_debug_sample_kat: the device's sampler on m caller-given decisions -- scores float64[m][156] (row i's first
+        n_legal[i] entries are its legal list's scores), best float64[m], inv_temperature float64[m], draw1 uint32[m].
+        Returns (rank int32[m] (-1 where total == 0), total uint32[m], weight uint32[m]): what game_log.sample_weights /
+        sample_rank compute."""
+        scores = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1, 156)
+        m = len(scores)
+        n_legal, draw1 = np.ascontiguousarray(n_legal, dtype=np.int32), np.ascontiguousarray(draw1, dtype=np.uint32)
+        best, inv_t = np.ascontiguousarray(best, dtype=np.float64), np.ascontiguousarray(inv_temperature, dtype=np.float64)
+        if not (len(n_legal) == len(draw1) == len(best) == len(inv_t) == m):
+            raise ValueError("debug_sample_kat: one entry per row of every argument")
+        rank, total, weight = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint32)
+        self._ck(self.lib.monsoon_debug_sample_kat(self.h, m, _ptr(scores), _ptr(n_legal), _ptr(best), _ptr(inv_t), _ptr(draw1), _ptr(rank),
+                                                   _ptr(total), _ptr(weight)), "monsoon_debug_sample_kat")
+        return rank, total, weight
+
     def debug_raw(self, i):
         buf = np.zeros(4096, dtype=np.uint8)
         ln = ctypes.c_int32()
@@ -370,9 +429,11 @@ class BatchEngine:
         Returns (counts, results, steps, log), log a RolloutLog whose score / n_legal are None where not asked for.
         explore = an Explore: monsoon_rollout_explore, the same call whose heuristic decisions may commit a drawn legal
         action; the log also carries greedy, explored and taken_score, and the counts describe the games that were played --
-        they are not fitness."""
-        log = RolloutLog.empty(len(matches), max_turns, scores, n_legal, explore is not None)
-        entry = "monsoon_rollout_logged" if explore is None else "monsoon_rollout_explore"
+        they are not fitness.  An Explore with a temperature: monsoon_rollout_sample, whose decisions draw from the softmax
+        over their scores; the log carries weight_total and taken_weight too (RolloutLog.taken_prob)."""
+        sample = explore is not None and explore.samples
+        log = RolloutLog.empty(len(matches), max_turns, scores, n_legal, explore is not None, sample)
+        entry = "monsoon_rollout_logged" if explore is None else "monsoon_rollout_sample" if sample else "monsoon_rollout_explore"
         return self._rollout(entry, weights, matches, deck_pairs, max_turns, True, log, explore) + (log,)
 
     @staticmethod
@@ -400,10 +461,16 @@ class BatchEngine:
             c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
             extra = (ctypes.byref(c_log),)
             entry_bytes = 11   # a logged call's batches are cut by the log's budget too ...
-            if explore is not None:   # ... an exploring call's by the arrays it asks for (include/monsoon.h)
-                c_ex, c_xlog = explore.c_struct(), _lib.ExploreLog(_ptr(log.greedy), _ptr(log.explored), _ptr(log.taken_score))
-                extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog))
-                entry_bytes = explore_entry_bytes(log.score is not None, log.n_legal is not None)
+            if explore is not None:   # ... an exploring or sampling call's by the arrays it asks for (include/monsoon.h)
+                c_xlog = _lib.ExploreLog(_ptr(log.greedy), _ptr(log.explored), _ptr(log.taken_score))
+                if explore.samples:
+                    c_ex, c_slog = explore.c_sample(), _lib.SampleLog(_ptr(log.weight_total), _ptr(log.taken_weight))
+                    extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog), ctypes.byref(c_slog))
+                    entry_bytes = sample_entry_bytes(log.score is not None, log.n_legal is not None)
+                else:
+                    c_ex = explore.c_struct()
+                    extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog))
+                    entry_bytes = explore_entry_bytes(log.score is not None, log.n_legal is not None)
             batch = min(batch, max(1, LOG_BUDGET // (entry_bytes * max_turns)))
         self._ck(getattr(self.lib, entry)(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
                                           max_turns, _ptr(counts), _ptr(results), _ptr(steps), *extra), entry)

@@ -27,6 +27,43 @@ def explore_draws(explore, match_seeds, k, n_legal):
     return draw0 < np.uint32(explore.threshold), ((draw1.astype(np.uint64) * n_legal) >> np.uint64(32)).astype(np.int64)
 
 
+# c_k = the double nearest 1 / k!, k = 0 .. 10 (monsoon_amd/csrc/sample_weight.h)
+_INV_FACTORIAL = (1.0, 1.0, 1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880, 1.0 / 3628800)
+SAMPLE_ONE = 1 << 24   # the weight of a decision's arg-max and of every action tied with it
+
+
+def sample_weights(scores, best, inv_temperature):
+    """The weights of monsoon_rollout_sample (include/monsoon.h), the numpy statement of the device's arithmetic, bit for
+    bit: x = (scores - best) * inv_temperature, two operations each rounded once, then weight24(x) = floor(exp(x) * 2**24)
+    by range reduction, a degree-10 polynomial in Horner form, ldexp and floor -- plain *, +, - only, which numpy never
+    fuses.  scores, best, inv_temperature broadcast to any shape; returns uint32 of that shape, 0 where x is NaN, -inf or
+    < -32.  (x > 0 does not occur for a decision's scores against its best score.)"""
+    scores, best, inv_t = np.broadcast_arrays(np.asarray(scores, dtype=np.float64), np.asarray(best, dtype=np.float64),
+                                              np.asarray(inv_temperature, dtype=np.float64))
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (scores - best) * inv_t
+        live = x >= -32.0   # (False for a NaN)
+        x = np.where(live, x, 0.0)
+        n = np.floor(x * float.fromhex("0x1.71547652b82fep+0") + 0.5)
+        r = (x - n * float.fromhex("0x1.62e42feep-1")) - n * float.fromhex("0x1.a39ef35793c76p-33")
+        p = np.full(x.shape, _INV_FACTORIAL[10])
+        for k in range(9, -1, -1):
+            p = p * r + _INV_FACTORIAL[k]
+        w = np.floor(np.ldexp(p, n.astype(np.int32) + 24))
+    return np.where(live, w, 0.0).astype(np.uint32)
+
+
+def sample_rank(weights, draw1):
+    """j* of monsoon_rollout_sample over the weights of one decision's ascending legal list (uint32[n_legal]) and its
+    draw1: r = (draw1 * total) >> 32, the smallest j whose inclusive prefix sum exceeds r (so an action of weight 0 is never
+    taken, and r equal to a prefix goes to the next action).  -1 where the weights sum to 0."""
+    prefix = np.cumsum(np.asarray(weights, dtype=np.uint64))
+    total = int(prefix[-1]) if len(prefix) else 0
+    if total == 0:
+        return -1
+    return int(np.searchsorted(prefix, (int(draw1) * total) >> 32, side="right"))
+
+
 def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, explore=None):
     """A schedule played on the smallest record each game needs, with its log.  engine_for_tier(tier) is the engine of a
     record (0 standard, 1 extended, 2 large): anything with BatchEngine's rollout_logged and rollout_faults.  The rule is
@@ -35,9 +72,11 @@ def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, exp
     its rows -- the log's among them -- are replaced.  An engine is handed only the deck pairs its sub-schedule names.
     explore = an engine.Explore: every tier plays with that rule (the draws are keyed by the match's seed and the step, so a
     game played again on a larger record explores as it did on the smaller one) and the log carries greedy, explored and
-    taken_score; the counts then describe explored games, not fitness.
+    taken_score; the counts then describe explored games, not fitness.  A rule with a temperature (the sampling rule) goes
+    through the tiers the same way, and the log carries weight_total and taken_weight too.
     Returns (counts[n_rows][3], results, steps, faults, log)."""
-    log = RolloutLog.empty(len(matches), max_turns, explore=explore is not None)
+    log = RolloutLog.empty(len(matches), max_turns, explore=explore is not None,
+                           sample=explore is not None and getattr(explore, "samples", False))
     how = {} if explore is None else {"explore": explore}
 
     def play(t, sub, sub_pairs):
@@ -87,7 +126,8 @@ COLUMNS = {"obs": ("int32", (27, 5, 4)), "legal": ("uint8", (156,)), "obs_raises
 ROW_BYTES = {"obs": 2160, "legal": 156, "obs_raises": 1, "to_play": 1, "action": 1, "bot": 1, "game": 4, "step": 4, "state_hash": 8}
 # ... those gathered on the host from the arrays of an exploring rollout's log at the kept entries (no replay involved):
 # greedy is the teacher's label of a row whose action was explored, explored marks such rows
-LOG_COLUMNS = {"greedy": ("uint8", ()), "explored": ("uint8", ())}
+# ; weight_total and taken_weight are a sampling rollout's (the log's uint32 values, as int64 tensors)
+LOG_COLUMNS = {"greedy": ("uint8", ()), "explored": ("uint8", ()), "weight_total": ("int64", ()), "taken_weight": ("int64", ())}
 # ... and of monsoon_replay_after, "K" = max_after: the candidates the row's choice was made among, entry k the k-th legal
 # action in ascending order.  Naming one of them turns the look-ahead on; _CANDIDATE_BASE comes along, as action does.
 CANDIDATE_COLUMNS = {"n_legal": ("int32", ()), "chosen": ("int16", ()), "after_action": ("uint8", ("K",)), "after_status": ("uint8", ("K",)),
@@ -188,7 +228,8 @@ def _log_columns(log, names):
     want = [c for c in names if c in LOG_COLUMNS]
     missing = [c for c in want if getattr(log, c, None) is None]
     if missing:
-        raise ValueError(f"column(s) {missing} need the log of a rollout with an Explore rule (rollout_logged(..., explore=))")
+        raise ValueError(f"column(s) {missing} need the log of a rollout with an Explore rule (rollout_logged(..., explore=); "
+                         "weight_total / taken_weight: one with a temperature)")
     return want
 
 
@@ -203,7 +244,7 @@ def _gather_log(tensors, log, want, steps, keep, a=0, b=None):
     if keep is not None:
         sel &= np.asarray(keep)[:, :sel.shape[1]] != 0
     for c in want:
-        vals = np.ascontiguousarray(getattr(log, c)[a:b][sel])   # (boolean indexing is row-major: the documented row order)
+        vals = np.ascontiguousarray(getattr(log, c)[a:b][sel], dtype=LOG_COLUMNS[c][0])   # (boolean indexing is row-major: the documented row order)
         tensors[c][:len(vals)] = torch.as_tensor(vals, device=tensors[c].device)
 
 
