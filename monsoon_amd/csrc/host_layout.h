@@ -94,68 +94,40 @@ inline GaOffspring ga_offspring(size_t mu, size_t dim, size_t lambda, size_t mt_
   return l;
 }
 
-// d_log, the device log of one rollout batch: `entries` = games x max_turns per array; an array the caller does not ask
-// for takes no room (its offset is NONE)
+// d_log, the device log of one batch of a logged rollout (monsoon_rollout_logged / _explore / _sample): one array of
+// `entries` = games x max_turns elements per column the caller asks for, in the order of this table -- by falling element
+// size, so every array is aligned to its element whatever the entry count.  `fill` is the byte the array is set to before
+// the launch: what an entry behind a game's last step reads, and a bot step in the columns the bot does not write.
+enum LogColumn { LOG_SCORE, LOG_TAKEN_SCORE, LOG_WEIGHT_TOTAL, LOG_TAKEN_WEIGHT, LOG_N_LEGAL, LOG_ACTION, LOG_GREEDY, LOG_EXPLORED, LOG_COLUMNS };
+struct LogColumnInfo { size_t bytes; int fill; };
+constexpr LogColumnInfo LOG_COLUMN[LOG_COLUMNS] = {
+    {8, 0xFF},   // score         f64  NaN (all ones)
+    {8, 0xFF},   // taken_score   f64  NaN
+    {4, 0},      // weight_total  u32
+    {4, 0},      // taken_weight  u32
+    {2, 0},      // n_legal       i16
+    {1, 0xFF},   // action        u8   255; always present
+    {1, 0xFF},   // greedy        u8   255
+    {1, 0},      // explored      u8
+};
+constexpr unsigned log_bit(LogColumn c) { return 1u << c; }
+// what one entry takes: the columns of `mask` and action (1 .. 29 bytes), the figure a call's batch cap is cut by
+constexpr size_t log_entry_bytes(unsigned mask) {
+  size_t bytes = 0;
+  for (int c = 0; c < LOG_COLUMNS; c++)
+    if ((mask | log_bit(LOG_ACTION)) >> c & 1u) bytes += LOG_COLUMN[c].bytes;
+  return bytes;
+}
 constexpr size_t NONE = ~(size_t)0;
-struct RolloutLog { size_t score, n_legal, action, total; };                 // f64 | i16 | u8, [entries] each
-inline RolloutLog rollout_log(size_t entries, bool score, bool n_legal) {
-  RolloutLog l;
-  l.score = score ? 0 : NONE;
-  const size_t after_score = score ? entries * 8 : 0;
-  l.n_legal = n_legal ? after_score : NONE;
-  l.action = after_score + (n_legal ? entries * 2 : 0);
-  l.total = l.action + entries;
-  return l;
-}
-
-// d_log of monsoon_rollout_explore: the same three arrays, then the three the exploring kernel adds, the 8-byte ones
-// first; an array the caller does not ask for takes no room.  explore_entry_bytes is what one entry takes (1 .. 21), the
-// figure the call's batch cap is cut by.
-struct ExploreLog { size_t score, taken_score, n_legal, action, greedy, explored, total; };   // f64 | f64 | i16 | u8 | u8 | u8, [entries] each
-constexpr size_t explore_entry_bytes(bool score, bool n_legal, bool greedy, bool explored, bool taken_score) {
-  return 1 + (score ? 8 : 0) + (n_legal ? 2 : 0) + (greedy ? 1 : 0) + (explored ? 1 : 0) + (taken_score ? 8 : 0);
-}
-inline ExploreLog explore_log(size_t entries, bool score, bool n_legal, bool greedy, bool explored, bool taken_score) {
-  ExploreLog l;
-  size_t at = 0;
-  const auto field = [&](bool on, size_t bytes) {
-    const size_t off = on ? at : NONE;
-    if (on) at += entries * bytes;
-    return off;
-  };
-  l.score = field(score, 8);
-  l.taken_score = field(taken_score, 8);
-  l.n_legal = field(n_legal, 2);
-  l.action = field(true, 1);
-  l.greedy = field(greedy, 1);
-  l.explored = field(explored, 1);
-  l.total = at;
-  return l;
-}
-// d_log of monsoon_rollout_sample: the exploring call's arrays and the two the sampling kernel adds, by falling element
-// size; an array the caller does not ask for takes no room.  sample_entry_bytes is what one entry takes (1 .. 29).
-struct SampleLog { size_t score, taken_score, weight_total, taken_weight, n_legal, action, greedy, explored, total; };   // f64 | f64 | u32 | u32 | i16 | u8 | u8 | u8
-constexpr size_t sample_entry_bytes(bool score, bool n_legal, bool greedy, bool explored, bool taken_score, bool weight_total, bool taken_weight) {
-  return explore_entry_bytes(score, n_legal, greedy, explored, taken_score) + (weight_total ? 4 : 0) + (taken_weight ? 4 : 0);
-}
-inline SampleLog sample_log(size_t entries, bool score, bool n_legal, bool greedy, bool explored, bool taken_score, bool weight_total,
-                            bool taken_weight) {
-  SampleLog l;
-  size_t at = 0;
-  const auto field = [&](bool on, size_t bytes) {
-    const size_t off = on ? at : NONE;
-    if (on) at += entries * bytes;
-    return off;
-  };
-  l.score = field(score, 8);
-  l.taken_score = field(taken_score, 8);
-  l.weight_total = field(weight_total, 4);
-  l.taken_weight = field(taken_weight, 4);
-  l.n_legal = field(n_legal, 2);
-  l.action = field(true, 1);
-  l.greedy = field(greedy, 1);
-  l.explored = field(explored, 1);
-  l.total = at;
+struct Log { size_t at[LOG_COLUMNS], total; };   // a column that is not asked for takes no room: its offset is NONE
+inline Log log_layout(size_t entries, unsigned mask) {
+  Log l;
+  l.total = 0;
+  for (int c = 0; c < LOG_COLUMNS; c++) {
+    const bool on = (mask | log_bit(LOG_ACTION)) >> c & 1u;
+    l.at[c] = on ? l.total : NONE;
+    if (on) l.total += entries * LOG_COLUMN[c].bytes;
+  }
   return l;
 }
 // games per batch of a logged call: as many as `budget` bytes of device log hold, one at least, max_games at most

@@ -3,9 +3,10 @@
 // them (play_game), the pop loop of the persistent kernels (pop_games), the hot kernel k_play as a template over
 // {candidate lanes per game U, waves per SIMD W}, and the launch-table base and default variant every kernel file uses.
 // Each instantiation is a full compilation of the rules core, so every variant lives in a translation unit of its own
-// (variant.hip, built in parallel by the Makefile); vs_expert.hip, play_log.hip, play_explore.hip, play_sample.hip, env_opp.hip, env_opp_explore.hip and env_after.hip hold one
-// further instantiation each, replay_log.hip one of the rules core without the decision loop; monsoon_hip.hip holds the
-// API kernels and the host side.
+// (variant.hip, built in parallel by the Makefile); vs_expert.hip, the three logging kernels' play_log.hip, play_explore.hip
+// and play_sample.hip (one launcher type, LoggedOps, and one argument struct on the host side, PlayLogged), env_opp.hip,
+// env_opp_explore.hip and env_after.hip hold one further instantiation each, replay_log.hip and replay_after.hip one of the
+// rules core without the decision loop; monsoon_hip.hip holds the API kernels and the host side.
 //
 // Execution model
 //   * Hot kernel k_play<U,W>: ONE WAVEFRONT PER GAME at a time (a persistent grid of resident wavefronts, each popping
@@ -962,28 +963,25 @@ constexpr int DEFAULT_U = kVariants[0][0], DEFAULT_W = kVariants[0][1];
 // k_play_vs<DEFAULT_U, DEFAULT_W> (vs_expert.hip): the rollout kernel that knows the scripted bot.
 const VariantOps* monsoon_vs_expert_ops();
 
-// k_play_log<DEFAULT_U, DEFAULT_W> (play_log.hip): k_play_vs that writes every committed step into a PlayLog.
-struct LogOps : KernelOps {
-  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
-               PlayLog lg);   // never split: the whole batch, the first pair of counter sets
+// The three logging kernels, one launcher type: k_play_log<DEFAULT_U, DEFAULT_W> (play_log.hip) is k_play_vs that writes
+// every committed step into a PlayLog, k_play_explore (play_explore.hip) is k_play_log whose decisions may explore
+// (PlayExplore), k_play_sample (play_sample.hip) is k_play_log whose decisions may sample (PlayExplore's rule, PlaySample).
+// The host hands every one of them the same PlayLogged; each file's stub passes its kernel the members it takes.
+struct PlayLogged {
+  PlayLog lg;
+  PlayExplore ex;
+  PlaySample sp;
 };
-const LogOps* monsoon_play_log_ops();
+struct LoggedOps : KernelOps {
+  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+               const PlayLogged& a);   // never split: the whole batch, the first pair of counter sets
+};
+const LoggedOps* monsoon_play_log_ops();
+const LoggedOps* monsoon_play_explore_ops();
+const LoggedOps* monsoon_play_sample_ops();
 
-// k_play_explore<DEFAULT_U, DEFAULT_W> (play_explore.hip): k_play_log whose decisions may explore (PlayExplore).
-struct ExploreOps : KernelOps {
-  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
-               PlayLog lg, PlayExplore ex);   // never split, like LogOps::play
-};
-const ExploreOps* monsoon_play_explore_ops();
-
-// k_play_sample<DEFAULT_U, DEFAULT_W> (play_sample.hip): k_play_log whose decisions may sample (PlayExplore's rule, PlaySample);
-// kat is k_sample_kat, sample_pick on caller-given rows (monsoon_debug_sample_kat), one wavefront per row.
-struct SampleOps : KernelOps {
-  void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
-               PlayLog lg, PlayExplore ex, PlaySample sp);   // never split, like LogOps::play
-  void (*kat)(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,
-              const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total, uint32_t* out_weight);
-};
-const SampleOps* monsoon_play_sample_ops();
+// k_sample_kat (play_sample.hip): sample_pick on caller-given rows (monsoon_debug_sample_kat), one wavefront per row.
+void monsoon_sample_kat_launch(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,
+                               const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total, uint32_t* out_weight);
 
 }  // namespace msbk

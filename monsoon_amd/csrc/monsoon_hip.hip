@@ -723,7 +723,7 @@ struct monsoon {
   bool own_stream = false;
   int32_t* d_steps = nullptr;
   size_t steps_cap = 0;
-  // monsoon_rollout_logged: the log of one batch (layout::rollout_log), grown on demand
+  // monsoon_rollout_logged / _explore / _sample: the log of one batch (layout::log_layout), grown on demand
   uint8_t* d_log = nullptr;
   size_t log_cap = 0;   // bytes
   // monsoon_replay_logged_dev: one batch's log, keep mask, row bases and outcome (layout::replay), grown on demand
@@ -1486,7 +1486,7 @@ int monsoon_debug_sample_kat(monsoon_t* h, int32_t m, const double* scores, cons
   HIP_TRY(h, hipMemcpy(d_inv, inv_temperature, rows * 8, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(d_n, n_legal, rows * 4, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(d_draw, draw1, rows * 4, hipMemcpyHostToDevice));
-  monsoon_play_sample_ops()->kat(h->stream, m, d_scores, d_n, d_best, d_inv, d_draw, d_rank, d_total, d_weight);
+  monsoon_sample_kat_launch(h->stream, m, d_scores, d_n, d_best, d_inv, d_draw, d_rank, d_total, d_weight);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out_rank, d_rank, rows * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipMemcpyAsync(out_total, d_total, rows * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1655,24 +1655,24 @@ struct PlayCall {
   bool write_scores = false;     // every candidate's score goes to b.scores
   bool timed = false;            // an event pair of the handle round the call (kernel_ms)
   bool split = false;            // PLAY only (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below
-  const PlayLog* log = nullptr;  // PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE (monsoon_rollout_logged / _explore / _sample): where every committed step is written
-  const PlayExplore* explore = nullptr;   // PLAY_EXPLORE and PLAY_SAMPLE: the exploration rule, the batch's match seeds, the further log arrays
-  const PlaySample* sample = nullptr;     // PLAY_SAMPLE only: the inverse temperature and the two weight arrays
+  const PlayLogged* logged = nullptr;   // PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE (monsoon_rollout_logged / _explore / _sample): where every
+                                        // committed step is written, the exploration rule and the batch's match seeds, the inverse temperature
 };
+// The launcher of a logging kind (kernels.h LoggedOps), null for PLAY and PLAY_VS.
+static const LoggedOps* logged_ops(PlayKind kind) {
+  return kind == PLAY_LOG ? monsoon_play_log_ops() : kind == PLAY_EXPLORE ? monsoon_play_explore_ops() : kind == PLAY_SAMPLE ? monsoon_play_sample_ops() : nullptr;
+}
 
 // `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE are never split.
 static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
-  const bool vs = call.kind == PLAY_VS, log = call.kind == PLAY_LOG, explore = call.kind == PLAY_EXPLORE, sample = call.kind == PLAY_SAMPLE;
   bool timed = call.timed;
   if (h->bot_rows && call.kind == PLAY) {   // (a weight row of -1 must never reach k_play)
     h->err = "the loaded games were scheduled against the scripted bot: assign players before deciding";
     return MONSOON_ERR_STATE;
   }
-  const VariantOps* vp = vs ? monsoon_vs_expert_ops() : h->var;
-  const KernelOps* v = sample    ? static_cast<const KernelOps*>(monsoon_play_sample_ops())
-                       : explore ? static_cast<const KernelOps*>(monsoon_play_explore_ops())
-                       : log     ? static_cast<const KernelOps*>(monsoon_play_log_ops())
-                                 : vp;
+  const VariantOps* vp = call.kind == PLAY_VS ? monsoon_vs_expert_ops() : h->var;
+  const LoggedOps* lp = logged_ops(call.kind);
+  const KernelOps* v = lp ? static_cast<const KernelOps*>(lp) : vp;
   const int lds = v->lds_bytes + g_lds_pad;
   int& grid_waves = h->grid_waves[call.kind];
   if (!grid_waves) {   // resident wavefronts of the kernel (queried once)
@@ -1734,13 +1734,8 @@ static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
   }
   for (int s = 0; s < parts; s++) {
     const int g0 = (int)((long long)n * s / parts), g1 = (int)((long long)n * (s + 1) / parts);
-    if (sample)   // (parts == 1)
-      monsoon_play_sample_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log, *call.explore,
-                                      *call.sample);
-    else if (explore)   // (parts == 1)
-      monsoon_play_explore_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log, *call.explore);
-    else if (log)   // (parts == 1)
-      monsoon_play_log_ops()->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.log);
+    if (lp)   // (parts == 1)
+      lp->play(grid, lds, h->stream, h->b, n, call.max_turns, call.rounds, pers, h->parity[0], *call.logged);
     else
       vp->play(grid, lds, s ? h->split_stream[s] : h->stream, h->b, g1 - g0, call.max_turns, call.rounds, call.write_scores, pers, h->parity[s], g0, s);
     // Only a persistent launch consumes its counter set and clears the other one: a non-persistent launch in between
@@ -1829,85 +1824,65 @@ int monsoon_decide(monsoon_t* h, const double* weights, uint8_t* out_action, dou
   return MONSOON_OK;
 }
 
-// A logged call's batch is cut so that its device log stays within LOG_BUDGET whatever max_turns is: 11 bytes per entry
-// (action + score + legal count), max_turns entries per game; an exploring call's by the columns it asks for, 1 .. 21 bytes
-// (layout::explore_entry_bytes).
+// A logged call's batch is cut so that its device log stays within LOG_BUDGET whatever max_turns is (layout::log_batch_cap),
+// max_turns entries per game.
 constexpr size_t LOG_BUDGET = (size_t)256 << 20;
 
-// What an exploring call adds to a logged one: the caller's further host arrays and the kernel's argument (device
-// pointers into d_log; match_seed is set per batch).
-struct ExploreCall {
-  const monsoon_explore_log* host;
-  PlayExplore dev;
-  // a sampling call (monsoon_rollout_sample) on top: its further host arrays and its kernel's own argument
-  bool sample = false;
-  const monsoon_sample_log* shost = nullptr;
-  PlaySample sdev = {};
+// The log of one logged call (monsoon_rollout_logged / _explore / _sample): per column of layout::LOG_COLUMN the caller's
+// host array (null: not asked for) and where a batch's array lies in d_log, and the kernel's arguments, which point there.
+struct LogCall {
+  PlayKind kind;
+  struct {
+    void* host;
+    uint8_t* dev;
+  } col[layout::LOG_COLUMNS];
+  PlayLogged args;   // (ex.match_seed is set per batch)
 };
 
 // Matches [base, base + n) of a rollout: load them, one launch plays the whole batch to the end, collect.  A batch without
 // a bot is k_play's, counted by k_collect, as ever.
 static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max_turns, const uint32_t* seeds, const uint8_t* decks, const int32_t* p1,
-                         const int32_t* p2, const monsoon_rollout_log* log, const PlayLog& dlog, const ExploreCall* xc) {
+                         const int32_t* p2, const LogCall* lc) {
   int rc = monsoon_reset(h, n, seeds, decks, nullptr);
   if (!rc) rc = assign_players(h, p1, p2, base, min_row);
   if (rc) return rc;
   const bool vs = h->bot_rows;
   const size_t cnt = (size_t)n * max_turns, row = (size_t)base * max_turns;   // log entries of the batch, and where they go
-  if (log) {   // the padding behind a game's last step: action 255, score NaN (all ones), legal count 0
-    HIP_TRY(h, hipMemsetAsync(dlog.action, 0xFF, cnt, h->stream));
-    if (dlog.score) HIP_TRY(h, hipMemsetAsync(dlog.score, 0xFF, cnt * 8, h->stream));
-    if (dlog.n_legal) HIP_TRY(h, hipMemsetAsync(dlog.n_legal, 0, cnt * 2, h->stream));
-  }
-  PlayExplore dex;
-  if (xc) {   // likewise: greedy 255, explored 0, taken_score NaN -- also what a bot step reads, which writes none of them
-    dex = xc->dev;
-    dex.match_seed = h->d_seeds;   // (monsoon_reset left the batch's seeds there)
-    if (dex.greedy) HIP_TRY(h, hipMemsetAsync(dex.greedy, 0xFF, cnt, h->stream));
-    if (dex.explored) HIP_TRY(h, hipMemsetAsync(dex.explored, 0, cnt, h->stream));
-    if (dex.taken_score) HIP_TRY(h, hipMemsetAsync(dex.taken_score, 0xFF, cnt * 8, h->stream));
-    if (xc->sdev.weight_total) HIP_TRY(h, hipMemsetAsync(xc->sdev.weight_total, 0, cnt * 4, h->stream));   // (both weights 0)
-    if (xc->sdev.taken_weight) HIP_TRY(h, hipMemsetAsync(xc->sdev.taken_weight, 0, cnt * 4, h->stream));
+  PlayLogged args;
+  if (lc) {   // the padding behind a game's last step, and what a bot step reads in the columns it does not write
+    args = lc->args;
+    args.ex.match_seed = h->d_seeds;   // (monsoon_reset left the batch's seeds there)
+    for (int c = 0; c < layout::LOG_COLUMNS; c++)
+      if (lc->col[c].host) HIP_TRY(h, hipMemsetAsync(lc->col[c].dev, layout::LOG_COLUMN[c].fill, cnt * layout::LOG_COLUMN[c].bytes, h->stream));
   }
   PlayCall call;
-  call.kind = xc && xc->sample ? PLAY_SAMPLE : xc ? PLAY_EXPLORE : log ? PLAY_LOG : vs ? PLAY_VS : PLAY;
+  call.kind = lc ? lc->kind : vs ? PLAY_VS : PLAY;
   call.max_turns = max_turns;
   call.rounds = max_turns + 1;
   call.timed = true;
-  call.log = log ? &dlog : nullptr;
-  call.explore = xc ? &dex : nullptr;
-  call.sample = xc && xc->sample ? &xc->sdev : nullptr;
+  call.logged = lc ? &args : nullptr;
   rc = launch_play(h, n, call);
   if (rc) return rc;
   hipLaunchKernelGGL(vs ? k_collect_vs : k_collect, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->b, n, h->d_counts, h->d_results,
                      h->d_steps, (uint8_t*)h->d_results + layout::results(h->results_cap).fault);
   HIP_TRY(h, hipGetLastError());
-  if (log) {
-    HIP_TRY(h, hipMemcpyAsync(log->action + row, dlog.action, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (dlog.score) HIP_TRY(h, hipMemcpyAsync(log->score + row, dlog.score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
-    if (dlog.n_legal) HIP_TRY(h, hipMemcpyAsync(log->n_legal + row, dlog.n_legal, cnt * 2, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (xc) {
-    if (dex.greedy) HIP_TRY(h, hipMemcpyAsync(xc->host->greedy + row, dex.greedy, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (dex.explored) HIP_TRY(h, hipMemcpyAsync(xc->host->explored + row, dex.explored, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (dex.taken_score) HIP_TRY(h, hipMemcpyAsync(xc->host->taken_score + row, dex.taken_score, cnt * 8, hipMemcpyDeviceToHost, h->stream));
-    if (xc->sdev.weight_total)
-      HIP_TRY(h, hipMemcpyAsync(xc->shost->weight_total + row, xc->sdev.weight_total, cnt * 4, hipMemcpyDeviceToHost, h->stream));
-    if (xc->sdev.taken_weight)
-      HIP_TRY(h, hipMemcpyAsync(xc->shost->taken_weight + row, xc->sdev.taken_weight, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+  for (int c = 0; lc && c < layout::LOG_COLUMNS; c++) {
+    const size_t bytes = layout::LOG_COLUMN[c].bytes;
+    if (lc->col[c].host)
+      HIP_TRY(h, hipMemcpyAsync((uint8_t*)lc->col[c].host + row * bytes, lc->col[c].dev, cnt * bytes, hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return drain_timing(h);
 }
 
-// monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and
-// monsoon_rollout_logged (log non-null: the latter, played by k_play_log, every batch's log copied to row `base` of *log);
-// monsoon_rollout_explore is the logged call with ex non-null (played by k_play_explore, xlog's arrays copied likewise),
-// monsoon_rollout_sample that call with sm non-null too (ex = &sm->rule; played by k_play_sample, slog's arrays likewise)
+// monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and the
+// logged calls (log non-null: the latter, played by the kernel of `kind`, every batch's log copied to row `base` of the
+// caller's arrays): PLAY_LOG is monsoon_rollout_logged, PLAY_EXPLORE monsoon_rollout_explore (rule->rule is the exploration
+// rule, xlog's arrays are logged too), PLAY_SAMPLE monsoon_rollout_sample (all of *rule, slog's arrays too)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                         int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
-                        int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr, const monsoon_explore* ex = nullptr,
-                        const monsoon_explore_log* xlog = nullptr, const monsoon_sample* sm = nullptr, const monsoon_sample_log* slog = nullptr) {
+                        int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr, PlayKind kind = PLAY,
+                        const monsoon_sample* rule = nullptr, const monsoon_explore_log* xlog = nullptr, const monsoon_sample_log* slog = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
@@ -1934,47 +1909,33 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
   HIP_TRY(h, hipMemsetAsync(h->d_counts, 0, (size_t)n_individuals * 12, h->stream));
   h->rollout_matches = 0;
   int cap = h->cfg.max_games;
-  PlayLog dlog = {nullptr, nullptr, nullptr, max_turns};
-  ExploreCall xc = {xlog, PlayExplore{}};
-  if (sm) {   // (ex == &sm->rule)
-    const bool gr = xlog && xlog->greedy, xp = xlog && xlog->explored, ts = xlog && xlog->taken_score;
-    const bool wt = slog && slog->weight_total, tw = slog && slog->taken_weight;
-    cap = (int)layout::log_batch_cap((size_t)cap, LOG_BUDGET, layout::sample_entry_bytes(log->score, log->n_legal, gr, xp, ts, wt, tw), (size_t)max_turns);
-    const layout::SampleLog l = layout::sample_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal, gr, xp, ts, wt, tw);
+  LogCall lc = {};
+  if (log) {
+    using namespace layout;
+    lc.kind = kind;
+    lc.col[LOG_ACTION].host = log->action, lc.col[LOG_SCORE].host = log->score, lc.col[LOG_N_LEGAL].host = log->n_legal;
+    if (kind != PLAY_LOG && xlog)
+      lc.col[LOG_GREEDY].host = xlog->greedy, lc.col[LOG_EXPLORED].host = xlog->explored, lc.col[LOG_TAKEN_SCORE].host = xlog->taken_score;
+    if (kind == PLAY_SAMPLE && slog) lc.col[LOG_WEIGHT_TOTAL].host = slog->weight_total, lc.col[LOG_TAKEN_WEIGHT].host = slog->taken_weight;
+    unsigned mask = 0;
+    for (int c = 0; c < LOG_COLUMNS; c++)
+      if (lc.col[c].host) mask |= log_bit((LogColumn)c);
+    // The batch cap (include/monsoon.h): the plain logged call is cut by its three columns' 11 bytes per entry whatever it
+    // asks for, an exploring or sampling call by the columns it asks for.
+    const unsigned cut_by = kind == PLAY_LOG ? log_bit(LOG_ACTION) | log_bit(LOG_SCORE) | log_bit(LOG_N_LEGAL) : mask;
+    cap = (int)log_batch_cap((size_t)cap, LOG_BUDGET, log_entry_bytes(cut_by), (size_t)max_turns);
+    const Log l = log_layout((size_t)std::min(cap, n_matches) * max_turns, mask);
     HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
-    // the kernel parks every decision's scores in the game's row of the score table (monsoon_decide's, allocated on first use)
-    if (!h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
-    if (log->score) dlog.score = (double*)(h->d_log + l.score);
-    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
-    dlog.action = h->d_log + l.action;
-    xc.dev.seed = ex->seed, xc.dev.threshold = ex->threshold, xc.dev.sides = ex->sides, xc.dev.until_step = ex->until_step;
-    if (gr) xc.dev.greedy = h->d_log + l.greedy;
-    if (xp) xc.dev.explored = h->d_log + l.explored;
-    if (ts) xc.dev.taken_score = (double*)(h->d_log + l.taken_score);
-    xc.sample = true;
-    xc.shost = slog;
-    xc.sdev.inv_temperature = sm->inv_temperature;
-    if (wt) xc.sdev.weight_total = (uint32_t*)(h->d_log + l.weight_total);
-    if (tw) xc.sdev.taken_weight = (uint32_t*)(h->d_log + l.taken_weight);
-  } else if (ex) {
-    const bool gr = xlog && xlog->greedy, xp = xlog && xlog->explored, ts = xlog && xlog->taken_score;
-    cap = (int)layout::log_batch_cap((size_t)cap, LOG_BUDGET, layout::explore_entry_bytes(log->score, log->n_legal, gr, xp, ts), (size_t)max_turns);
-    const layout::ExploreLog l = layout::explore_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal, gr, xp, ts);
-    HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
-    if (log->score) dlog.score = (double*)(h->d_log + l.score);
-    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
-    dlog.action = h->d_log + l.action;
-    xc.dev.seed = ex->seed, xc.dev.threshold = ex->threshold, xc.dev.sides = ex->sides, xc.dev.until_step = ex->until_step;
-    if (gr) xc.dev.greedy = h->d_log + l.greedy;
-    if (xp) xc.dev.explored = h->d_log + l.explored;
-    if (ts) xc.dev.taken_score = (double*)(h->d_log + l.taken_score);
-  } else if (log) {
-    cap = (int)std::min((size_t)cap, std::max((size_t)1, LOG_BUDGET / ((size_t)11 * max_turns)));
-    const layout::RolloutLog l = layout::rollout_log((size_t)std::min(cap, n_matches) * max_turns, log->score, log->n_legal);
-    HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
-    if (log->score) dlog.score = (double*)(h->d_log + l.score);
-    if (log->n_legal) dlog.n_legal = (int16_t*)(h->d_log + l.n_legal);
-    dlog.action = h->d_log + l.action;
+    // a sampling kernel parks every decision's scores in the game's row of the score table (monsoon_decide's, allocated on first use)
+    if (kind == PLAY_SAMPLE && !h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
+    for (int c = 0; c < LOG_COLUMNS; c++) lc.col[c].dev = lc.col[c].host ? h->d_log + l.at[c] : nullptr;
+    const auto dev = [&](LogColumn c) { return lc.col[c].dev; };
+    lc.args.lg = {dev(LOG_ACTION), (double*)dev(LOG_SCORE), (int16_t*)dev(LOG_N_LEGAL), max_turns};
+    if (rule) {
+      const monsoon_explore& ex = rule->rule;
+      lc.args.ex = {ex.seed, ex.threshold, ex.sides, ex.until_step, nullptr, dev(LOG_GREEDY), dev(LOG_EXPLORED), (double*)dev(LOG_TAKEN_SCORE)};
+      lc.args.sp = {rule->inv_temperature, (uint32_t*)dev(LOG_WEIGHT_TOTAL), (uint32_t*)dev(LOG_TAKEN_WEIGHT)};
+    }
   }
   std::vector<uint32_t> seeds;
   std::vector<uint8_t> decks;
@@ -1992,7 +1953,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
       p1[i] = mm.p1;
       p2[i] = mm.p2;
     }
-    rc = rollout_batch(h, base, n, min_row, max_turns, seeds.data(), decks.data(), p1.data(), p2.data(), log, dlog, ex ? &xc : nullptr);
+    rc = rollout_batch(h, base, n, min_row, max_turns, seeds.data(), decks.data(), p1.data(), p2.data(), log ? &lc : nullptr);
     if (rc) return rc;
   }
   std::vector<int32_t> counts((size_t)n_individuals * 3);
@@ -2018,47 +1979,49 @@ int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_ind
                       max_turns, out_counts, out_results, out_steps);
 }
 
+// What the three logged entry points share: the log that must be there, the rule's checks, and which kernel plays.  A rule
+// that never fires (none, or threshold 0) still goes through the entry's kernel where one of xlog's or slog's arrays is
+// asked for (the kernel fills them: greedy = action, taken_score = score on decisions, both weights 0); without any the
+// call is the logged call itself, batch cap included.
+static int rollout_logged_impl(monsoon_t* h, const char* who, PlayKind kind, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                               int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
+                               int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_sample* sm,
+                               const monsoon_explore_log* xlog, const monsoon_sample_log* slog) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (!log || !log->action) return bad_arg(h, who, "log and log->action are required");
+  if (sm && (sm->rule.sides & ~3u)) return bad_arg(h, who, "sides holds a bit above bit 1");
+  if (sm && !(sm->inv_temperature > 0.0 && sm->inv_temperature < INFINITY))   // (a NaN fails the first test)
+    return bad_arg(h, who, "inv_temperature must be finite and > 0");
+  static const monsoon_sample never = {{0u, 0u, 0u, 0}, 1.0};
+  const bool wants = (xlog && (xlog->greedy || xlog->explored || xlog->taken_score)) || (slog && (slog->weight_total || slog->taken_weight));
+  const monsoon_sample* rule = (sm && sm->rule.threshold) ? sm : wants ? &never : nullptr;
+  return rollout_impl(h, who, MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns, out_counts,
+                      out_results, out_steps, log, rule ? kind : PLAY_LOG, rule, xlog, slog);
+}
+
 int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
                            const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
                            int32_t* out_steps, const monsoon_rollout_log* log) {
-  if (!h) return MONSOON_ERR_ARG;
-  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_logged", "log and log->action are required");
-  return rollout_impl(h, "monsoon_rollout_logged", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
-                      max_turns, out_counts, out_results, out_steps, log);
+  return rollout_logged_impl(h, "monsoon_rollout_logged", PLAY_LOG, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns,
+                             out_counts, out_results, out_steps, log, nullptr, nullptr, nullptr);
 }
 
-// monsoon_rollout_logged's call with an exploration rule.  A rule that never explores still goes through k_play_explore
-// where one of xlog's arrays is asked for (the kernel fills them: greedy = action, taken_score = score on decisions);
-// without any it is the logged call itself.
+// monsoon_rollout_logged's call with an exploration rule (a sampling rule whose temperature nobody reads).
 int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
                             const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
                             int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_explore* ex, const monsoon_explore_log* xlog) {
-  if (!h) return MONSOON_ERR_ARG;
-  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_explore", "log and log->action are required");
-  if (ex && (ex->sides & ~3u)) return bad_arg(h, "monsoon_rollout_explore", "sides holds a bit above bit 1");
-  static const monsoon_explore never = {0u, 0u, 0u, 0};
-  const bool wants = xlog && (xlog->greedy || xlog->explored || xlog->taken_score);
-  const monsoon_explore* rule = (ex && ex->threshold) ? ex : wants ? &never : nullptr;
-  return rollout_impl(h, "monsoon_rollout_explore", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
-                      max_turns, out_counts, out_results, out_steps, log, rule, xlog);
+  const monsoon_sample sm = {ex ? *ex : monsoon_explore{}, 1.0};
+  return rollout_logged_impl(h, "monsoon_rollout_explore", PLAY_EXPLORE, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns,
+                             out_counts, out_results, out_steps, log, ex ? &sm : nullptr, xlog, nullptr);
 }
 
-// monsoon_rollout_explore's call with a sampling rule.  As there, a rule that never samples still goes through the kernel
-// where one of xlog's or slog's arrays is asked for (it fills them); without any it is the logged call itself.
+// monsoon_rollout_explore's call with a sampling rule.
 int monsoon_rollout_sample(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
                            const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
                            int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_sample* sm, const monsoon_explore_log* xlog,
                            const monsoon_sample_log* slog) {
-  if (!h) return MONSOON_ERR_ARG;
-  if (!log || !log->action) return bad_arg(h, "monsoon_rollout_sample", "log and log->action are required");
-  if (sm && (sm->rule.sides & ~3u)) return bad_arg(h, "monsoon_rollout_sample", "sides holds a bit above bit 1");
-  if (sm && !(sm->inv_temperature > 0.0 && sm->inv_temperature < INFINITY))   // (a NaN fails the first test)
-    return bad_arg(h, "monsoon_rollout_sample", "inv_temperature must be finite and > 0");
-  static const monsoon_sample never = {{0u, 0u, 0u, 0}, 1.0};
-  const bool wants = (xlog && (xlog->greedy || xlog->explored || xlog->taken_score)) || (slog && (slog->weight_total || slog->taken_weight));
-  const monsoon_sample* rule = (sm && sm->rule.threshold) ? sm : wants ? &never : nullptr;
-  return rollout_impl(h, "monsoon_rollout_sample", MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks,
-                      max_turns, out_counts, out_results, out_steps, log, rule ? &rule->rule : nullptr, xlog, rule, slog);
+  return rollout_logged_impl(h, "monsoon_rollout_sample", PLAY_SAMPLE, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns,
+                             out_counts, out_results, out_steps, log, sm, xlog, slog);
 }
 
 // Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.

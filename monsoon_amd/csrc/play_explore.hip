@@ -23,13 +23,13 @@ __global__ void __launch_bounds__(64, WPE) k_play_explore(DevBuffers b, int n, i
 hipError_t explore_occupancy(int* blocks_per_cu, int lds_bytes) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_play_explore<DEFAULT_U, DEFAULT_W>, 64, lds_bytes);
 }
-void explore_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity, PlayLog lg,
-                  PlayExplore ex) {
-  hipLaunchKernelGGL((k_play_explore<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, lg,
-                     ex);
+void explore_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+                  const PlayLogged& a) {
+  hipLaunchKernelGGL((k_play_explore<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, a.lg,
+                     a.ex);
 }
-const ExploreOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, explore_occupancy}, explore_play};
+const LoggedOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, explore_occupancy}, explore_play};
 
 }  // namespace
 
-const ExploreOps* msbk::monsoon_play_explore_ops() { return &kOps; }
+const LoggedOps* msbk::monsoon_play_explore_ops() { return &kOps; }

@@ -21,11 +21,12 @@ __global__ void __launch_bounds__(64, WPE) k_play_log(DevBuffers b, int n, int m
 hipError_t log_occupancy(int* blocks_per_cu, int lds_bytes) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_play_log<DEFAULT_U, DEFAULT_W>, 64, lds_bytes);
 }
-void log_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity, PlayLog lg) {
-  hipLaunchKernelGGL((k_play_log<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, lg);
+void log_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+              const PlayLogged& a) {
+  hipLaunchKernelGGL((k_play_log<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, a.lg);
 }
-const LogOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, log_occupancy}, log_play};
+const LoggedOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, log_occupancy}, log_play};
 
 }  // namespace
 
-const LogOps* msbk::monsoon_play_log_ops() { return &kOps; }
+const LoggedOps* msbk::monsoon_play_log_ops() { return &kOps; }

@@ -40,17 +40,17 @@ __global__ void __launch_bounds__(64) k_sample_kat(int m, const double* scores, 
 hipError_t sample_occupancy(int* blocks_per_cu, int lds_bytes) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_play_sample<DEFAULT_U, DEFAULT_W>, 64, lds_bytes);
 }
-void sample_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity, PlayLog lg,
-                 PlayExplore ex, PlaySample sp) {
-  hipLaunchKernelGGL((k_play_sample<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, lg,
-                     ex, sp);
+void sample_play(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
+                 const PlayLogged& a) {
+  hipLaunchKernelGGL((k_play_sample<DEFAULT_U, DEFAULT_W>), dim3(grid), dim3(64), lds_bytes, stream, b, n, max_turns, rounds, persistent, parity, a.lg,
+                     a.ex, a.sp);
 }
-void sample_kat(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,
-                const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total, uint32_t* out_weight) {
-  hipLaunchKernelGGL(k_sample_kat, dim3(m), dim3(64), 0, stream, m, scores, n_legal, best, inv_t, draw1, out_rank, out_total, out_weight);
-}
-const SampleOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, sample_occupancy}, sample_play, sample_kat};
+const LoggedOps kOps = {{DEFAULT_U, DEFAULT_W, PlayLds<DEFAULT_U>::TOTAL, sample_occupancy}, sample_play};
 
 }  // namespace
 
-const SampleOps* msbk::monsoon_play_sample_ops() { return &kOps; }
+const LoggedOps* msbk::monsoon_play_sample_ops() { return &kOps; }
+void msbk::monsoon_sample_kat_launch(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,
+                                     const uint32_t* draw1, int32_t* out_rank, uint32_t* out_total, uint32_t* out_weight) {
+  hipLaunchKernelGGL(k_sample_kat, dim3(m), dim3(64), 0, stream, m, scores, n_legal, best, inv_t, draw1, out_rank, out_total, out_weight);
+}

@@ -10,14 +10,38 @@ MATCH_DTYPE = np.dtype([("p1", "<i4"), ("p2", "<i4"), ("seed", "<u4"), ("deck", 
 LOG_BUDGET = 256 << 20   # bytes of device log a batch of monsoon_rollout_logged may take (include/monsoon.h)
 
 
+# The arrays of a logged rollout's log (csrc/host_layout.h LOG_COLUMN, in RolloutLog's order): name, dtype, the value behind
+# a game's last step, bytes of device log per entry, and the entry point that introduces the array.
+LOG_ARRAYS = (("action", np.uint8, 255, 1, "monsoon_rollout_logged"),
+              ("score", np.float64, np.nan, 8, "monsoon_rollout_logged"),
+              ("n_legal", np.int16, 0, 2, "monsoon_rollout_logged"),
+              ("greedy", np.uint8, 255, 1, "monsoon_rollout_explore"),
+              ("explored", np.uint8, 0, 1, "monsoon_rollout_explore"),
+              ("taken_score", np.float64, np.nan, 8, "monsoon_rollout_explore"),
+              ("weight_total", np.uint32, 0, 4, "monsoon_rollout_sample"),
+              ("taken_weight", np.uint32, 0, 4, "monsoon_rollout_sample"))
+_LOG_ENTRIES = ("monsoon_rollout_logged", "monsoon_rollout_explore", "monsoon_rollout_sample")
+
+
+def _log_arrays(entry):
+    """Names of the arrays a call of `entry` logs: the ones it introduces and its predecessors'."""
+    return [name for name, *_, at in LOG_ARRAYS if _LOG_ENTRIES.index(at) <= _LOG_ENTRIES.index(entry)]
+
+
+def _entry_bytes(**asked):
+    """Bytes of device log one entry takes with the named arrays asked for (action always)."""
+    return sum(size for name, _, _, size, _ in LOG_ARRAYS if name == "action" or asked.get(name))
+
+
 def explore_entry_bytes(scores=True, n_legal=True, greedy=True, explored=True, taken_score=True):
     """Bytes of device log one entry of monsoon_rollout_explore takes, by the arrays asked for (action always): 1 .. 21."""
-    return 1 + 8 * bool(scores) + 2 * bool(n_legal) + bool(greedy) + bool(explored) + 8 * bool(taken_score)
+    return _entry_bytes(score=scores, n_legal=n_legal, greedy=greedy, explored=explored, taken_score=taken_score)
 
 
 def sample_entry_bytes(scores=True, n_legal=True, greedy=True, explored=True, taken_score=True, weight_total=True, taken_weight=True):
     """Bytes of device log one entry of monsoon_rollout_sample takes, by the arrays asked for (action always): 1 .. 29."""
-    return explore_entry_bytes(scores, n_legal, greedy, explored, taken_score) + 4 * bool(weight_total) + 4 * bool(taken_weight)
+    return _entry_bytes(score=scores, n_legal=n_legal, greedy=greedy, explored=explored, taken_score=taken_score,
+                        weight_total=weight_total, taken_weight=taken_weight)
 
 
 def _ptr(a):
@@ -91,12 +115,10 @@ class RolloutLog:
     def empty(cls, n, max_turns, scores=True, n_legal=True, explore=False, sample=False):
         """n rows of padding; explore: with the three arrays of an exploring rollout; sample: with those and the two of a
         sampling one."""
-        explore = explore or sample
-        return cls(np.full((n, max_turns), 255, dtype=np.uint8), np.full((n, max_turns), np.nan) if scores else None,
-                   np.zeros((n, max_turns), dtype=np.int16) if n_legal else None, np.zeros(n, dtype=np.int32),
-                   np.full((n, max_turns), 255, dtype=np.uint8) if explore else None,
-                   np.zeros((n, max_turns), dtype=np.uint8) if explore else None, np.full((n, max_turns), np.nan) if explore else None,
-                   np.zeros((n, max_turns), dtype=np.uint32) if sample else None, np.zeros((n, max_turns), dtype=np.uint32) if sample else None)
+        asked = dict.fromkeys(_log_arrays(_LOG_ENTRIES[2 if sample else 1 if explore else 0]), True)
+        asked.update(score=scores, n_legal=n_legal)
+        arrays = {name: np.full((n, max_turns), pad, dtype=dtype) if asked.get(name) else None for name, dtype, pad, *_ in LOG_ARRAYS}
+        return cls(steps=np.zeros(n, dtype=np.int32), **arrays)
 
     def taken_prob(self):
         """float64[n][max_turns]: taken_weight / weight_total, the probability the softmax gave the committed action GIVEN
@@ -110,8 +132,8 @@ class RolloutLog:
 
     def put(self, rows, other):
         """Rows `rows` become the rows of `other` (a log of len(rows) games with the same arrays)."""
-        self.action[rows], self.steps[rows] = other.action, other.steps
-        for name in ("score", "n_legal", "greedy", "explored", "taken_score", "weight_total", "taken_weight"):
+        self.steps[rows] = other.steps
+        for name, *_ in LOG_ARRAYS:
             if getattr(self, name) is not None:
                 getattr(self, name)[rows] = getattr(other, name)
 
@@ -458,19 +480,15 @@ class BatchEngine:
         steps = log.steps if log is not None else np.zeros(len(m), dtype=np.int32) if want_results else None
         extra, batch = (), self.max_games
         if log is not None:
-            c_log = _lib.RolloutLog(_ptr(log.action), _ptr(log.score), _ptr(log.n_legal))
-            extra = (ctypes.byref(c_log),)
+            # the arrays each entry point introduces, as its struct of host pointers (_lib.RolloutLog / ExploreLog / SampleLog)
+            c_logs = [struct(*(_ptr(getattr(log, name)) for name, *_, at in LOG_ARRAYS if at == e))
+                      for e, struct in zip(_LOG_ENTRIES, (_lib.RolloutLog, _lib.ExploreLog, _lib.SampleLog))]
+            extra = (ctypes.byref(c_logs[0]),)
             entry_bytes = 11   # a logged call's batches are cut by the log's budget too ...
             if explore is not None:   # ... an exploring or sampling call's by the arrays it asks for (include/monsoon.h)
-                c_xlog = _lib.ExploreLog(_ptr(log.greedy), _ptr(log.explored), _ptr(log.taken_score))
-                if explore.samples:
-                    c_ex, c_slog = explore.c_sample(), _lib.SampleLog(_ptr(log.weight_total), _ptr(log.taken_weight))
-                    extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog), ctypes.byref(c_slog))
-                    entry_bytes = sample_entry_bytes(log.score is not None, log.n_legal is not None)
-                else:
-                    c_ex = explore.c_struct()
-                    extra += (ctypes.byref(c_ex), ctypes.byref(c_xlog))
-                    entry_bytes = explore_entry_bytes(log.score is not None, log.n_legal is not None)
+                c_ex = explore.c_sample() if explore.samples else explore.c_struct()
+                extra += (ctypes.byref(c_ex),) + tuple(ctypes.byref(c) for c in c_logs[1:_LOG_ENTRIES.index(entry) + 1])
+                entry_bytes = _entry_bytes(**{name: getattr(log, name) is not None for name in _log_arrays(entry)})
             batch = min(batch, max(1, LOG_BUDGET // (entry_bytes * max_turns)))
         self._ck(getattr(self.lib, entry)(self.h, _ptr(weights), n_ind, _ptr(m), len(m), _ptr(deck_pairs), len(deck_pairs),
                                           max_turns, _ptr(counts), _ptr(results), _ptr(steps), *extra), entry)

@@ -1,10 +1,9 @@
 #!/bin/bash
 # Are the existing kernels instruction-identical in two builds of the library, and do they use the same resources?
 #   bash scripts/isa_diff.sh <csrc/build of the parent commit> <csrc/build of this tree>
-# For every object of the three record builds (the hot-kernel variants, env_opp.o, env_opp_explore.o, vs_expert.o, env_after.o, main.o, play_log.o,
-# play_explore.o, play_sample.o, env_snap.o, replay_log.o and replay_after.o; one the parent build does not have yet is not compared and printed as NEW
-# with its resources): the gfx950 code object is taken out of the
-# host object (llvm-objdump --offloading), disassembled, and compared with the kernel-name suffix of the anonymous
+# For every object the parent's build directory holds, per record build (std, ext, big; the hot-kernel variants first, then
+# the other objects by name), and every one only this tree's holds (not compared: printed as NEW with its resources): the
+# gfx950 code object is taken out of the host object (llvm-objdump --offloading), disassembled, and compared with the kernel-name suffix of the anonymous
 # namespace and the __hip_cuid_ symbol normalised.  Prints SAME / DIFFERENT per object, and next to it what decides the
 # waves per SIMD, old -> new: per kernel the VGPR count, the private segment (scratch) and the static LDS of the code-object
 # metadata, and the number of scratch_* instructions of the object.  Exit status 1 if any object differs, 2 if a kernel
@@ -27,8 +26,10 @@ res() {   # "vgpr V scratch S lds L" per kernel, in symbol order, then the scrat
   echo "scratch_* $(dis $1 | grep -c '^[[:space:]]*scratch_')"
 }
 for b in std ext big; do
-  for o in $old/$b/variant_*.o $old/$b/env_opp.o $old/$b/env_opp_explore.o $old/$b/vs_expert.o $old/$b/env_after.o $old/$b/main.o $old/$b/play_log.o $old/$b/play_explore.o $old/$b/play_sample.o $old/$b/env_snap.o $old/$b/replay_log.o $old/$b/replay_after.o; do
-    f=$b/$(basename $o)
+  names=$(for o in $old/$b/variant_*.o $old/$b/*.o; do basename $o; done | awk '!seen[$0]++'
+          for o in $new/$b/*.o; do [ -f $old/$b/$(basename $o) ] || basename $o; done)
+  for n in $names; do
+    o=$old/$b/$n; f=$b/$n
     if [ ! -f $o ]; then
       if [ -f $new/$f ]; then tn=$(unpack $new/$f); echo "NEW       $f ($(dis $tn | wc -l) lines)  $(res $tn)"; rm -rf $tn; fi
       continue

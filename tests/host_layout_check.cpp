@@ -114,13 +114,17 @@ static void check_layouts(size_t cap) {
     for (int flags = 0; flags < 4; flags++) {
       const size_t n = cap * max_turns;
       const bool sc = flags & 1, nl = flags & 2;
-      const RolloutLog l = rollout_log(n, sc, nl);
+      const Log l = log_layout(n, (sc ? log_bit(LOG_SCORE) : 0) | (nl ? log_bit(LOG_N_LEGAL) : 0));   // monsoon_rollout_logged's three arrays
       EXPECT(l.total == n * ((sc ? 8 : 0) + (nl ? 2 : 0) + 1), l.total, n);
-      std::vector<Field> f = {{l.action, 1, n}};
-      if (sc) f.push_back({l.score, 8, 8 * n});
-      if (nl) f.push_back({l.n_legal, 2, 2 * n});
-      EXPECT(sc || l.score == NONE, l.score, 0);
-      EXPECT(nl || l.n_legal == NONE, l.n_legal, 0);
+      std::vector<Field> f = {{l.at[LOG_ACTION], 1, n}};
+      if (sc) f.push_back({l.at[LOG_SCORE], 8, 8 * n});
+      if (nl) f.push_back({l.at[LOG_N_LEGAL], 2, 2 * n});
+      EXPECT(sc || l.at[LOG_SCORE] == NONE, l.at[LOG_SCORE], 0);
+      EXPECT(nl || l.at[LOG_N_LEGAL] == NONE, l.at[LOG_N_LEGAL], 0);
+      // score at 0, n_legal behind it, action behind that; no other column
+      EXPECT(l.at[LOG_SCORE] == (sc ? 0 : NONE) && l.at[LOG_N_LEGAL] == (nl ? (sc ? 8 * n : 0) : NONE), l.at[LOG_N_LEGAL], n);
+      EXPECT(l.at[LOG_ACTION] == (sc ? 8 * n : 0) + (nl ? 2 * n : 0) && l.total == l.at[LOG_ACTION] + n, l.at[LOG_ACTION], n);
+      for (int c : {LOG_TAKEN_SCORE, LOG_WEIGHT_TOTAL, LOG_TAKEN_WEIGHT, LOG_GREEDY, LOG_EXPLORED}) EXPECT(l.at[c] == NONE, c, l.at[c]);
       check_fields(f, l.total);
       n_layouts++;
     }

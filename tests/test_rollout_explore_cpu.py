@@ -161,8 +161,8 @@ def test_ladder_replays_explore_as_the_draws_prescribe():
 
 
 def test_device_log_layout_and_batch_cap_under_sanitizers(tmp_path):
-    """tests/explore_layout_check.cpp over host_layout.h's explore_log / explore_entry_bytes / log_batch_cap, and the same cap
-    formula in the Python layer."""
+    """tests/explore_layout_check.cpp over host_layout.h's log_layout / log_entry_bytes / log_batch_cap -- all 128 choices of
+    the seven optional columns, each against the layouts the one table replaced -- and the same cap formula in the Python layer."""
     cxx = shutil.which("g++") or shutil.which("clang++")
     assert cxx, "a host C++ compiler builds the oracle too"
     exe = str(tmp_path / "explore_layout_check")
@@ -172,7 +172,7 @@ def test_device_log_layout_and_batch_cap_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     words = r.stdout.split()
-    assert words[0] == "ok" and int(words[1]) == 6 * 3 * 32 and int(words[3]) == 4 * 3 * 4, r.stdout
+    assert words[0] == "ok" and int(words[1]) == 6 * 3 * 128 and int(words[3]) == 4 * 3 * 4, r.stdout
     assert explore_entry_bytes() == 21 and explore_entry_bytes(False, False) == 11 and explore_entry_bytes(True, True, False, False, False) == 11
     assert LOG_BUDGET // (explore_entry_bytes() * 30000) == 426 and LOG_BUDGET // (explore_entry_bytes() * 200) == 63913
     header = open(os.path.join(REPO, "include", "monsoon.h")).read()

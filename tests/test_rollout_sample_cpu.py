@@ -145,6 +145,32 @@ def test_log_arrays_entry_bytes_and_abi():
     assert game_log.LOG_COLUMNS["weight_total"][1] == game_log.LOG_COLUMNS["taken_weight"][1] == ()
 
 
+def test_empty_log_arrays_dtypes_shapes_and_padding():
+    """RolloutLog.empty for the four combinations of explore and sample, against literal values: which arrays there are,
+    their dtypes and shapes, and the value every entry holds (what the device pads with behind a game's last step)."""
+    base = {"action": ("|u1", 255), "score": ("<f8", None), "n_legal": ("<i2", 0)}
+    explore = {"greedy": ("|u1", 255), "explored": ("|u1", 0), "taken_score": ("<f8", None)}
+    sample = {"weight_total": ("<u4", 0), "taken_weight": ("<u4", 0)}
+    names = ("action", "score", "n_legal", "greedy", "explored", "taken_score", "weight_total", "taken_weight")
+    for ex, sm, want in ((False, False, base), (True, False, {**base, **explore}), (False, True, {**base, **explore, **sample}),
+                         (True, True, {**base, **explore, **sample})):
+        log = RolloutLog.empty(5, 3, explore=ex, sample=sm)
+        assert sorted(vars(log)) == sorted(names + ("steps",))
+        assert log.steps.dtype == np.int32 and log.steps.shape == (5,) and not log.steps.any()
+        for name in names:
+            a = getattr(log, name)
+            if name not in want:
+                assert a is None, (ex, sm, name)
+                continue
+            dtype, pad = want[name]
+            assert a.dtype.str == dtype and a.shape == (5, 3) and a.flags.c_contiguous and a.flags.writeable, (ex, sm, name)
+            assert np.isnan(a).all() if pad is None else (a == pad).all(), (ex, sm, name)
+        arrays = [getattr(log, name) for name in names if name in want] + [log.steps]
+        assert all(not np.shares_memory(a, b) for i, a in enumerate(arrays) for b in arrays[:i])
+    bare = RolloutLog.empty(2, 4, scores=False, n_legal=False, sample=True)
+    assert bare.score is None and bare.n_legal is None and bare.action.shape == (2, 4) and bare.taken_weight.dtype == np.uint32
+
+
 class _OracleEngine:
     """BatchEngine's reset / legal_mask / step / status / observe / state_hash over one record of the oracle, for game_log.replay."""
 
