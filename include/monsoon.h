@@ -22,7 +22,13 @@ extern "C" {
 #endif
 
 #define MONSOON_OK 0
-#define MONSOON_ERR_ARG 1       /* bad argument (null pointer, size, illegal action, unsupported card) */
+#define MONSOON_ERR_ARG 1       /* bad argument (null pointer, size, illegal action, unsupported card or deck) */
+/* What the standard build (libmonsoon_hip.so) refuses in every deck it is handed -- monsoon_reset, monsoon_rollout*,
+ * monsoon_replay*, monsoon_env_reset, monsoon_env_set_schedule's archetypes: the cards ua20 and b005, and a 12-card deck
+ * that lists a unit or structure card more than once (spells and up01 / up02 / up03 may repeat; a card in both players'
+ * decks is no repeat).  The reference's list.remove takes the first EQUAL card, so with such a deck the drawn object
+ * stays in the deck while it sits in the hand; only the extended record (libmonsoon_hip_ext.so, same ABI) plays that as
+ * the reference does.  The check runs before anything is loaded or launched; monsoon_last_error names the card. */
 #define MONSOON_ERR_DEVICE 2    /* HIP error; see monsoon_last_error */
 #define MONSOON_ERR_STATE 3     /* call order (e.g. step before reset) */
 
@@ -693,7 +699,10 @@ int monsoon_env_opponent_explored_dev(monsoon_t* h, void* out_dev);
  * next monsoon_env_step_dev on -- also a captured one: the graph holds the buffer's address, not its contents -- while
  * running episodes keep their decks.  MONSOON_ERR_ARG: tag == 0, a phase outside 0..2, n_preserve outside 0..12, in phases
  * 1 / 2 a pool size outside 12..128, an archetype entry or (phases 1 / 2) a pool entry that is not a card index or that
- * this record build does not support (ua20 and b005 need the extended record; every faction's pool holds ua20).
+ * this record build does not support (ua20 and b005 need the extended record; every faction's pool holds ua20); on the
+ * standard build also an archetype or a pool that lists a unit or structure card twice, and phase 1 with 0 < n_preserve
+ * < 12: the kept and the drawn cards of such a deck may repeat a card, which only the extended record plays as the
+ * reference does, and the host never sees a deck drawn on the device.
  * sc == NULL clears the schedule; MONSOON_ERR_STATE while a schedule-mode env is loaded.
  *
  * A walk that would read past the first 624 outputs of its stream cannot fail an asynchronous step: such an episode is

@@ -47,17 +47,47 @@ def supported_pool(include_fault_cards=False, extended=False):
     return [c for c in CARD_IDS if (extended or c not in UNSUPPORTED) and (include_fault_cards or c not in FAULT_CARDS)]
 
 
+# THE RULE, stated here once for the Python layer (msb_base.h deck_repeated_card states it for the
+# native side): a deck pair needs the extended record if a deck holds ua20 / b005, or lists a unit or structure card
+# more than once.  Unit / Structure equality is (card_id, player, position), so the reference's deck.remove(drawn card)
+# takes the first EQUAL object: the drawn one stays in the deck while it also sits in the hand, and ages there.  Only
+# the extended record (object ids, a weight per object) can express that; the standard build refuses such a deck.  A
+# spell compares by identity, and a card both players hold is no repeat (equality includes the player).  up01 / up02 /
+# up03 may repeat too: the shared object ages only in its owner's own play or cycle, and that owner never completes a
+# step (the step's observation shows the card and raises, which ends the game: FAULT_CARDS).
+_KIND_SPELL = 2
+_REPEATABLE = np.array([c["kind"] == _KIND_SPELL or c["id"] in FAULT_CARDS for c in CARD_META], dtype=bool)   # by card index: may be listed twice
+
+
+def _as_indices(decks):
+    flat = [CARD_INDEX[c] if isinstance(c, str) else int(c) for c in np.asarray(decks, dtype=object).ravel()]
+    if len(flat) % 12:
+        raise ValueError("decks of exactly 12 cards")
+    return np.array(flat, dtype=np.uint8).reshape(-1, 12)
+
+
+def repeats_card(decks):
+    """bool[n]: which 12-card decks (indices [n][12]) list a unit or structure card more than once."""
+    decks = np.asarray(decks, dtype=np.uint8).reshape(-1, 12)
+    s = np.sort(decks, axis=1)
+    return ((s[:, 1:] == s[:, :-1]) & ~_REPEATABLE[s[:, 1:]]).any(axis=1)
+
+
+def _deck_needs_extended(decks):
+    """bool[n] for 12-card decks [n][12] (indices): the rule above."""
+    return np.isin(decks, [CARD_INDEX[c] for c in NEEDS_EXTENDED]).any(axis=1) | repeats_card(decks)
+
+
 def needs_extended(decks):
-    """True if any deck (ids or indices) holds a card that only the extended build supports."""
-    idx = {CARD_INDEX[c] for c in NEEDS_EXTENDED}
-    return any((CARD_INDEX[c] if isinstance(c, str) else int(c)) in idx for c in np.asarray(decks, dtype=object).ravel())
+    """True if any deck (12 ids or indices each) needs the extended build: it holds ua20 / b005, or repeats a unit or
+    structure card (the rule above)."""
+    return bool(_deck_needs_extended(_as_indices(decks)).any())
 
 
 def needs_extended_each(deck_pairs):
-    """bool[n]: which deck pairs [n][2][12] (card indices) hold a card that only the extended build supports."""
-    pairs = np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 24)
-    idx = np.array(sorted(CARD_INDEX[c] for c in NEEDS_EXTENDED), dtype=np.uint8)
-    return np.isin(pairs, idx).any(axis=1)
+    """bool[n]: which deck pairs [n][2][12] (card indices) need the extended build (either deck does, by the rule above)."""
+    decks = np.asarray(deck_pairs, dtype=np.uint8).reshape(-1, 12)
+    return _deck_needs_extended(decks).reshape(-1, 2).any(axis=1)
 
 
 # Configuration C5 (SURVEY.md §8d): every game draws its two decks from the 109 observable cards -- every card but

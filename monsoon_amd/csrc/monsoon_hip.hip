@@ -1036,11 +1036,23 @@ static int launch_reset(monsoon_t* h, int n) {
 
 static int fold_stats(monsoon_t* h);
 
-static int check_decks(monsoon_t* h, const uint8_t* decks, size_t n_cards, const char* who) {
+// n_cards card indices: a table of 12-card decks, or with pool = true a pool to draw from (any length, no deck rule).
+static int check_decks(monsoon_t* h, const uint8_t* decks, size_t n_cards, const char* who, bool pool = false) {
   for (size_t i = 0; i < n_cards; i++) {
     if (decks[i] >= NUM_CARDS || card_unsupported(decks[i]))
       return bad_arg(h, who, std::string("card not supported by this build: ") + (decks[i] < NUM_CARDS ? kCardIds[decks[i]] : "index out of range"));
   }
+#if !(defined(MSB_EXT) && MSB_EXT)
+  // the standard record's rule (msb_base.h deck_repeated_card), per 12-card deck, and over a whole pool: a deck drawn
+  // from one that lists a card twice can hold it twice.  An id tells what may repeat: s... is a spell, up0. has int_id < 0
+  const size_t span = pool ? n_cards : 12;
+  for (size_t d = 0; d + span <= n_cards && span; d += span) {
+    int c = deck_repeated_card(decks + d, (int)span, [](int card) { return kCardIds[card][0] == 's' || strncmp(kCardIds[card], "up0", 3) == 0; });
+    if (c >= 0)
+      return bad_arg(h, who, std::string(pool ? "the pool" : "a deck") + " lists the unit / structure card " + kCardIds[c] +
+                                 " more than once: only the extended record plays that as the reference does (extended=1, libmonsoon_hip_ext.so)");
+  }
+#endif
   return MONSOON_OK;
 }
 
@@ -2452,9 +2464,16 @@ int monsoon_env_set_schedule(monsoon_t* h, const monsoon_deck_schedule* sc) {
   if (bad) return bad_arg(h, "monsoon_env_set_schedule", bad);
   for (int side = 0; side < 2; side++) {
     int rc = check_decks(h, sc->archetype[side], 12, "monsoon_env_set_schedule (archetype)");
-    if (!rc && draws) rc = check_decks(h, sc->pool[side], (size_t)sc->pool_n[side], "monsoon_env_set_schedule (pool)");
+    if (!rc && draws) rc = check_decks(h, sc->pool[side], (size_t)sc->pool_n[side], "monsoon_env_set_schedule (pool)", true);
     if (rc) return rc;
   }
+#if !(defined(MSB_EXT) && MSB_EXT)
+  // an explore draw keeps n_preserve cards of the archetype and adds 12 - n_preserve from a pool that still holds the
+  // archetype: the deck can list a card twice, and the host never sees it (no draw at 12; at 0 all twelve are one sample)
+  if (sc->phase == DS_EXPLORE && sc->n_preserve > 0 && sc->n_preserve < 12)
+    return bad_arg(h, "monsoon_env_set_schedule", "an explore generation with 0 < n_preserve < 12 can draw a deck that lists a card twice: "
+                                                  "only the extended record plays that as the reference does (extended=1, libmonsoon_hip_ext.so)");
+#endif
   HIP_TRY(h, bind_device(h));
   if (!h->d_sched) {
     HIP_TRY(h, h->mem.alloc(&h->d_sched, sizeof(monsoon_deck_schedule) + 64));
@@ -2517,7 +2536,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   }
   const bool by_schedule = !cfg->pool_n && !decks;   // the stored schedule's cards were checked by monsoon_env_set_schedule
   int rc = by_schedule ? MONSOON_OK
-           : cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)")
+           : cfg->pool_n ? check_decks(h, cfg->pool, (size_t)cfg->pool_n, "monsoon_env_reset (pool)", true)
                          : check_decks(h, decks, (size_t)n * 24, "monsoon_env_reset");
   if (rc) return rc;
   HIP_TRY(h, bind_device(h));

@@ -179,4 +179,21 @@ static const WeightTable g_wtab = make_weight_table();
 // Card indices used by name in rules.h (sorted-id order; checked against card_ids.json by tests).
 #include "card_names.inc"
 
+// THE RULE of the standard record (monsoon_amd/cards.py states it for the Python layer): a deck that lists
+// a unit or structure card more than once needs the extended record.  Unit / Structure equality is (card_id, player,
+// position), so the reference's deck.remove(drawn card) takes the first EQUAL object: the drawn one stays in the deck
+// while it also sits in the hand, and ages there -- which only object ids and a weight per object can express.  A spell
+// compares by identity and may repeat.  So may up01 / up02 / up03 (int_id < 0): the shared object ages only in its
+// owner's own play or cycle (nothing makes the opponent discard), and that owner never completes a step -- the step's
+// observation shows the card and raises (FAULT_INT_CARD), which ends the game in the reference and here.  Host code
+// only (may_repeat: the caller's view of the card table: a spell, or int_id < 0).  Returns the first repeated card of
+// the n listed (a deck's 12, or a pool that decks are drawn from) that may not repeat, or -1.
+template <class MayRepeat>
+inline int deck_repeated_card(const uint8_t* cards, int n, MayRepeat may_repeat) {
+  for (int i = 1; i < n; i++)
+    for (int j = 0; j < i; j++)
+      if (cards[i] == cards[j] && !may_repeat(cards[i])) return cards[i];
+  return -1;
+}
+
 }  // namespace msb

@@ -140,7 +140,8 @@ class RolloutLog:
 
 class BatchEngine:
     def __init__(self, max_games, device=0, lanes_per_game=0, stack_bytes=0, extended=False):
-        """extended=True loads the build with the larger per-game record (decks holding ua20 / b005), extended=2 the
+        """extended=True loads the build with the larger per-game record (decks holding ua20 / b005 or a unit / structure
+        card twice: cards.needs_extended), extended=2 the
         one with the largest (254 entity slots; the replay tier of monsoon_amd/fitness.py).
         lanes_per_game selects a hot-kernel variant of the build (0 = default); a value the build does not hold is
         refused."""

@@ -49,7 +49,8 @@ class Stormbound:
         self.seed = int(seed) & 0xFFFFFFFF
         self._decks = np.stack([deck_indices(deck0), deck_indices(deck1)])
         self._factions = np.array([[faction0, faction1]], dtype=np.uint8)
-        self._eng = engine or BatchEngine(1, device=device)
+        # no engine given: the smallest record build that plays this pair as the reference does (cards.needs_extended)
+        self._eng = engine or BatchEngine(1, device=device, extended=int(needs_extended(self._decks)))
         self._eng.reset(np.array([self.seed], dtype=np.uint32), self._decks[None], self._factions)
 
     @property
@@ -168,9 +169,10 @@ class EvolutionaryGame(Game):
     the pair is deck_config.game_decks(generation, seed, TAG_ENV) -- the decks of the VecEnv episode that starts from the
     same seed (VecEnv.reset(deck_schedule=deck_config, generation=generation)) -- else get_deck_configuration(generation)
     from the config's sequential stream, as in the reference.  deck_config None is the default pair Stormbound plays.  A
-    pair that holds ua20 or b005 is played on the extended record build (extended=None; 0 / 1 / 2 names the build, e.g. the
-    one a VecEnv runs on: the standard and the extended records keep hand and deck differently -- value entries and object
-    ids, DESIGN.md §2a -- and play a deck that holds a card twice, as explore decks often do, differently)."""
+    pair that holds ua20 or b005, or a deck that lists a unit or structure card twice -- as explore decks often do -- is
+    played on the extended record build (extended=None: cards.needs_extended decides; 0 / 1 / 2 names the build, e.g. the
+    one a VecEnv runs on).  Only the extended record plays a repeated card as the reference does: there the drawn object
+    stays in the deck while it sits in the hand, and the standard build refuses such a deck."""
 
     def __init__(self, seed=None, generation=0, deck_config=None, device=0, extended=None):
         from .decks import TAG_ENV

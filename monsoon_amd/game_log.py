@@ -67,7 +67,7 @@ def sample_rank(weights, draw1):
 def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, explore=None):
     """A schedule played on the smallest record each game needs, with its log.  engine_for_tier(tier) is the engine of a
     record (0 standard, 1 extended, 2 large): anything with BatchEngine's rollout_logged and rollout_faults.  The rule is
-    fitness.tiered_rollout's, the same function (fitness._ladder): a deck pair holding ua20 / b005 starts on the extended
+    fitness.tiered_rollout's, the same function (fitness._ladder): a deck pair that cards.needs_extended_each names (ua20 / b005, a unit or structure card twice) starts on the extended
     record, a game that ends on a limit of its record (fitness.record_limited) is played again on the next larger one, and
     its rows -- the log's among them -- are replaced.  An engine is handed only the deck pairs its sub-schedule names.
     explore = an engine.Explore: every tier plays with that rule (the draws are keyed by the match's seed and the step, so a

@@ -112,7 +112,7 @@ class VecEnv:
     INTEGRATION.md for a trainer loop."""
 
     def __init__(self, max_slots, device=0, extended=0, lanes_per_game=0):
-        """extended = 0 / 1 / 2 selects the record build (1: decks holding ua20 / b005).  Raises MonsoonError when no
+        """extended = 0 / 1 / 2 selects the record build (1: decks holding ua20 / b005, or a unit / structure card twice).  Raises MonsoonError when no
         gfx950 device is usable."""
         # torch ships a ROCm runtime of its own.  It has to be the first one the process loads: once libmonsoon_hip*.so has
         # pulled in the system's, a torch imported afterwards finds no device (torch.cuda.is_available() is False).  The
@@ -173,7 +173,10 @@ class VecEnv:
         starts; set_deck_schedule moves the generation between steps; decks() tells what every slot is playing.  Factions
         stay those of `factions` (episode 0 only, as ever).  Every faction's pool holds ua20 and Shadowfen's b005, so a
         schedule made from a config needs VecEnv(extended=1) once it draws (explore and balance phases): on the standard
-        build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised.
+        build the library refuses it (MONSOON_ERR_ARG) and MonsoonError is raised.  Whatever its pools hold, the standard
+        build also refuses an explore generation that keeps some but not all of the archetype (0 < n_preserve < 12): the
+        kept cards and the drawn ones may repeat a card, which only the extended record plays as the reference does
+        (DESIGN.md §9), and the host never sees a deck drawn on the device.  The message names extended=1.
 
         opponent_explore (an OpponentExplore; opponent "heuristic" only) makes the opponents epsilon-greedy from the first
         decision on, and lets set_opponent_explore retune them between steps -- eps 0 everywhere arms the env for that and

@@ -189,6 +189,12 @@ int orc_reset(void* h, int gi, uint32_t seed, const uint8_t* deck0, const uint8_
   g.la_fault = 0;
   Engine<FlatMem> e = engine(g);
   e.init_game(deck0, deck1, f0, f1, seed);
+#if !(defined(MSB_EXT) && MSB_EXT)
+  // the standard record cannot play a deck that repeats a unit / structure card as the reference does (msb_base.h
+  // deck_repeated_card): the game is built and faulted, FAULT_UNSUPPORTED, as monsoon_reset refuses it with MONSOON_ERR_ARG
+  auto may_repeat = [](int c) { return g_cards[c].kind == KIND_SPELL || g_cards[c].int_id < 0; };
+  if (deck_repeated_card(deck0, 12, may_repeat) >= 0 || deck_repeated_card(deck1, 12, may_repeat) >= 0) e.set_fault(FAULT_UNSUPPORTED);
+#endif
   commit_rng(g, e);
   return e.fault();
 }

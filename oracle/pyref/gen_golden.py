@@ -19,6 +19,9 @@ by running it here and committing inputs + expected outputs (data only, no refer
   population_seed42.npz        GA driver: initial population + first offspring for config.seed=42
   trace_live_*.npz             the difffuzz.py runs of tests/test_reference_live.py (features at every step)
   checkpoint_reference.pkl     the reference's own Population.save_population checkpoint (mu = lambda = 12, seed 9)
+  trace_dup.npz, trace_heuristic_dup.npz, trace_vs_expert_dup.npz
+                               decks that hold a card more than once: random-policy games (the fields of trace_live_*),
+                               heuristic self-play, agent against the scripted bot; with their coverage counts
 
 Usage: PYTHONHASHSEED=0 python oracle/pyref/gen_golden.py [--only NAME] [--jobs N]
 """
@@ -108,13 +111,50 @@ def gen_score():
 
 
 # ---------------------------------------------------------------------------------------------
+# Coverage of the repeated-deck fixtures (trace_dup and its companions), measured on the reference alone and by object
+# identity: Unit / Structure equality is (card_id, player, position), so Player.draw's deck.remove(choice) can take
+# another, equal object than the one drawn, which then sits in the hand and the deck at once.
+COV = {"reweight": 0, "aged": 0}
+
+
+def install_coverage():
+    """Count, in this process, Player.reweight calls over a deck that lists one object twice and Player.play calls on a
+    hand card whose weight is not 1 (a fresh draw sets it to 1: only an object that is also in the deck ages)."""
+    from player import Player
+    if getattr(Player, "_coverage", False):
+        return
+    reweight, play = Player.reweight, Player.play
+
+    def counted_reweight(self):
+        if len({id(c) for c in self.deck}) < len(self.deck):
+            COV["reweight"] += 1
+        return reweight(self)
+
+    def counted_play(self, index, position):
+        if getattr(self.hand[index], "weight", 1) != 1:
+            COV["aged"] += 1
+        return play(self, index, position)
+    Player.reweight, Player.play, Player._coverage = counted_reweight, counted_play, True
+
+
+def listing(g):
+    """(an object is listed in a hand and in that player's deck, an object is listed twice in one deck) right now."""
+    shared = twice = False
+    for p in (g.board.local, g.board.remote):
+        shared |= any(c is d for c in p.hand for d in p.deck)
+        twice |= len({id(c) for c in p.deck}) < len(p.deck)
+    return int(shared), int(twice)
+
+
 def random_trace(args):
     seed, d0, d1, steps, want_feat = args[:5]
     expert = len(args) > 5 and args[5]
     from evo.features import StateFeatures
+    install_coverage()
+    COV["reweight"] = COV["aged"] = 0
     g = H.make_game(seed, d0, d1)
     pol = np.random.RandomState(seed + 1000)
-    rec = dict(legal=[], action=[], hash=[], obs=[], reward=[], done=[], feat=[], fault=0)
+    rec = dict(legal=[], action=[], hash=[], obs=[], reward=[], done=[], feat=[], fault=0, shared=0, twice=0)
     init_hash = H.fnv1a64(H.canon(g))
     for _ in range(steps):
         la = g.legal_actions()
@@ -142,12 +182,16 @@ def random_trace(args):
         rec["done"].append(int(done))
         if want_feat:
             rec["feat"].append(StateFeatures(obs, g.to_play()).get_feature_vector())
+        shared, twice = listing(g)
+        rec["shared"] += shared
+        rec["twice"] += twice
         if g.have_winner():
             break
+    rec["reweight"], rec["aged"] = COV["reweight"], COV["aged"]
     return seed, init_hash, rec
 
 
-def pack_traces(name, jobs, results, decks0, decks1):
+def pack_traces(name, jobs, results, decks0, decks1, extra=None):
     out = dict(seeds=[], init_hash=[], offsets=[0], fault=[], legal=[], action=[], hash=[], obs=[], reward=[], done=[], feat=[])
     for seed, init_hash, rec in results:
         out["seeds"].append(seed)
@@ -172,6 +216,7 @@ def pack_traces(name, jobs, results, decks0, decks1):
         deck0=np.array(decks0, dtype=np.uint8), deck1=np.array(decks1, dtype=np.uint8))
     if out["feat"]:
         arrs["feat"] = np.array(out["feat"], dtype=np.float64)
+    arrs.update(extra or {})
     np.savez_compressed(os.path.join(GOLD, name), **arrs)
     print(name, "games", len(out["seeds"]), "steps", len(out["action"]))
 
@@ -286,7 +331,7 @@ def heuristic_trace(args):
         wv1.weights = np.array(w_second, dtype=np.float64)
     agents = [HeuristicAgent(wv, 0), HeuristicAgent(wv1, 1)]
     adapter = StormboundAdapter(game)
-    rec = dict(action=[], hash=[], best=[], shash=[], nlegal=[])
+    rec = dict(action=[], hash=[], best=[], shash=[], nlegal=[], shared=0, twice=0)
     steps = 0
     fault = 0
     with contextlib.redirect_stdout(io.StringIO()):
@@ -309,6 +354,9 @@ def heuristic_trace(args):
                 break
             steps += 1
             rec["hash"].append(H.fnv1a64(H.canon(adapter.game.env)))
+            shared, twice = listing(adapter.game.env)
+            rec["shared"] += shared
+            rec["twice"] += twice
     env = adapter.game.env
     b = {int(env.board.local.order): env.board.local.strength, int(env.board.remote.order): env.board.remote.strength}
     result = -1 if fault else (0 if (b[1] < 0 <= b[0]) else 1 if (b[0] < 0 <= b[1]) else -1)
@@ -432,6 +480,190 @@ def gen_heuristic_c5(indices, max_turns, jobs):
           "ended by an exception", int(np.sum(out["fault"])))
 
 
+# ---------------------------------------------------------------------------------------------
+# Decks that hold a card more than once: trace_dup.npz, trace_heuristic_dup.npz, trace_vs_expert_dup.npz.
+# Every class draws its decks from a stream of the candidate's seed; candidates are tried in seed order and the first
+# ones that meet the class's condition ON THE REFERENCE (listing / COV above: object identity, nothing of the product)
+# are kept.  The counts go into the files, so that a CPU test can assert the conditions without the reference.
+DUP_POOL = [c for c in H.CARD_IDS if c not in UNSUPPORTED and c not in FAULT_CARDS]
+# class -> (what is repeated: [(kinds, extra copies)], cards both decks must hold).  kinds by id prefix: u nit, b structure, s pell.
+DUP_CLASSES = [
+    ("unit_twice", [("u", 1)], ()),
+    ("structure_twice", [("b", 1)], ()),
+    ("three_repeats", [("ub", 1), ("ub", 1), ("ubs", 1)], ()),
+    ("one_card_three_times", [("ub", 2)], ()),
+    ("next_to_b305", [("b", 1)], ("b305",)),
+    ("next_to_ua20", [("ub", 1)], ("ua20",)),
+    ("next_to_b005", [("ub", 1)], ("b005",)),
+    ("explore_phase", None, ()),
+    ("spells_only", [("s", 1), ("s", 1)], ()),
+]
+DUP_CLASS_NAMES = [c[0] for c in DUP_CLASSES]
+DUP_SPELLS_ONLY = DUP_CLASS_NAMES.index("spells_only")
+
+
+def dup_deck(rs, spec, must=()):
+    """12 cards in a drawn order: `must`, one card per spec entry of the entry's kinds with its extra copies, the rest
+    distinct cards of DUP_POOL."""
+    chosen = []
+    for kinds, _ in spec:
+        cands = [c for c in DUP_POOL if c[0] in kinds and c not in chosen and c not in must]
+        chosen.append(cands[int(rs.randint(0, len(cands)))])
+    copies = [c for c, (_, extra) in zip(chosen, spec) for _ in range(extra)]
+    rest = [c for c in DUP_POOL if c not in chosen and c not in must]
+    fill = [str(c) for c in rs.choice(rest, 12 - len(must) - len(chosen) - len(copies), replace=False)]
+    deck = list(must) + chosen + fill + copies
+    return [deck[int(i)] for i in rs.permutation(12)]
+
+
+def repeats_non_spell(deck):
+    return any(c[0] != "s" and deck.count(c) > 1 for c in deck)
+
+
+def dup_pair(klass, seed):
+    """The deck pair of candidate `seed` of class number klass; None where the candidate is no member of the class."""
+    name, spec, must = DUP_CLASSES[klass]
+    if spec is not None:
+        rs = np.random.RandomState(seed ^ 0x9E3779B9)
+        return dup_deck(rs, spec, must), dup_deck(rs, spec, must)
+    # real explore-phase pairs: the per-game schedule of the project's GA configuration (monsoon_amd/decks.py restates
+    # utils.DeckEvolutionConfig over card ids, pinned by deck_schedule.json), generations 5 and 7
+    sys.path.insert(0, H.REPO)
+    from monsoon_amd.decks import DeckEvolutionConfig
+    cfg = DeckEvolutionConfig(H.DECKS["IRONCLAD"], H.DECKS["SWARM"], exploit_generations=2, explore_generations=6, seed=123, per_game=True)
+    d0, d1 = cfg.game_decks(5 + 2 * (seed & 1), seed)
+    if any(c in FAULT_CARDS for c in d0 + d1) or not (repeats_non_spell(d0) or repeats_non_spell(d1)):
+        return None
+    return list(d0), list(d1)
+
+
+def explore_share(generations=(3, 5, 7), games=2000):
+    """Share of the schedule's game seeds 0 .. games-1 whose pair repeats a unit / structure card, and any card, per generation."""
+    sys.path.insert(0, H.REPO)
+    from monsoon_amd.decks import DeckEvolutionConfig
+    cfg = DeckEvolutionConfig(H.DECKS["IRONCLAD"], H.DECKS["SWARM"], exploit_generations=2, explore_generations=6, seed=123, per_game=True)
+    out = []
+    for gen in generations:
+        pairs = [cfg.game_decks(gen, s) for s in range(games)]
+        out.append([gen, games, sum(repeats_non_spell(a) or repeats_non_spell(b) for a, b in pairs),
+                    sum(len(set(a)) < 12 or len(set(b)) < 12 for a, b in pairs)])
+    return np.array(out, dtype=np.int32)
+
+
+def choose_dup(play, quotas, seed0, jobs, accept):
+    """Candidates seed0 + 1000 * class + j in order of j; keeps per class the first quota whose game `accept`s, at most a
+    quarter of them (rounded down) ended by an exception.  play(task) -> game; task = (seed, d0, d1, class, j)."""
+    kept = []
+    with ProcessPoolExecutor(jobs) as ex:
+        for klass, quota in enumerate(quotas):
+            got, faulted, j = [], 0, 0
+            while len(got) < quota:
+                tasks = []
+                while len(tasks) < jobs:
+                    pair = dup_pair(klass, seed0 + 1000 * klass + j)
+                    if pair is not None:
+                        tasks.append((seed0 + 1000 * klass + j, pair[0], pair[1], klass, j))
+                    j += 1
+                for task, game in zip(tasks, ex.map(play, tasks)):
+                    ok, fault = accept(klass, game, len(got))
+                    if not ok or (fault and faulted >= quota // 4) or len(got) >= quota:
+                        continue
+                    faulted += fault
+                    got.append((task, game))
+            kept += got
+    return kept
+
+
+def dup_random_game(task):
+    seed, d0, d1 = task[:3]
+    return random_trace((seed, d0, d1, 300, True))
+
+
+def gen_dup(jobs):
+    """trace_dup.npz: random-policy games on decks that repeat a card, the fields of trace_live_*, the class of each game and
+    the coverage counts.  Every game whose decks repeat a unit / structure has a step behind which an object sits in a hand
+    and its deck at once."""
+    quotas = [5, 5, 5, 4, 4, 4, 4, 5, 4]
+    kept = choose_dup(dup_random_game, quotas, 120000, jobs,
+                      lambda klass, game, n: (klass == DUP_SPELLS_ONLY or game[2]["shared"] > 0, game[2]["fault"]))
+    recs = [game[2] for _, game in kept]
+    cov = {k: np.array([r[k] for r in recs], dtype=np.int32) for k in ("shared", "twice", "reweight", "aged")}
+    klass = np.array([t[3] for t, _ in kept], dtype=np.uint8)
+    faults = sum(r["fault"] for r in recs)
+    assert all(cov["shared"][klass != DUP_SPELLS_ONLY] > 0) and not cov["shared"][klass == DUP_SPELLS_ONLY].any()
+    assert cov["twice"].sum() >= 10 and cov["reweight"].sum() >= 10 and cov["aged"].sum() >= 5, {k: int(v.sum()) for k, v in cov.items()}
+    assert 4 * faults <= len(recs), faults
+    assert (klass == DUP_CLASS_NAMES.index("explore_phase")).sum() >= 4
+    pack_traces("trace_dup.npz", jobs, [game for _, game in kept], [idx(t[1]) for t, _ in kept], [idx(t[2]) for t, _ in kept],
+                extra=dict(klass=klass, class_names=np.array(DUP_CLASS_NAMES), candidate=np.array([t[4] for t, _ in kept], dtype=np.int32),
+                           cov_shared=cov["shared"], cov_twice=cov["twice"], cov_reweight=cov["reweight"], cov_aged=cov["aged"],
+                           explore_share=explore_share()))
+    print("trace_dup.npz coverage", {k: int(v.sum()) for k, v in cov.items()}, "ended by an exception", faults,
+          "candidates", [t[4] for t, _ in kept], "bytes", os.path.getsize(os.path.join(GOLD, "trace_dup.npz")))
+
+
+def dup_heuristic_game(task):
+    seed, d0, d1 = task[:3]
+    return heuristic_trace((seed, d0, d1, 80))
+
+
+def gen_heuristic_dup(jobs):
+    """trace_heuristic_dup.npz: HeuristicAgent self-play (W0) on repeated decks, the fields of trace_heuristic_pool_ext."""
+    quotas = [2, 2, 1, 1, 1, 1, 0, 0, 0]
+    kept = choose_dup(dup_heuristic_game, quotas, 140000, jobs, lambda klass, game, n: (game[1]["shared"] > 0, game[3]))
+    out = dict(seeds=[], offsets=[0], result=[], fault=[], action=[], hash=[], best=[], shash=[], nlegal=[])
+    for _, (seed, rec, result, fault) in kept:
+        out["seeds"].append(seed)
+        out["result"].append(result)
+        out["fault"].append(fault)
+        for k in ("action", "hash", "best", "shash", "nlegal"):
+            out[k] += rec[k]
+        out["offsets"].append(len(out["action"]))
+    np.savez_compressed(
+        os.path.join(GOLD, "trace_heuristic_dup.npz"), seeds=np.array(out["seeds"], dtype=np.uint32),
+        offsets=np.array(out["offsets"], dtype=np.int64), result=np.array(out["result"], dtype=np.int8),
+        fault=np.array(out["fault"], dtype=np.uint8),
+        action=np.array(out["action"], dtype=np.uint8), hash=np.array(out["hash"], dtype=np.uint64),
+        best=np.array(out["best"], dtype=np.float64), shash=np.array(out["shash"], dtype=np.uint64),
+        nlegal=np.array(out["nlegal"], dtype=np.int16), decks=np.array([[idx(t[1]), idx(t[2])] for t, _ in kept], dtype=np.uint8),
+        w0=W0, max_turns=np.int32(80), klass=np.array([t[3] for t, _ in kept], dtype=np.uint8), class_names=np.array(DUP_CLASS_NAMES),
+        cov_shared=np.array([g[1]["shared"] for _, g in kept], dtype=np.int32), cov_twice=np.array([g[1]["twice"] for _, g in kept], dtype=np.int32))
+    print("trace_heuristic_dup.npz games", len(kept), "decisions", len(out["action"]), "look-ahead steps", int(np.sum(out["nlegal"])),
+          "ended by an exception", int(np.sum(out["fault"])), "steps with a shared object", [g[1]["shared"] for _, g in kept])
+
+
+def dup_vs_expert_game(task):
+    sys.path.insert(0, os.path.join(H.REPO, "scripts"))
+    import gen_golden_vs_expert as V
+    seed, d0, d1, _, j = task
+    return V.play((seed, d0, d1, j % 2))
+
+
+def gen_vs_expert_dup(jobs):
+    """trace_vs_expert_dup.npz: the trace_vs_expert contract (scripts/gen_golden_vs_expert.py: its loop, its fields) on
+    repeated decks, the scripted bot on each side."""
+    quotas = [2, 2, 0, 0, 0, 0, 0, 0, 0]
+    kept = choose_dup(dup_vs_expert_game, quotas, 160000, jobs, lambda klass, game, n: (game["shared"] > 0 and game["bot_side"] == n % 2, game["fault"]))
+    games = [g for _, g in kept]
+    assert {g["bot_side"] for g in games} == {0, 1}
+    offsets, soffsets = [0], [0]
+    for g in games:
+        offsets.append(offsets[-1] + len(g["action"]))
+        soffsets.append(soffsets[-1] + len(g["shash"]))
+    cat = lambda k, dt: np.array([x for g in games for x in g[k]], dtype=dt)   # noqa: E731
+    col = lambda k, dt: np.array([g[k] for g in games], dtype=dt)   # noqa: E731
+    np.savez_compressed(
+        os.path.join(GOLD, "trace_vs_expert_dup.npz"), seeds=col("seed", np.uint32), bot_side=col("bot_side", np.int8),
+        result=col("result", np.int8), fault=col("fault", np.uint8), steps=col("steps", np.int32), winner=col("winner", np.uint8),
+        final=col("final", np.uint64), deck0=np.array([idx(t[1]) for t, _ in kept], dtype=np.uint8),
+        deck1=np.array([idx(t[2]) for t, _ in kept], dtype=np.uint8), offsets=np.array(offsets, dtype=np.int64),
+        soffsets=np.array(soffsets, dtype=np.int64), action=cat("action", np.uint8), bot=cat("bot", np.uint8),
+        hash=cat("hash", np.uint64), shash=cat("shash", np.uint64), w0=W0, max_turns=np.int32(200),
+        cov_shared=col("shared", np.int32), cov_twice=col("twice", np.int32))
+    print("trace_vs_expert_dup.npz games", len(games), "entries", offsets[-1], "bot sides", [g["bot_side"] for g in games],
+          "steps with a shared object", [g["shared"] for g in games])
+
+
 def gen_initial():
     recs, lens, seeds = [], [], []
     for deck in ("N12V", "N12M", "S12"):
@@ -546,6 +778,10 @@ def main():
         "live_b005": lambda: gen_live("trace_live_b005.npz", 40, 300, 90000, args.jobs, ext=True, must=("b005",)),
         "live_expert": lambda: gen_live("trace_live_expert.npz", 12, 300, 91000, args.jobs, deck="IRONCLAD", deck2="SWARM", expert=True),
         "checkpoint": gen_checkpoint,
+        # decks that hold a card more than once
+        "dup": lambda: gen_dup(args.jobs),
+        "heuristic_dup": lambda: gen_heuristic_dup(args.jobs),
+        "vs_expert_dup": lambda: gen_vs_expert_dup(args.jobs),
     }
     for name, fn in todo.items():
         if args.only and args.only != name:

@@ -50,7 +50,7 @@ def play(args):
     wv.weights = W0.copy()
     agent = HeuristicAgent(wv, 1 - bot_side)
     rec = dict(action=[], bot=[], hash=[], shash=[])
-    steps = fault = 0
+    steps = fault = shared = twice = 0   # shared / twice: steps behind which one card OBJECT is listed in a hand and its deck / twice in a deck
     with contextlib.redirect_stdout(io.StringIO()):
         while not env.have_winner() and steps < MAX_TURNS:
             adapter = StormboundAdapter(game)   # as play_vs_expert.py does every turn: the adapter caches its observation
@@ -79,10 +79,13 @@ def play(args):
                 fault = 1
                 break
             rec["hash"].append(H.fnv1a64(H.canon(env)))
+            players = (env.board.local, env.board.remote)
+            shared += any(c is d for p in players for c in p.hand for d in p.deck)
+            twice += any(len({id(c) for c in p.deck}) < len(p.deck) for p in players)
     b = {int(env.board.local.order): env.board.local.strength, int(env.board.remote.order): env.board.remote.strength}
     result = -1 if fault else (0 if (b[1] < 0 <= b[0]) else 1 if (b[0] < 0 <= b[1]) else -1)
     return dict(seed=seed, bot_side=bot_side, result=result, fault=fault, steps=steps, winner=int(env.have_winner()),
-                final=H.fnv1a64(H.canon(env)), **rec)
+                final=H.fnv1a64(H.canon(env)), shared=shared, twice=twice, **rec)
 
 
 def main():

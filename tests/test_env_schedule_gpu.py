@@ -2,7 +2,9 @@
 set_deck_schedule, decks(), monsoon_amd.game.EvolutionaryGame): every episode's decks are the pair the schedule in force
 when it starts draws for its seed -- the stdlib's draw, through tests/vec_env_schedule_model.py -- in lockstep with the
 model of the env contract; across a generation change, inside a captured step, after a restore; on the extended build with
-a real faction schedule; and the argument errors."""
+a real faction schedule; and the argument errors.  An explore generation that keeps some but not all of the archetype can
+draw a deck that lists a card twice, which only the extended record plays as the reference does: the
+standard build refuses such a schedule (tests/test_dup_decks_gpu.py), so those cases run on VecEnv(extended=1)."""
 import ctypes
 
 import numpy as np
@@ -55,10 +57,11 @@ def test_parity_with_the_model(name, sched, opponent, agent_side):
     salt = [p[0] for p in PARITY].index(name)
     params = standard_schedule(generation=40 + salt, **sched)
     seed0 = _seed0(N, salt)
-    env = VecEnv(N)
+    ext = int(sched["phase"] == 1)   # the explore draws can repeat a card: the extended record
+    env = VecEnv(N, extended=ext)
     views = env.reset(seed0, factions=_factions(N), opponent=opponent, agent_side=agent_side, max_steps=MAX_STEPS, deck_schedule=params)
     model = ScheduleVecEnvModel(seed0, params, factions=_factions(N), opponent=int(opponent == "expert"), agent_side=agent_side,
-                                max_steps=MAX_STEPS)
+                                max_steps=MAX_STEPS, extended=bool(ext))
     assert_views_equal(host_views(views), model.views, "reset")
     assert np.array_equal(env.state_hash(), model.hashes())
     assert np.array_equal(env.decks().cpu().numpy(), model.decks)
@@ -84,9 +87,9 @@ def test_decks_follow_the_schedule_across_a_generation_change():
     from monsoon_amd.vec_env import VecEnv
     first, second = standard_schedule(1, n_preserve=4, generation=33), standard_schedule(2, ratio=0.3, generation=71)
     seed0, stride = _seed0(N, 11), 1000003
-    env = VecEnv(N)
+    env = VecEnv(N, extended=1)
     views = env.reset(seed0, factions=_factions(N), opponent="expert", max_steps=MAX_STEPS, seed_stride=stride, deck_schedule=first)
-    model = ScheduleVecEnvModel(seed0, first, factions=_factions(N), opponent=1, max_steps=MAX_STEPS, seed_stride=stride)
+    model = ScheduleVecEnvModel(seed0, first, factions=_factions(N), opponent=1, max_steps=MAX_STEPS, seed_stride=stride, extended=True)
     rs = np.random.RandomState(5)
     by_old = by_new = kept = 0
     for t in range(36):
@@ -148,9 +151,9 @@ def test_captured_step_sees_the_new_schedule():
     from monsoon_amd.vec_env import VecEnv
     first, second = standard_schedule(0, generation=1), standard_schedule(1, n_preserve=2, generation=44)
     seed0 = _seed0(N, 31)
-    env = VecEnv(N)
+    env = VecEnv(N, extended=1)
     views = env.reset(seed0, factions=_factions(N), opponent="expert", max_steps=MAX_STEPS, deck_schedule=first)
-    model = ScheduleVecEnvModel(seed0, first, factions=_factions(N), opponent=1, max_steps=MAX_STEPS)
+    model = ScheduleVecEnvModel(seed0, first, factions=_factions(N), opponent=1, max_steps=MAX_STEPS, extended=True)
     s = env.stream
     actions = torch.zeros(N, dtype=torch.uint8, device="cuda")
     with torch.cuda.stream(s):   # warm-up outside the graph
@@ -190,7 +193,7 @@ def test_evolutionary_game_is_episode_0_of_its_slot():
     for generation in (1, 5, 10):   # exploit, explore, balance
         env = VecEnv(n, extended=1)
         views = env.reset(seed0, factions=facs, deck_schedule=dc, generation=generation)   # no opponent: the caller plays both sides
-        # on the env's record build: the standard and the extended record differ on decks that hold a card twice
+        # on the env's record build, which is the one a pair that repeats a card needs anyway
         games = [EvolutionaryGame(int(s), generation, dc, extended=1) for s in seed0]
         decks = env.decks().cpu().numpy()
         live = np.ones(n, dtype=bool)
@@ -220,10 +223,12 @@ def test_evolutionary_game_is_episode_0_of_its_slot():
         for g in games:
             g.close()
         env.close()
-    # left to itself the game picks the build by its decks: generation 5 draws ua20 for seed 424242, not for seed 7
-    for seed, ext in ((424242, 1), (7, 0)):
+    # left to itself the game picks the build by its decks (cards.needs_extended): generation 5 draws ua20 for seed 424242,
+    # a unit or structure twice in both decks and no ua20 for seed 7, neither for seed 3
+    for seed, ext, ua20, repeat in ((424242, 1, True, False), (7, 1, False, True), (3, 0, False, False)):
         g = EvolutionaryGame(seed, 5, dc)
-        assert int(g.env._eng.extended) == ext and ("ua20" in g.player1_deck + g.player2_deck) == bool(ext)
+        assert int(g.env._eng.extended) == ext and ("ua20" in g.player1_deck + g.player2_deck) == ua20
+        assert any(d.count(c) > 1 and c[0] != "s" for d in (g.player1_deck, g.player2_deck) for c in d) == repeat
         assert g.get_phase_info()["phase"] == "Explore"
         g.close()
     g = EvolutionaryGame(11)   # no config: the pair Stormbound plays
@@ -237,7 +242,7 @@ def test_restored_slot_draws_with_the_destinations_seed():
     params = standard_schedule(1, n_preserve=5, generation=37)
     n = 6
     seed0 = _seed0(n, 41)
-    env = VecEnv(n)
+    env = VecEnv(n, extended=1)
     views = env.reset(seed0, factions=_factions(n), opponent="expert", max_steps=MAX_STEPS, deck_schedule=params)
     views = env.step(_first_legal(torch, views["legal"]))
     src = int(torch.nonzero((views["episode"] == 0) & (views["winner"] == -2))[0])   # a slot in the middle of episode 0
@@ -286,7 +291,7 @@ def test_argument_errors():
     seed0 = _seed0(n, 51)
     pair = np.stack([deck_indices("IRONCLAD"), deck_indices("SWARM")])
     params = standard_schedule(1, n_preserve=6)
-    env = VecEnv(n)
+    env = VecEnv(n, extended=1)
     with pytest.raises(ValueError, match="decks and pool must be None"):
         env.reset(seed0, pair, deck_schedule=params)
     with pytest.raises(ValueError, match="decks and pool must be None"):

@@ -27,7 +27,7 @@ def _one_life(torch):
     from monsoon_amd.vec_env import VecEnv
     out = {}
     rs = np.random.RandomState(2024)
-    env = VecEnv(N)
+    env = VecEnv(N, extended=1)   # the explore schedule below can repeat a card: only the extended record takes it
     eng = env.engine
     deck = deck_indices("N12M")
     pairs = np.stack([np.stack([deck, deck]), np.stack([deck_indices(DECKS["IRONCLAD"]), deck_indices(DECKS["SWARM"])])])

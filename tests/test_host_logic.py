@@ -230,7 +230,8 @@ def test_recursion_guard_is_not_a_record_limit_and_strict_mode_raises():
     assert record_limited(np.array([18, 29, 28, 2], dtype=np.uint8)).tolist() == [False, True, True, False]
     m = np.zeros(4, dtype=MATCH_DTYPE)
     m["seed"] = np.arange(4)
-    pairs = np.zeros((1, 2, 12), dtype=np.uint8)
+    from monsoon_amd.cards import deck_indices
+    pairs = np.stack([deck_indices("N12M")] * 2)[None]   # a pair of the standard tier (twelve times one card is not: cards.needs_extended)
     calls = []
 
     def play(tier, sub, sub_pairs):
@@ -273,7 +274,8 @@ def test_work_stack_budget_code_is_reported_as_a_limit_and_never_as_the_guard():
     import monsoon_amd.fitness as F
     m = np.zeros(3, dtype=MATCH_DTYPE)
     m["seed"] = np.arange(3)
-    pairs = np.zeros((1, 2, 12), dtype=np.uint8)
+    from monsoon_amd.cards import deck_indices
+    pairs = np.stack([deck_indices("N12M")] * 2)[None]   # a pair of the standard tier (twelve times one card is not: cards.needs_extended)
     calls = []
 
     def play(tier, sub, sub_pairs):
