@@ -507,7 +507,8 @@ int monsoon_draw_schedule_time(monsoon_t* h, double* kernel_ms);
  * each child, out_tries[lambda] = polar-method rounds consumed up to and including that child (both optional).  Every
  * draw and every accept / reject decision is numpy's own, so the parents and the returned stream state (key, position,
  * has_gauss) are bit-identical to the host's; exp / log / sqrt are the device library's, within 1 ulp of the host's,
- * so weights and sigmas agree with the host's to a few ulp (tests/test_gpu_parity.py).
+ * so weights and sigmas agree with the host's to a few ulp (tests/test_gpu_parity.py; tests/test_ga_operators_gpu.py at mu
+ * that is no power of two, dim 1..16, clamped, infinite and NaN sigmas and every kind of state to enter with).
  *
  * monsoon_ga_select: the order of select_from_combined, evo/population.py:91-103: indices of all n individuals by
  * descending fitness, equal fitness in original order (Python's stable sort with reverse=True). */

@@ -905,10 +905,32 @@ def test_draw_decks_on_device_equals_numpy(engines, gold):
     assert np.array_equal(got, draw_random_decks_numpy(seeds))
     assert all(len(set(d.tolist())) == 12 for d in got.reshape(-1, 12))
     small = np.arange(12, dtype=np.uint8)   # a pool of exactly 12 cards: every draw is a permutation of it
-    assert np.array_equal(np.sort(eng.draw_decks(seeds[:50], small).reshape(-1, 12), axis=1), np.tile(small, (100, 1)))
+    got12 = eng.draw_decks(seeds[:50], small)
+    assert np.array_equal(np.sort(got12.reshape(-1, 12), axis=1), np.tile(small, (100, 1)))
+    assert np.array_equal(got12, draw_random_decks_numpy(seeds[:50], small))   # ... and the one numpy draws
     from monsoon_amd import MonsoonError
     with pytest.raises(MonsoonError):
         eng.draw_decks(seeds[:4], np.arange(11, dtype=np.uint8))   # fewer than 12 cards: refused
+
+
+def test_draw_decks_on_device_at_the_pool_sizes_that_move_the_mask(engines):
+    """monsoon_draw_decks against RandomState(seed).choice(pool, 12, replace=False) taken twice, drawn by numpy right here
+    (test_oracle_golden.draw_pool_cases: 64 seeds, 0, 1 and 2**32 - 1 among them, pool sizes on both sides of every power
+    of two from 12 to 128, where the mask of the shuffle's random_interval(i) changes).  A pool of 129 is refused, as one
+    of 11 is, and the handle draws the known answer afterwards."""
+    from monsoon_amd import MonsoonError
+    from test_oracle_golden import DRAW_POOL_SIZES, draw_pool_cases
+    eng = engines(64)
+    seen = []
+    for pool, seeds, want in draw_pool_cases():
+        got = eng.draw_decks(seeds, pool)
+        bad = np.nonzero((got != want).any(axis=(1, 2)))[0]
+        assert len(bad) == 0, f"pool of {len(pool)}: {len(bad)} of {len(seeds)} seeds differ, first {int(seeds[bad[0]])}: {got[bad[0]].tolist()} != {want[bad[0]].tolist()}"
+        seen.append(len(pool))
+    assert tuple(seen) == DRAW_POOL_SIZES
+    with pytest.raises(MonsoonError, match="status 1"):
+        eng.draw_decks(seeds[:4], np.arange(129, dtype=np.uint8) % 112)
+    assert np.array_equal(eng.draw_decks(seeds, pool), want)
 
 
 def test_mixed_schedule_is_tiered_per_game_and_equals_cpu_replay():

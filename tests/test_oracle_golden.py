@@ -307,6 +307,32 @@ def test_deck_draw_restatement_vs_numpy(gold):
     assert np.array_equal(oracle_draw_decks(seeds, observable_pool()), draw_random_decks_numpy(seeds))
 
 
+DRAW_POOL_SIZES = (12, 13, 16, 17, 32, 33, 64, 65, 127, 128)   # both sides of every power of two: the mask of random_interval(i) moves there
+
+
+def draw_pool_cases():
+    """(pool uint8[pool_n], seeds uint32[64], numpy's own pairs uint8[64][2][12]) per pool size of DRAW_POOL_SIZES; shared
+    with tests/test_gpu_parity.py."""
+    from monsoon_amd.cards import draw_random_decks_numpy
+    seeds = np.concatenate([np.array([0, 1, 0xFFFFFFFF], dtype=np.uint32),
+                            np.random.RandomState(12).randint(0, 1 << 32, size=61, dtype=np.uint64).astype(np.uint32)])
+    for pool_n in DRAW_POOL_SIZES:
+        pool = np.array([(5 + 37 * j) % 112 for j in range(pool_n)], dtype=np.uint8)
+        yield pool, seeds, draw_random_decks_numpy(seeds, pool)
+
+
+def test_deck_draw_restatement_at_the_pool_sizes_that_move_the_mask():
+    """orc_draw_decks against RandomState(seed).choice(pool, 12, replace=False) taken twice, drawn by numpy right here, for
+    64 seeds (0, 1 and 2**32 - 1 among them) at pool sizes on both sides of every power of two from 12 to 128; a pool of
+    exactly 12 is a permutation of it."""
+    from oracle_rollout import oracle_draw_decks
+    for pool, seeds, want in draw_pool_cases():
+        got = oracle_draw_decks(seeds, pool)
+        assert np.array_equal(got, want), len(pool)
+        if len(pool) == 12:
+            assert np.array_equal(np.sort(got.reshape(-1, 12), axis=1), np.tile(np.sort(pool), (128, 1)))
+
+
 def ulps(a, b):
     """Distance in units of the last place between float64 arrays (same sign assumed where it matters)."""
     a = np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
@@ -316,18 +342,25 @@ def ulps(a, b):
 
 def orc_ga(g, tag):
     """The oracle's restatement of Population.generate_offspring on fixture case `tag` -> (w, s, parent, tries, key, pos, has_gauss, gauss)."""
+    lam = int(g[f"{tag}_cfg"][1])
+    tau, taup, mins = (float(x) for x in g[f"{tag}_params"])
+    return orc_ga_arrays(g[f"{tag}_st0_key"], int(g[f"{tag}_st0_pos"][0]), int(g[f"{tag}_st0_pos"][1]), float(g[f"{tag}_st0_gauss"][0]),
+                         g[f"{tag}_pw"], g[f"{tag}_ps"], lam, tau, taup, mins)
+
+
+def orc_ga_arrays(key, pos, has_gauss, gauss, pw, ps, lam, tau, taup, mins):
+    """The same on arrays: the stream state to enter with, parents pw / ps [mu][dim], lam children."""
     import ctypes
 
     class St(ctypes.Structure):
         _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_int32), ("has_gauss", ctypes.c_int32), ("gauss", ctypes.c_double)]
     L = oracle_lib.lib()
-    mu, lam, dim = (int(x) for x in g[f"{tag}_cfg"])
-    tau, taup, mins = (float(x) for x in g[f"{tag}_params"])
     st = St()
-    key0 = np.ascontiguousarray(g[f"{tag}_st0_key"], dtype=np.uint32)   # kept alive across the memmove
+    key0 = np.ascontiguousarray(key, dtype=np.uint32)   # kept alive across the memmove
     ctypes.memmove(st.key, key0.ctypes.data, 624 * 4)
-    st.pos, st.has_gauss, st.gauss = int(g[f"{tag}_st0_pos"][0]), int(g[f"{tag}_st0_pos"][1]), float(g[f"{tag}_st0_gauss"][0])
-    pw, ps = np.ascontiguousarray(g[f"{tag}_pw"]), np.ascontiguousarray(g[f"{tag}_ps"])
+    st.pos, st.has_gauss, st.gauss = int(pos), int(has_gauss), float(gauss)
+    pw, ps = np.ascontiguousarray(pw, dtype=np.float64), np.ascontiguousarray(ps, dtype=np.float64)
+    mu, dim = pw.shape
     ow, osg = np.zeros((lam, dim)), np.zeros((lam, dim))
     par, tries = np.zeros(lam, dtype=np.int32), np.zeros(lam, dtype=np.int64)
     L.orc_ga_offspring.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
