@@ -104,7 +104,7 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
 // The look-ahead of the state column 0 holds, into entry row_ of o_ (a monsoon_env_after with K_ entries per row): game
 // g_'s record with the stream window at rng_ attached, v_par_ its image in registers, ls_ its legal set (rem is used up).
 // n_legal, the draw hint, the "before" features, then the passes; column 0 is a candidate's afterwards.  For the whole
-// wave, where b, pe, ce, priv and L are what after_slot calls so.  Spelled in place like MSB_EACH_GRANULE, for after_slot
+// wave, where b, pe, ce and L are what after_slot calls so.  Spelled in place like MSB_EACH_GRANULE, for after_slot
 // and replay_game (replay_log.h): as a function template it reordered k_env_after's code object (scripts/isa_diff.sh).
 #if MSB_AFTER_OBS_COOP
 #define MSB_AFTER_OBS_(o_, K_, row_, lane_)                                                                                                           \
@@ -113,7 +113,7 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
       for (int c = 0; c < n_act; c++) {                                                                                                               \
         if (!((part >> c) & 1)) continue;   /* (uniform) */                                                                                           \
         typename L::SubEngine se;                                                                                                                     \
-        se.m.c16 = c * 16;                                                                                                                            \
+        se.m.set_col(c);                                                                                                                              \
         MSB_OBS_DECK_ORDER(se, lane_, ord)   /* (its first barrier: the order of the candidate before has been read) */                               \
         int32_t* out = o_.obs + (row_ * K_ + base + c) * MONSOON_OBS_INTS;                                                                            \
         for (int i = lane_; i < MONSOON_OBS_INTS; i += 64) out[i] = obs_word(se, i, ord);                                                             \
@@ -145,7 +145,7 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
     const int n_act = n_do - base < U ? n_do - base : U;                                                                                              \
     {   /* clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use */                        \
       __syncthreads();                                                                                                                                \
-      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane_, priv[gr_ * U + col] = v_par_[j_])                                         \
+      for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane_, *L::gran(col, gr_) = v_par_[j_])                                        \
       __syncthreads();                                                                                                                                \
     }                                                                                                                                                 \
     const bool active = lane_ < n_act;                                                                                                                \
@@ -192,7 +192,7 @@ __device__ MSB_INL int32_t obs_word(const E& e, const int i, const MSB_AS_LDS ui
 // The afterstates of slot g by the calling wavefront; K = max_after.  Call with the whole wave.
 template <int U>
 __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after& o, const int K, const int g, const int lane) {
-  typedef PlayLds<U> L;
+  typedef PlayLds<U, PLAY_LDS_COLUMNS_AFTER> L;
   const GameMeta meta = b.meta[g];
   uint8_t* const act_row = o.action + (size_t)g * K;
   if (meta.result != -2) {   // the episode ended before the agent could act: the next step reports it
@@ -200,7 +200,6 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
     for (int k = lane; k < K; k += 64) act_row[k] = 255;
     return;
   }
-  MSB_AS_LDS u32x4* priv = L::priv();
   const u32x4* grec = (const u32x4*)(b.state + (size_t)g * SW);
   u32x4 v_par[L::GPL];   // granules lane, lane + 64, ... of the slot's record
   _Pragma("unroll") for (int j_ = 0; j_ < L::GPL; j_++) v_par[j_] = u32x4{0u, 0u, 0u, 0u};
@@ -208,11 +207,11 @@ __device__ MSB_INL void after_slot(const DevBuffers& b, const monsoon_env_after&
   typename L::ParEngine pe;
   typename L::CandEngine ce;
   // stage: the image of the record in column 0; with the stream window attached it is what the clones start from
-  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
+  MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
   __syncthreads();
   if (lane == 0) attach_rng(pe, b, g, meta.rng);
   __syncthreads();
-  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = *L::gran(0, gr_))
 
   LegalSet ls = legal_set(pe);
   MSB_AFTER_STATE(o, K, (size_t)g, g, meta.rng, ls, v_par, lane)

@@ -14,9 +14,12 @@
 //     there for up to `rounds` decisions: a record is SG granules of 16 bytes, and lane l keeps granules l, l + 64, ...
 //     of the current record (v_par) and of the best successor found so far in this decision (v_best) -- one granule =
 //     four VGPRs each on the standard record.  Per decision: up to U candidate actions are advanced at once, lane l
-//     stepping its own private copy of the state in LDS.  The private copies are interleaved across lanes in 16-byte
-//     granules (granule c of lane l at (c*U + l)*16), so lanes touching the same field hit distinct LDS banks and a
-//     whole entity is one ds_read_b128; cloning is U 16-byte LDS writes per lane straight from registers.  The
+//     stepping its own private copy of the state in LDS.  On the standard record every private copy is one
+//     contiguous column, STATE_BYTES apart (752 = -16 mod 128: lanes touching the same field hit distinct LDS
+//     banks, and a field's address is the lane's column base plus an offset); the extended and the large record, and on
+//     the standard record k_play_vs, k_play_log, k_play_explore and k_env_after (PLAY_LDS_COLUMNS_BOT / _AFTER below), keep the copies
+//     interleaved across lanes in 16-byte granules (granule c of lane l at (c*U + l)*16).  Both maps: lds_layout.h.  A whole entity is one
+//     ds_read_b128; cloning is U 16-byte LDS writes per lane straight from registers, lane l carrying granule l.  The
 //     functions that read the current record (end of game, legal mask, features, stream cursor) find its image in
 //     candidate column 0, written there from the registers before they run (Col0Mem, state.h).  Scores are reduced
 //     with shuffles over the U candidate lanes (first maximum in ascending action order = np.argmax over the sorted
@@ -209,7 +212,8 @@ constexpr int LDS_ORIGIN = LDS_RECORDS;
 // ------------------------------------------------------------------------------------------------
 // Hot kernel: a wavefront takes a game, keeps its record in registers and plays up to `rounds` decisions of it
 // (look-ahead + score + argmax + commit each) before it writes the record back and takes the next game.
-// Dynamic LDS map (bytes): weight table | [PRIV, +SG*U*16) candidate records, lane-interleaved in 16-byte granules
+// Dynamic LDS map (bytes): weight table | [PRIV, +SG*U*16) candidate records -- standard record: column c is the
+// contiguous [PRIV + c*STATE_BYTES, +STATE_BYTES); extended records: lane-interleaved in 16-byte granules; PlayLds::Map
 // (column 0 doubles as the image of the current record, the whole area as the twist buffer) |
 // 10 weights + 10 "before" + 10 "best after" features | the candidates' work stacks (SKW words each, interleaved word by
 // word), which hold their "after" features once a pass has stepped
@@ -223,7 +227,27 @@ __device__ MSB_INL unsigned long long uni64(unsigned long long v) {   // a wave-
 // The pieces of a decision's look-ahead, named once per U: the LDS map, the engines, which forms the build uses, and the
 // steps of a decision that work on LDS and scalars.  play_game (below) and after_slot (env_after.h) compose them; a new
 // consumer of the look-ahead does too.
-template <int U>
+template <bool COLS, class Columns, class Interleaved>
+struct LdsPick {
+  typedef Columns T;
+};
+template <class Columns, class Interleaved>
+struct LdsPick<false, Columns, Interleaved> {
+  typedef Interleaved T;
+};
+// COLS: the candidate records' map.  A kernel takes the build's (PLAY_LDS_COLUMNS) unless it is one of the four that came
+// out of the compiler larger on columns than on the interleave on the standard record, which keep the interleave there
+// (profiles/lds_columns_isa_diff.txt: k_play_vs and k_play_log a private segment of 16 bytes more, k_play_explore and
+// k_env_after one and three scratch instructions more; none of them is on the path bench.py measures).  On the large
+// record, were it built on columns (state.h MSB_LDS_COLUMNS_LARGE), every kernel shrank: they would all take them.
+#if defined(MSB_EXT) && MSB_EXT == 2
+constexpr bool LARGE_RECORD = true;
+#else
+constexpr bool LARGE_RECORD = false;
+#endif
+constexpr bool PLAY_LDS_COLUMNS_BOT = PLAY_LDS_COLUMNS && LARGE_RECORD;     // k_play_vs, k_play_log, k_play_explore (play_game<.., VS, !SAMPLE>)
+constexpr bool PLAY_LDS_COLUMNS_AFTER = PLAY_LDS_COLUMNS && LARGE_RECORD;   // k_env_after (after_slot)
+template <int U, bool COLS_ = PLAY_LDS_COLUMNS>
 struct PlayLds {
   static constexpr int PRIV = LDS_ORIGIN;
   static constexpr int PRIV_BYTES = SG * U * 16 > MT_N * 4 ? SG * U * 16 : ((MT_N * 4 + 15) & ~15);   // doubles as the twist buffer
@@ -231,9 +255,16 @@ struct PlayLds {
   static constexpr int SKB = WF + 240;               // work stacks of the U candidate lanes ...
   static constexpr int CF = SKB;                     // ... and, once a pass has stepped (stacks empty), their ten "after" features each (f64)
   static constexpr int TOTAL = SKB + U * SKW * 4;
-  typedef Engine<Col0Mem<U, PRIV>> ParEngine;               // the current record: candidate column 0
-  typedef Engine<LaneMem<U, PRIV, SKB, SKW>> CandEngine;    // candidate `lane`'s private copy
-  typedef Engine<SubColMem<U, PRIV>> SubEngine;             // candidate (lane % U)'s record, read only: the wave-cooperative features
+  // The candidate records' map (lds_layout.h): a contiguous column each where the record's size keeps the columns off each
+  // other's banks, the 16-byte interleave elsewhere (state.h PLAY_LDS_COLUMNS).  Both fill exactly SG * U * 16 bytes: TOTAL
+  // is the same for either.
+  static constexpr bool COLS = COLS_;
+  typedef lds_layout::RecordMap<U, PRIV, STATE_BYTES, COLS> Map;
+  static_assert(Map::AREA <= PRIV_BYTES && Map::granule(U - 1, SG - 1) + 16 == PRIV + Map::AREA, "the records lie inside the candidate area");
+  template <class Columns, class Interleaved> using Pick = typename LdsPick<COLS, Columns, Interleaved>::T;
+  typedef Engine<Pick<Col0ColMem<U, PRIV>, Col0Mem<U, PRIV>>> ParEngine;                           // the current record: candidate column 0
+  typedef Engine<Pick<LaneColMem<U, PRIV, SKB, SKW>, LaneMem<U, PRIV, SKB, SKW>>> CandEngine;      // candidate `lane`'s private copy
+  typedef Engine<Pick<SubColColMem<U, PRIV>, SubColMem<U, PRIV>>> SubEngine;   // candidate (lane % U)'s record, read only: the wave-cooperative features
   static constexpr int GPL = (SG + 63) / 64;   // granules of a record per lane
   // Features by the whole wave (coop_features.h) where a candidate has sub-lanes to spare, on the standard record.  The
   // extended records keep the serial form: with 2 x 12 VGPRs of record per lane next to the phase's temporaries the
@@ -245,7 +276,12 @@ struct PlayLds {
 #else
   static constexpr bool COOP_DRAW = false;
 #endif
-  static __device__ MSB_INL MSB_AS_LDS u32x4* priv() { return (MSB_AS_LDS u32x4*)(uintptr_t)PRIV; }   // granule c of column l: priv()[c * U + l]
+  static __device__ MSB_INL MSB_AS_LDS u32x4* priv() { return (MSB_AS_LDS u32x4*)(uintptr_t)PRIV; }   // the area as the twist buffer
+  // Granule g of candidate column c: what every whole-wave move of a record reads and writes, by the accessors' own map.
+  static __device__ MSB_INL MSB_AS_LDS u32x4* gran(const int c, const int g) {
+    if constexpr (COLS) return (MSB_AS_LDS u32x4*)(uintptr_t)Map::granule(c, g);
+    else return priv() + (g * U + c);   // (RecordMap<.., false>::granule, spelled as the interleaved accessors spell it)
+  }
   static __device__ MSB_INL MSB_AS_LDS double* wf() { return (MSB_AS_LDS double*)(uintptr_t)WF; }
   // What the first draw of this decision's REPLACE steps (actions 148..151) will find, into DRAW_HINT_LDS (coop_draw.h);
   // the candidates read it after the next barrier, wherever in the passes they sit.  A decision without such a
@@ -271,7 +307,7 @@ struct PlayLds {
     const int col = sl % U;
     const bool on = (part >> col) & 1;
     SubEngine se;
-    se.m.c16 = col * 16;
+    se.m.set_col(col);
     MSB_AS_LDS double* cfc = (MSB_AS_LDS double*)(uintptr_t)(dst + col * 80);
     coop_features<U>(se, sl, on, cfc);
     return cfc;
@@ -308,7 +344,7 @@ __device__ MSB_INL LegalSet legal_set(E& pe) {
 
 // Lane `lane_`'s share of a record: granules lane_, lane_ + 64, ... (gr_), the j_-th of them in element j_ of a register
 // array u32x4[GPL_].  The moves of a record between HBM, registers and the candidate columns are spelled with it in
-// place -- load: v[j_] = grec[gr_]; column c: priv[gr_ * U + c] -- and not as functions: handed the register array by
+// place -- load: v[j_] = grec[gr_]; column c: *L::gran(c, gr_) -- and not as functions: handed the register array by
 // reference, pointer, value or lambda capture, a function cost k_play<8,5> up to 16 bytes of scratch.
 #define MSB_EACH_GRANULE(GPL_, lane_, body_)            \
   _Pragma("unroll") for (int j_ = 0; j_ < GPL_; j_++) { \
@@ -510,7 +546,7 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
 // second time.
 #define MSB_COMMIT_BEST()                                                                           \
   __syncthreads();                                                                                  \
-  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_best[j_])                                                      \
+  MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_best[j_])                                                      \
   __syncthreads();                                                                                  \
   {                                                                                                 \
     uint32_t new_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pe.rng_pos());                 \
@@ -518,7 +554,7 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
     if (new_pos >= (uint32_t)MT_N) {                                                                \
       new_pos -= MT_N;                                                                              \
       wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);                                     \
-      MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_best[j_])                                                  \
+      MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_best[j_])                                                  \
       __syncthreads();                                                                              \
       cur ^= 1;                                                                                     \
       if (lane == 0) pe.rng_block_advance();                                                        \
@@ -528,7 +564,7 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
     have_before = feat_ok != 0;                                                                     \
     if (have_before && lane < 10) wf[10 + lane] = wf[20 + lane];                                    \
     __syncthreads();                                                                                \
-    MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])                                                     \
+    MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = *L::gran(0, gr_))                                                     \
   }
 // EXPLORE: candidate lane wl_ of this pass is what the commit takes -- its fault, its feature flag and features, its record.
 #define MSB_TAKE_LANE(wl_)                                                                          \
@@ -536,14 +572,14 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
   feat_ok = __builtin_amdgcn_readlane(my_feat, wl_);                                                \
   if (feat_ok && lane < 10) wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl_ * 10 + lane]; \
   __syncthreads();                                                                                  \
-  MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl_])
+  MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(wl_, gr_))
 template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false, bool SAMPLE = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
                                   ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr, const PlaySample* const sp = nullptr) {
   static_assert(!EXPLORE || (LOG && !ENV) || (ENV && !VS && !LOG), "the exploring form is a logging rollout or the env's opponent");
   static_assert(!SAMPLE || (LOG && !ENV && !EXPLORE), "the sampling form is a logging rollout with a rule of its own");
-  typedef PlayLds<U> L;
+  typedef PlayLds<U, (VS && !SAMPLE) ? PLAY_LDS_COLUMNS_BOT : PLAY_LDS_COLUMNS> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
   if (meta.result != -2) {
@@ -565,11 +601,11 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
   typename L::ParEngine pe;
   typename L::CandEngine ce;
   // stage: the image of the current record in column 0; with the stream window attached it is also what the clones start from
-  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
+  MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
   __syncthreads();
   if (lane == 0) attach_rng(pe, b, g, meta.rng);
   __syncthreads();
-  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = priv[gr_ * U])
+  MSB_EACH_GRANULE(L::GPL, lane, v_par[j_] = *L::gran(0, gr_))
   bool have_before = false;   // wf[10..19] holds the features of the CURRENT state (the committed successor's)
   double last_score = NAN;
   int played = 0;
@@ -607,7 +643,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         a = __builtin_amdgcn_readfirstlane(a);
         f = __builtin_amdgcn_readfirstlane(f);
         fs = __builtin_amdgcn_readfirstlane(fs);
-        MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U])   // the successor (if the bot raised: the record with its cursor moved on)
+        MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(0, gr_))   // the successor (if the bot raised: the record with its cursor moved on)
         constexpr int feat_ok = 0;   // the bot's successor has no features: the next decision computes its "before" side
         MSB_COMMIT_BEST()
         if (!f) {   // one committed transition, no decision, no look-ahead
@@ -677,7 +713,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       const int n_act = n_legal - base < U ? n_legal - base : U;   // (uniform) the candidates of this pass: lanes 0 .. n_act-1
       {   // clone: copy.deepcopy (stream window included) for the whole pass, lane l writes granule l of every column in use
         __syncthreads();
-        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, *L::gran(col, gr_) = v_par[j_])
         __syncthreads();
       }
       const bool active = lane < n_act;
@@ -694,7 +730,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
         if (active) ce.step(a);
 #endif
         __syncthreads();
-        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U + col] = v_par[j_])
+        for (int col = 0; col < n_act; col++) MSB_EACH_GRANULE(L::GPL, lane, *L::gran(col, gr_) = v_par[j_])
         __syncthreads();
       }
 #endif
@@ -779,7 +815,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           if (feat_ok && lane < 10)   // the winner keeps its features: the next decision's "before" side
             wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl * 10 + lane];
           __syncthreads();
-          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U + wl])   // the best successor so far, into registers
+          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(wl, gr_))   // the best successor so far, into registers
         } else if (xt->r < 0) {   // (a decision that explores moves the two scalars only: its v_best is the explored lane's, below)
           const int wl = __ffsll((long long)__ballot(a == ca)) - 1;
           MSB_TAKE_LANE(wl)
@@ -802,7 +838,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
     if constexpr (SAMPLE) {
       // column 0 is the current record again: the rule asks whose turn it is, and a sampled action is stepped from it
       __syncthreads();
-      MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_par[j_])
+      MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
       __syncthreads();
       uint32_t draw1, total = 0u, taken_w = 0u;
       const bool on = sample_draw(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
@@ -826,7 +862,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           __syncthreads();
           cfault = __builtin_amdgcn_readfirstlane(fs);
           feat_ok = 0;   // the next decision computes its "before" side
-          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = priv[gr_ * U])
+          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(0, gr_))
         }
       }
       log_explore(ex, lg, g, lane, meta.steps, run_a, on, take_s);   // (greedy = the arg-max; run_s stays the decision's best score)

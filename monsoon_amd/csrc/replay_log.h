@@ -80,7 +80,7 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
   typename L::ParEngine pe;
   typename L::CandEngine ce;   // (lane 0's is column 0 with a work stack)
   // stage: the record in column 0, the stream window attached
-  MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_rec[j_])
+  MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_rec[j_])
   __syncthreads();
   if (lane == 0) {
     attach_rng(pe, b, g, meta.rng);
@@ -115,7 +115,7 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
         // attached) waits in registers and is staged again before lane 0 steps it, so the look-ahead consumes nothing --
         // cursor, stream blocks and meta are the committed ones.  The draw hint it sets is cleared again: the committed
         // REPLACE and the bot draw serially.  (replay_row's order has left the stack area behind the look-ahead's barriers.)
-        MSB_EACH_GRANULE(L::GPL, lane, v_rec[j_] = priv[gr_ * U])
+        MSB_EACH_GRANULE(L::GPL, lane, v_rec[j_] = *L::gran(0, gr_))
         if (chosen && lane == 0) {   // the rank of a in the ascending legal list (PASS may be outside it)
           const int rank = __popcll(word & ((1ull << (a & 63)) - 1)) + (a >= 64 ? __popcll(ls.mask[0]) : 0) + (a >= 128 ? __popcll(ls.mask[1]) : 0);
           chosen[r] = (int16_t)(((word >> (a & 63)) & 1) ? rank : -1);
@@ -125,7 +125,7 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
         MSB_AFTER_STATE(oa, K, r, g, meta.rng, la, v_rec, lane)
         meta.lookahead += (uint32_t)(ls.n < K ? ls.n : K);   // the candidates stepped; no decision is counted
         __syncthreads();   // the last pass's successors have been read out of the columns
-        MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_rec[j_])
+        MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_rec[j_])
         if constexpr (L::COOP_DRAW) {
           if (lane == 0) *(MSB_AS_LDS uint32_t*)(uintptr_t)DRAW_HINT_LDS = 0u;
         }
@@ -155,10 +155,10 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
       int cur = (meta.rng >> 16) & 1;
       if (new_pos >= (uint32_t)MT_N) {
         new_pos -= MT_N;
-        MSB_EACH_GRANULE(L::GPL, lane, v_rec[j_] = priv[gr_ * U])
+        MSB_EACH_GRANULE(L::GPL, lane, v_rec[j_] = *L::gran(0, gr_))
         __syncthreads();
         wave_refill(b, g, cur, (MSB_AS_LDS uint32_t*)priv, lane);
-        MSB_EACH_GRANULE(L::GPL, lane, priv[gr_ * U] = v_rec[j_])
+        MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_rec[j_])
         __syncthreads();
         cur ^= 1;
         if (lane == 0) pe.rng_block_advance();
@@ -192,7 +192,7 @@ __device__ MSB_INL void replay_game(const DevBuffers& b, const ReplayArgs& ra, c
     meta.flags |= 1;
   }
   __syncthreads();
-  MSB_EACH_GRANULE(L::GPL, lane, grec[gr_] = priv[gr_ * U])
+  MSB_EACH_GRANULE(L::GPL, lane, grec[gr_] = *L::gran(0, gr_))
   if (lane == 0) {
     b.meta[g] = meta;
     ra.status[g] = (uint8_t)status;

@@ -2,9 +2,11 @@
 //
 // One record = STATE_BYTES bytes (a whole number of 16-byte granules), every field naturally aligned.  In HBM a
 // batch of games is stored record-major: the hot kernel gives a wavefront to a game, so one game's record is one
-// coalesced 16-bytes-per-lane read.  Inside a kernel a record lives in LDS; the candidate copies of a decision are
-// interleaved across the lanes of the wave in 16-byte granules (granule c of lane l at (c*LANES + l)*16): lanes
-// touching the same field hit different banks, and an entity (one granule) is a single ds_read_b128.
+// coalesced 16-bytes-per-lane read.  Inside a kernel a record lives in LDS, in one of the two maps of lds_layout.h: the
+// lane-per-game kernels interleave their records across the lanes of the wave in 16-byte granules (granule c of lane l at
+// (c*LANES + l)*16), the candidate copies of a decision of the wavefront-per-game kernels are one contiguous column each
+// where the record's size allows it (PLAY_LDS_COLUMNS below).  Either way lanes touching the same field hit different
+// banks, and an entity (one granule) is a single ds_read_b128.
 //
 // What the fields restate (reference file:line):
 //   header      games/stormbound.py:304 (player), board.py:20-25 (current_player, history, triggers,
@@ -16,6 +18,7 @@
 //               units on its trigger stack, so a tile grid alone cannot reproduce it.
 #pragma once
 #include "msb_base.h"
+#include "lds_layout.h"
 
 namespace msb {
 
@@ -236,6 +239,28 @@ constexpr int X_BYTES = REM_LISTS ? (X_TRIGSRC - OFF_X) + (TRIG_WIDE ? 4 : 0) : 
 constexpr int STATE_BYTES = (OFF_X + X_BYTES + 15) & ~15;   // whole 16-byte granules
 static_assert(NUM_ENT <= 254 && (!TRIG_WIDE || REM_LISTS), "slot ids are bytes; 0xFE and 0xFF are markers");
 constexpr int STATE_WORDS = STATE_BYTES / 4;
+// How the wavefront-per-game kernels (kernels.h PlayLds) lay their candidate records out in LDS (lds_layout.h): one
+// contiguous column per record on the standard record, whose 752 bytes = -16 (mod 128) keep 8 columns off each other's
+// banks, and the 16-byte interleave on the other two.  The extended record's 2 400 bytes are 96 (mod 128), so columns k and
+// k + 4 would share banks on every 4-byte access, and the 16 bytes of padding that would mend it cost the extended tier
+// its eighth wavefront per CU.  The large record's 8 336 bytes = +16 (mod 128) would pass the rule and its kernels compile
+// smaller on columns, but the workloads that reach it did not separate from the parent when it was built so
+// (profiles/lds_columns_ab.txt): it moves only with an A/B that shows no loss;
+// -DMSB_LDS_COLUMNS_LARGE=1 builds it on columns for that.  -DMSB_LDS_COLUMNS=0 builds the interleave everywhere.
+#ifndef MSB_LDS_COLUMNS
+#define MSB_LDS_COLUMNS 1
+#endif
+#ifndef MSB_LDS_COLUMNS_LARGE
+#define MSB_LDS_COLUMNS_LARGE 0
+#endif
+#if !(defined(MSB_EXT) && MSB_EXT)
+constexpr bool PLAY_LDS_COLUMNS = MSB_LDS_COLUMNS;
+#elif MSB_EXT == 2
+constexpr bool PLAY_LDS_COLUMNS = MSB_LDS_COLUMNS && MSB_LDS_COLUMNS_LARGE;
+#else
+constexpr bool PLAY_LDS_COLUMNS = false;
+#endif
+static_assert(!PLAY_LDS_COLUMNS || lds_layout::stride_conflict_free(STATE_BYTES), "columns need a record of +-16 bytes (mod 128)");
 constexpr int EF_OWNER = 1, EF_FF = 2, EF_RESOLVING_PLAY = 4, EF_SINGLE_USE = 8;
 typedef uint32_t msb_u32x4 __attribute__((vector_size(16)));
 
@@ -339,10 +364,17 @@ MSB_HD MSB_INL void lds_init_wtab(uint32_t* wk_ovf = nullptr) {
   }
   __syncthreads();
 }
-// LDS image of one record, interleaved across the lanes of a wave in 16-BYTE granules: granule c of
-// lane l sits at (c*LANES + l)*16.  A lane's record is copied 16 bytes at a time (ds_read_b128 /
-// ds_write_b128, conflict-free: consecutive lanes touch consecutive 16-byte slots), f64 weights are one
-// ds_read_b64, and with 8 lanes per game a same-field access by all lanes still hits 8 distinct banks.
+// LDS image of one record among LANES of them.  Two families of accessors, one per map of lds_layout.h:
+//   LaneMem / Col0Mem / SubColMem: interleaved across the lanes of a wave in 16-BYTE granules, granule c of lane l at
+//     (c*LANES + l)*16 (RecordMap<.., false>, spelled in place here).  Consecutive lanes touch consecutive 16-byte slots
+//     whatever the record's size, f64 weights are one ds_read_b64, an entity one ds_read_b128.  The lane-per-game kernels
+//     (k_step, k_env_step, k_init, k_legal, k_observe, ...) use it -- with 64 lanes per wave a contiguous record per lane
+//     would conflict no less -- and so do the wavefront-per-game kernels where PLAY_LDS_COLUMNS is false.  An offset the
+//     compiler does not know pays the shift, mask and scale of b().
+//   LaneColMem / Col0ColMem / SubColColMem (below them): record l is the contiguous column [BASE + l*STATE_BYTES,
+//     + STATE_BYTES) (RecordMap<.., true>, called).  b(o) is one add, the constant part of o sits in the instruction's offset
+//     field, and the 8 candidate lanes of the standard record, 752 bytes = -16 (mod 128) apart, still hit 8 distinct bank
+//     groups at every width.  The whole-wave moves of a record (kernels.h PlayLds::gran) go through the same map.
 //
 // The accessors are STATELESS: the kernels use only dynamic LDS, so the image starts at LDS address
 // BASE (a compile-time constant) and the lane is the work-item id.  An Engine over such an accessor is an
@@ -449,7 +481,7 @@ struct Col0Mem {
   MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }
   MSB_HD MSB_INL static void ovf_st(int, uint32_t) {}
 };
-// One column of a lane-interleaved image, chosen per lane by the caller (c16 = column * 16), READ ONLY: how the sub-lanes of a
+// One column of a lane-interleaved image, chosen per lane by the caller (set_col), READ ONLY: how the sub-lanes of a
 // candidate (lanes c, c + LANES, c + 2*LANES, ... of the wave) all see candidate c's record in the wave-cooperative features
 // (coop_features.h).  It has loads only: an Engine over it can inspect a record and nothing else.  Unlike its stateless
 // neighbours it carries the column offset: a value the caller derives where it is used, so that the address arithmetic is not
@@ -457,6 +489,7 @@ struct Col0Mem {
 template <int LANES, int BASE>
 struct SubColMem {
   int c16;
+  MSB_HD MSB_INL void set_col(int column) { c16 = column * 16; }
   MSB_HD MSB_INL MSB_AS_LDS const uint8_t* b(int o) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)(BASE + (o >> 4) * (LANES * 16) + (o & 15) + c16); }
   MSB_HD MSB_INL MSB_AS_LDS const uint8_t* gb(int g, int k) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)(BASE + g * (LANES * 16) + k + c16); }
   MSB_HD MSB_INL int ld8(int o) const { return *b(o); }
@@ -472,6 +505,85 @@ struct SubColMem {
   MSB_HD MSB_INL double ldfg(int g, int k) const { return *(MSB_AS_LDS const double*)gb(g, k); }
   MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
 };
+
+// The column forms of the three: record c is the contiguous column c of lds_layout::RecordMap<LANES, BASE, STATE_BYTES, true>,
+// and every address is that map's.  The loads and stores are the neighbours' own, over this b() / gb(); Q_ is `static` or
+// empty, C_ is empty or `const` (the sub-lane view carries its column and only loads).
+#define MSB_LDS_LOADS(Q_, C_)                                                                                          \
+  MSB_HD MSB_INL Q_ int ld8(int o) C_ { return *b(o); }                                                                \
+  MSB_HD MSB_INL Q_ int ld16(int o) C_ { return *(MSB_AS_LDS const int16_t*)b(o); }                                    \
+  MSB_HD MSB_INL Q_ uint32_t ld32(int o) C_ { return *(MSB_AS_LDS const uint32_t*)b(o); }                              \
+  MSB_HD MSB_INL Q_ double ldf(int o) C_ { return *(MSB_AS_LDS const double*)b(o); }                                   \
+  MSB_HD MSB_INL Q_ uint64_t ld64(int o) C_ { return *(MSB_AS_LDS const uint64_t*)b(o); }                              \
+  MSB_HD MSB_INL Q_ msb_u32x4 ld128(int o) C_ { return *(MSB_AS_LDS const msb_u32x4*)b(o); }                           \
+  MSB_HD MSB_INL Q_ int ld8g(int g, int k) C_ { return *gb(g, k); }                                                    \
+  MSB_HD MSB_INL Q_ int ld16g(int g, int k) C_ { return *(MSB_AS_LDS const int16_t*)gb(g, k); }                        \
+  MSB_HD MSB_INL Q_ msb_u32x4 ld128g(int g) C_ { return *(MSB_AS_LDS const msb_u32x4*)gb(g, 0); }                      \
+  MSB_HD MSB_INL Q_ uint32_t ld32g(int g, int k) C_ { return *(MSB_AS_LDS const uint32_t*)gb(g, k); }                  \
+  MSB_HD MSB_INL Q_ double ldfg(int g, int k) C_ { return *(MSB_AS_LDS const double*)gb(g, k); }                       \
+  MSB_HD MSB_INL static double wtab(int age) { return lds_wtab(age); }
+#define MSB_LDS_STORES()                                                                                               \
+  MSB_HD MSB_INL static void st8(int o, int v) { *b(o) = (uint8_t)v; }                                                 \
+  MSB_HD MSB_INL static void st16(int o, int v) { *(MSB_AS_LDS int16_t*)b(o) = (int16_t)v; }                           \
+  MSB_HD MSB_INL static void st32(int o, uint32_t v) { *(MSB_AS_LDS uint32_t*)b(o) = v; }                              \
+  MSB_HD MSB_INL static void stf(int o, double v) { *(MSB_AS_LDS double*)b(o) = v; }                                   \
+  MSB_HD MSB_INL static void st64(int o, uint64_t v) { *(MSB_AS_LDS uint64_t*)b(o) = v; }                              \
+  MSB_HD MSB_INL static void st128(int o, msb_u32x4 v) { *(MSB_AS_LDS msb_u32x4*)b(o) = v; }                           \
+  MSB_HD MSB_INL static void st8g(int g, int k, int v) { *gb(g, k) = (uint8_t)v; }                                     \
+  MSB_HD MSB_INL static void st16g(int g, int k, int v) { *(MSB_AS_LDS int16_t*)gb(g, k) = (int16_t)v; }               \
+  MSB_HD MSB_INL static void st128g(int g, msb_u32x4 v) { *(MSB_AS_LDS msb_u32x4*)gb(g, 0) = v; }                      \
+  MSB_HD MSB_INL static void st32g(int g, int k, uint32_t v) { *(MSB_AS_LDS uint32_t*)gb(g, k) = v; }                  \
+  MSB_HD MSB_INL static void stfg(int g, int k, double v) { *(MSB_AS_LDS double*)gb(g, k) = v; }
+// This lane's private column.  The work stack, its eviction block, the draw hint and the (absent) ability log are LaneMem's:
+// the stacks stay interleaved word by word behind the records.
+template <int LANES, int BASE, int SKB = 0, int SKW_ = 0>
+struct LaneColMem {
+  typedef lds_layout::RecordMap<LANES, BASE, STATE_BYTES, true> Map;
+  typedef LaneMem<LANES, BASE, SKB, SKW_> Stack;
+  static constexpr int SKW = SKW_;
+  MSB_HD MSB_INL static uint32_t ovf_ld(int i) { return Stack::ovf_ld(i); }
+  MSB_HD MSB_INL static void ovf_st(int i, uint32_t v) { Stack::ovf_st(i, v); }
+  MSB_HD MSB_INL static uint32_t sk_ld(int i) { return Stack::sk_ld(i); }
+  MSB_HD MSB_INL static void sk_st(int i, uint32_t v) { Stack::sk_st(i, v); }
+  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* b(int o) {
+    return (MSB_AS_LDS uint8_t*)(uintptr_t)Map::byte_at(Map::col_off((int)__builtin_amdgcn_workitem_id_x()), o);
+  }
+  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* gb(int g, int k) {
+    return (MSB_AS_LDS uint8_t*)(uintptr_t)Map::gbyte_at(Map::col_off((int)__builtin_amdgcn_workitem_id_x()), g, k);
+  }
+  MSB_LDS_LOADS(static, )
+  MSB_LDS_STORES()
+  MSB_HD MSB_INL static uint32_t draw_hint() { return Stack::draw_hint(); }
+  MSB_HD MSB_INL static void trace_ability(int, int) {}
+};
+// Column 0, addressed by every lane alike (Col0Mem's role).
+template <int LANES, int BASE>
+struct Col0ColMem {
+  typedef lds_layout::RecordMap<LANES, BASE, STATE_BYTES, true> Map;
+  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* b(int o) { return (MSB_AS_LDS uint8_t*)(uintptr_t)Map::byte_at(0, o); }
+  MSB_HD MSB_INL static MSB_AS_LDS uint8_t* gb(int g, int k) { return (MSB_AS_LDS uint8_t*)(uintptr_t)Map::gbyte_at(0, g, k); }
+  MSB_LDS_LOADS(static, )
+  MSB_LDS_STORES()
+  MSB_HD MSB_INL static uint32_t draw_hint() { return 0u; }
+  MSB_HD MSB_INL static void trace_ability(int, int) {}
+  static constexpr int SKW = SK_CAP;   // (nothing is stepped through it)
+  MSB_HD MSB_INL static uint32_t sk_ld(int) { return 0; }
+  MSB_HD MSB_INL static void sk_st(int, uint32_t) {}
+  MSB_HD MSB_INL static uint32_t ovf_ld(int) { return 0; }
+  MSB_HD MSB_INL static void ovf_st(int, uint32_t) {}
+};
+// One column chosen per lane by the caller (set_col), READ ONLY (SubColMem's role): it carries the column's offset.
+template <int LANES, int BASE>
+struct SubColColMem {
+  typedef lds_layout::RecordMap<LANES, BASE, STATE_BYTES, true> Map;
+  int coff;
+  MSB_HD MSB_INL void set_col(int column) { coff = Map::col_off(column); }
+  MSB_HD MSB_INL MSB_AS_LDS const uint8_t* b(int o) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)Map::byte_at(coff, o); }
+  MSB_HD MSB_INL MSB_AS_LDS const uint8_t* gb(int g, int k) const { return (MSB_AS_LDS const uint8_t*)(uintptr_t)Map::gbyte_at(coff, g, k); }
+  MSB_LDS_LOADS(, const)
+};
+#undef MSB_LDS_LOADS
+#undef MSB_LDS_STORES
 #endif
 
 template <class A, class B>
