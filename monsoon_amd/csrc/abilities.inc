@@ -14,6 +14,9 @@
 
 MSB_HD MSB_INL PList sel_targets(int shape, P c, int pov, Tgt t) { return shape_targets(shape, c, pov, t, PK_NONE); }
 
+// len(<selector>(.., target)) > 0
+MSB_HD MSB_INL bool sel_any(int shape, P c, int pov, Tgt t) { return shape_any(shape, c, pov, t); }
+
 // [tile for tile in <raw shape tiles> if board.at(tile) is None]
 MSB_HD MSB_A_TILES PList empty_shape_tiles(int shape, P c, int pov) {
   PList raw = shape_tiles(shape, c, pov);

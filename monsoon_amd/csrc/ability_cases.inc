@@ -265,20 +265,17 @@ MSB_CARD(C_U050,  // cards/u050.py:13-15
       break;
 )
 MSB_CARD(C_U051, {  // cards/u051.py:14-21
-      l = sel_targets(SH_BORDERING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY));
-      if (l.n() == 0)
+      if (!sel_any(SH_BORDERING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY)))
         gain_speed(e, 1);
       else
         heal(e, 2);
     } break;
 )
 MSB_CARD(C_U053, {  // cards/u053.py:14-24
-      l = sel_targets(SH_SURROUNDING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY));
-      if (l.n() == 0) {
+      if (!sel_any(SH_SURROUNDING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY))) {
         gain_speed(e, 2);
       } else {
-        l = sel_targets(SH_BORDERING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY));
-        if (l.n() == 0) gain_speed(e, 1);
+        if (!sel_any(SH_BORDERING, mypos, dpov, mk_tgt(TK_UNIT, TS_ANY))) gain_speed(e, 1);
       }
     } break;
 )
@@ -341,8 +338,7 @@ MSB_CARD(C_U103, {  // cards/u103.py:12-19
     } break;
 )
 MSB_CARD(C_U106, {  // cards/u106.py:13-18
-      l = sel_targets(SH_BORDERING, mypos, dpov, mk_tgt(TK_STRUCTURE, TS_FRIENDLY));
-      if (l.n() > 0 || mypos.y == 4) heal(e, 7);
+      if (sel_any(SH_BORDERING, mypos, dpov, mk_tgt(TK_STRUCTURE, TS_FRIENDLY)) || mypos.y == 4) heal(e, 7);
     } break;
 )
 MSB_CARD(C_U111, {  // cards/u111.py:13-21
@@ -531,8 +527,7 @@ MSB_CARD(C_UA07, {  // cards/ua07.py:11-22
     } break;
 )
 MSB_CARD(C_UA20, {  // cards/ua20.py:21-32 (needs the extended record's deck capacity)
-      l = sel_targets(SH_FRONT, mypos, me, mk_tgt(TK_UNIT, TS_ENEMY));
-      if (l.n() == 0) {
+      if (!sel_any(SH_FRONT, mypos, me, mk_tgt(TK_UNIT, TS_ENEMY))) {
         const int cand[4] = {C_B005, C_B006, C_B203, C_B305};
         int c = cand[rng_randint(0, 4)];
         // copy(); cost = 0; weight = 1; is_single_use = True; deck.append(card)

@@ -1137,11 +1137,11 @@ struct Engine {
     const int side = tg_side(t);
     return ((side == TS_FRIENDLY || side == TS_ANY) ? 1 : 0) | ((side == TS_ENEMY || side == TS_ANY) ? 2 : 0);
   }
-  // Pass 1 of get_targets: visit only the occupied tiles and collect the matching ones as a tile bit mask (the board is
-  // read as five 32-bit rows; one 16-byte LDS read per entity).
-  MSB_HD MSB_INL uint32_t get_targets_hit(const int pov, const Tgt t) const {
+  // Pass 1 of get_targets: visit only the occupied tiles among `tiles` and collect the matching ones as a tile bit mask
+  // (the board is read as five 32-bit rows; one 16-byte LDS read per entity visited).
+  MSB_HD MSB_INL uint32_t get_targets_hit(const int pov, const Tgt t, const uint32_t tiles = 0xFFFFFu) const {
     const uint32_t r0 = board_row(0), r1 = board_row(1), r2 = board_row(2), r3 = board_row(3), r4 = board_row(4);
-    uint32_t occ = row_occ4(r0) | (row_occ4(r1) << 4) | (row_occ4(r2) << 8) | (row_occ4(r3) << 12) | (row_occ4(r4) << 16);
+    uint32_t occ = (row_occ4(r0) | (row_occ4(r1) << 4) | (row_occ4(r2) << 8) | (row_occ4(r3) << 12) | (row_occ4(r4) << 16)) & tiles;
     const unsigned long long b01 = (unsigned long long)r0 | ((unsigned long long)r1 << 32);
     const unsigned long long b23 = (unsigned long long)r2 | ((unsigned long long)r3 << 32);
     uint32_t hit = 0;
@@ -1155,32 +1155,55 @@ struct Engine {
     }
     return hit;
   }
-  MSB_HD MSB_A_TARGETS PList get_targets_impl(int pov, Tgt t, int exclude_pk) {
-    MSB_SCOPE(PS_GET_TARGETS);
-    PList out;
-    out.clear();
-    const bool asc = (pov == local());
-    uint32_t hit = get_targets_hit(pov, t);
-    // Pass 2 emits them in iteration order:
-    // ascending tiles for the local point of view, descending for the remote one (board.py:160-166)
-    {
-      unsigned long long w0 = 0, w1 = 0;
-      int n = 0;
-      while (hit) {
-        const int tile = asc ? __builtin_ctz(hit) : 31 - __builtin_clz(hit);
-        hit &= ~(1u << tile);
-        const unsigned long long v = (unsigned long long)((((tile >> 2) + 1) << 3) | ((tile & 3) + 1));   // p_pack(tile_p(tile))
-        if (n < 10) w0 |= v << (6 * n);
-        else w1 |= v << (6 * (n - 10));
-        n++;
-      }
-      out.w = msb_u64x4{w0, w1, 0ull, (unsigned long long)n};
+  // Pass 2 emits the tiles of `hit` in iteration order:
+  // ascending tiles for the local point of view, descending for the remote one (board.py:160-166)
+  MSB_HD MSB_INL static PList hit_list(uint32_t hit, const bool asc) {
+    unsigned long long w0 = 0, w1 = 0;
+    int n = 0;
+    while (hit) {
+      const int tile = asc ? __builtin_ctz(hit) : 31 - __builtin_clz(hit);
+      hit &= ~(1u << tile);
+      const unsigned long long v = (unsigned long long)((((tile >> 2) + 1) << 3) | ((tile & 3) + 1));   // p_pack(tile_p(tile))
+      if (n < 10) w0 |= v << (6 * n);
+      else w1 |= v << (6 * (n - 10));
+      n++;
     }
+    PList out;
+    out.w = msb_u64x4{w0, w1, 0ull, (unsigned long long)n};
+    return out;
+  }
+  // The two base points behind the tiles: the point of view's own first (board.py:196-203)
+  MSB_HD MSB_INL static P base_point(const bool friendly, const bool asc) { return friendly == asc ? P{-1, 5} : P{-1, -1}; }
+  // `exclude` of get_targets as what it removes from the list: the tile's bit of the scan, or a base
+  MSB_HD MSB_INL static void exclude_point(const int exclude_pk, const bool asc, uint32_t& tiles, int& bases) {
+    if (exclude_pk == PK_NONE) return;
+    const P x = p_unpack(exclude_pk);
+    if (p_valid(x)) tiles &= ~(1u << p_tile(x));
+    else if (exclude_pk < 64 && p_is_base(x)) bases &= ~((x.y == 5) == asc ? 1 : 2);
+  }
+  MSB_HD MSB_A_TARGETS PList get_targets_impl(int pov, Tgt t, int exclude_pk) {
+#if MSB_TARGET_SCAN
+    MSB_SCOPE(PS_GET_TARGETS);
+    const bool asc = (pov == local());
+    uint32_t tiles = 0xFFFFFu;
+    int bases = target_bases(t);
+    exclude_point(exclude_pk, asc, tiles, bases);
+    PList out = hit_list(get_targets_hit(pov, t, tiles), asc);
+    if (bases & 1) out.push(base_point(true, asc));
+    if (bases & 2) out.push(base_point(false, asc));
+    return out;
+#else
+    return get_targets_full(pov, t, exclude_pk);
+#endif
+  }
+  // -DMSB_TARGET_SCAN=0: the exclusion by searching the finished list
+  MSB_HD MSB_INL PList get_targets_full(int pov, Tgt t, int exclude_pk) {
+    MSB_SCOPE(PS_GET_TARGETS);
+    const bool asc = (pov == local());
+    PList out = hit_list(get_targets_hit(pov, t), asc);
     if (const int bases = target_bases(t)) {
-      P friendly = asc ? P{-1, 5} : P{-1, -1};
-      P enemy = asc ? P{-1, -1} : P{-1, 5};
-      if (bases & 1) out.push(friendly);
-      if (bases & 2) out.push(enemy);
+      if (bases & 1) out.push(base_point(true, asc));
+      if (bases & 2) out.push(base_point(false, asc));
     }
     if (exclude_pk != PK_NONE) {
       int m = out.n();
@@ -1191,6 +1214,30 @@ struct Engine {
         }
     }
     return out;
+  }
+  // Questions about a target list that need no list (-DMSB_TARGET_SCAN=0: asked of the list).
+  // get_targets(pov, t).n() > 0
+  MSB_HD MSB_INL bool targets_any(const int pov, const Tgt t) {
+#if MSB_TARGET_SCAN
+    MSB_SCOPE(PS_GET_TARGETS);
+    return target_bases(t) != 0 || get_targets_hit(pov, t) != 0;
+#else
+    return get_targets_full(pov, t, PK_NONE).n() > 0;
+#endif
+  }
+  // get_targets(pov, t).has(p): the predicate on one tile's entity, or the descriptor's bases
+  MSB_HD MSB_INL bool target_has(const int pov, const Tgt t, const P p) {
+#if MSB_TARGET_SCAN
+    MSB_SCOPE(PS_GET_TARGETS);
+    if (p_valid(p)) {
+      const int s = board_at(p_tile(p));
+      return s != SLOT_NONE && target_matches(m.ld128g(eg(s)), pov, t);
+    }
+    if (!p_is_base(p)) return false;
+    return (target_bases(t) & ((p.y == 5) == (pov == local()) ? 1 : 2)) != 0;
+#else
+    return get_targets_full(pov, t, PK_NONE).has(p);
+#endif
   }
 
   // membership of `p` in the raw tile list of a geometric selector (board.py:206-296)
@@ -1259,34 +1306,90 @@ struct Engine {
     }
     return out;
   }
-  // ... WITH a target: get_targets order filtered by membership; front/behind re-sorted by y.
+  // The tiles of a geometric selector as a 20-bit mask (bit y*4+x), in plain integer code: bit p_tile(p) is set exactly
+  // where in_shape(shape, c, pov, p) holds, for any centre.
+  MSB_HD MSB_INL static uint32_t rows_below(int y) { return (1u << (4 * (y < 0 ? 0 : (y > 5 ? 5 : y)))) - 1u; }   // tiles with p.y < y
+  MSB_HD MSB_INL static uint32_t cols_below(int x) { return ((1u << (x < 0 ? 0 : (x > 4 ? 4 : x))) - 1u) * 0x11111u; }   // tiles with p.x < x
+  MSB_HD MSB_INL static uint32_t row_tiles(int y) { return rows_below(y + 1) & ~rows_below(y); }
+  MSB_HD MSB_INL static uint32_t col_tiles(int x) { return cols_below(x + 1) & ~cols_below(x); }
+  MSB_HD MSB_INL uint32_t shape_mask(const int shape, const P c, const int pov) const {
+    const bool loc = (pov == local());
+    switch (shape) {
+      case SH_FRONT: return col_tiles(c.x) & (loc ? rows_below(c.y) : 0xFFFFFu & ~rows_below(c.y + 1));
+      case SH_BEHIND: return col_tiles(c.x) & (loc ? 0xFFFFFu & ~rows_below(c.y + 1) : rows_below(c.y));
+      case SH_SIDE: return row_tiles(c.y) & (col_tiles(c.x - 1) | col_tiles(c.x + 1));
+      case SH_ROW: return row_tiles(c.y);
+      case SH_COLUMN: return col_tiles(c.x);
+      case SH_BORDERING: return (row_tiles(c.y) & (col_tiles(c.x - 1) | col_tiles(c.x + 1))) | (col_tiles(c.x) & (row_tiles(c.y - 1) | row_tiles(c.y + 1)));
+      default: return (rows_below(c.y + 2) & ~rows_below(c.y - 1)) & (cols_below(c.x + 2) & ~cols_below(c.x - 1)) & ~(row_tiles(c.y) & col_tiles(c.x));
+    }
+  }
+  // which selectors keep a descriptor's bases (board.py:206-296)
+  MSB_HD MSB_INL static bool shape_base_rule(const int shape) {
+    return shape == SH_FRONT || shape == SH_BEHIND || shape == SH_COLUMN || shape == SH_BORDERING || shape == SH_SURROUNDING;
+  }
+  // stable sort by y of a front / behind list; reverse=True keeps equal keys in original order too (CPython list.sort)
+  MSB_HD MSB_INL static void sort_by_y(PList& out, const bool desc) {
+    int on = out.n();
+    for (int i = 1; i < on; i++) {
+      int k = out.get(i);
+      int ky = p_unpack(k).y;
+      int j = i - 1;
+      while (j >= 0 && (desc ? p_unpack(out.get(j)).y < ky : p_unpack(out.get(j)).y > ky)) {
+        out.set(j + 1, out.get(j));
+        j--;
+      }
+      out.set(j + 1, k);
+    }
+  }
+  // ... WITH a target: get_targets order filtered by membership; front/behind re-sorted by y.  The scan visits the
+  // selector's own tiles only.
   MSB_HD MSB_A_SHAPE PList shape_targets(int shape, P c, int pov, Tgt t, int exclude_pk) {
-    PList all = get_targets(pov, t, exclude_pk);
+#if MSB_TARGET_SCAN
+    MSB_SCOPE(PS_GET_TARGETS);
+    const bool asc = (pov == local());
+    uint32_t tiles = shape_mask(shape, c, pov);
+    int bases = target_bases(t);
+    exclude_point(exclude_pk, asc, tiles, bases);
+    PList out = hit_list(get_targets_hit(pov, t, tiles), asc);
+    if (bases) {
+      const bool rule = shape_base_rule(shape);
+      if ((bases & 1) && (rule || in_shape(shape, c, pov, base_point(true, asc)))) out.push(base_point(true, asc));
+      if ((bases & 2) && (rule || in_shape(shape, c, pov, base_point(false, asc)))) out.push(base_point(false, asc));
+    }
+    if (shape == SH_FRONT || shape == SH_BEHIND) sort_by_y(out, (shape == SH_FRONT) ? asc : !asc);
+    return out;
+#else
+    return shape_targets_full(shape, c, pov, t, exclude_pk);
+#endif
+  }
+  // -DMSB_TARGET_SCAN=0: the whole board's list, filtered
+  MSB_HD MSB_INL PList shape_targets_full(int shape, P c, int pov, Tgt t, int exclude_pk) {
+    PList all = get_targets_full(pov, t, exclude_pk);
     PList out;
     out.clear();
-    bool base_rule = (shape == SH_FRONT || shape == SH_BEHIND || shape == SH_COLUMN || shape == SH_BORDERING ||
-                      shape == SH_SURROUNDING);
+    bool base_rule = shape_base_rule(shape);
     int m = all.n();
     for (int i = 0; i < m; i++) {
       P p = all.at(i);
       if (in_shape(shape, c, pov, p) || (base_rule && p_is_base(p) && tg_base(t))) out.push_raw(all.get(i));
     }
-    if (shape == SH_FRONT || shape == SH_BEHIND) {
-      // stable sort by y; reverse=True keeps equal keys in original order too (CPython list.sort)
-      bool desc = (shape == SH_FRONT) ? (pov == local()) : (pov == remote());
-      int on = out.n();
-      for (int i = 1; i < on; i++) {
-        int k = out.get(i);
-        int ky = p_unpack(k).y;
-        int j = i - 1;
-        while (j >= 0 && (desc ? p_unpack(out.get(j)).y < ky : p_unpack(out.get(j)).y > ky)) {
-          out.set(j + 1, out.get(j));
-          j--;
-        }
-        out.set(j + 1, k);
-      }
-    }
+    if (shape == SH_FRONT || shape == SH_BEHIND) sort_by_y(out, (shape == SH_FRONT) ? (pov == local()) : (pov == remote()));
     return out;
+  }
+  // shape_targets(shape, c, pov, t, PK_NONE).n() > 0
+  MSB_HD MSB_INL bool shape_any(const int shape, const P c, const int pov, const Tgt t) {
+#if MSB_TARGET_SCAN
+    MSB_SCOPE(PS_GET_TARGETS);
+    if (get_targets_hit(pov, t, shape_mask(shape, c, pov)) != 0) return true;
+    const int bases = target_bases(t);
+    if (!bases) return false;
+    const bool asc = (pov == local());
+    return shape_base_rule(shape) || ((bases & 1) && in_shape(shape, c, pov, base_point(true, asc))) ||
+           ((bases & 2) && in_shape(shape, c, pov, base_point(false, asc)));
+#else
+    return shape_targets_full(shape, c, pov, t, PK_NONE).n() > 0;
+#endif
   }
 
   // numpy RandomState.choice(list) / shuffle(list)
@@ -2243,10 +2346,9 @@ struct Engine {
     bool go = true;
     if (ci.tgt.has) {
       Tgt t = mk_tgt(ci.tgt);
-      PList l = get_targets(cp(), t, PK_NONE);
-      go = has_pos && l.has(position);
+      go = has_pos && target_has(cp(), t, position);   // position in get_targets(..)
       // `None in [Point...]` evaluates Point.__eq__(None) -> AttributeError when the list is non-empty
-      if (!has_pos && l.n() > 0) {
+      if (!has_pos && targets_any(cp(), t)) {
         set_fault(FAULT_PY_EXCEPTION);
         return;
       }

@@ -185,7 +185,13 @@ constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
 #ifndef MSB_COOP_LEGAL
 #define MSB_COOP_LEGAL 1
 #endif
-constexpr int LDS_RECORDS = WK_OVF_LDS + 16;         // first LDS byte the kernels may use for records
+// Target scans inside a step that read only the tiles their caller keeps (rules.h shape_targets, shape_any, targets_any,
+// target_has): every record build.  0 builds the full-board scan and the point list everywhere; both texts are always
+// compiled (the *_full forms), tests/target_scan_check.cpp holds one against the other.
+#ifndef MSB_TARGET_SCAN
+#define MSB_TARGET_SCAN 1
+#endif
+constexpr int LDS_RECORDS = WK_OVF_LDS + 16;        // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
 // a handler runs, everything below the top frame is EVICTED to the workgroup's block in HBM and comes back when the
