@@ -677,6 +677,46 @@ int monsoon_env_set_opponent_explore(monsoon_t* h, const monsoon_env_explore* ex
  * MONSOON_ERR_STATE without a loaded env or when the env has no rule, MONSOON_ERR_ARG for a NULL out_dev. */
 int monsoon_env_opponent_explored_dev(monsoon_t* h, void* out_dev);
 
+/* Softmax heuristic opponents, a temperature per slot: monsoon_env_set_opponent_explore's rule for WHEN a decision leaves
+ * its arg-max, monsoon_rollout_sample's rule for WHAT it then commits.
+ *
+ * WHEN.  Word for word the rule above: with k, s, draw0 and draw1 as defined there, a decision of slot i's opponent over
+ * n_legal >= 1 actions SAMPLES when (until_step <= 0 || k < until_step) and draw0 < thresholds[i].
+ * WHAT.  monsoon_rollout_sample's x_j, w_j, total, r and j* with the slot's own inverse temperature: over the ascending
+ * legal list, x_j = (score_j - best) * inv_temperature[i], w_j = weight24(x_j), total = sum w_j,
+ * r = ((uint64_t)draw1 * total) >> 32, and j* the smallest j whose inclusive prefix sum exceeds r; the decision commits
+ * action j*.  Ties share the probability: an action tied with the arg-max weighs 2**24 as it does and may be committed
+ * instead of it.  total == 0 (best is NaN or infinite) commits the arg-max and still counts as explored.
+ * The arg-max runs over all candidates as ever.  The choice is known only after the last look-ahead, so a decision that
+ * samples an action other than its arg-max steps that action once more from the parent record (bit-identical to its
+ * look-ahead: the clone carries the stream window); that successor's fault or raising observation ends the episode by the
+ * env's rules exactly as for the arg-max winner.  monsoon_debug_counters word 16 keeps counting n_legal per decision: A
+ * DECISION THAT SAMPLED ANOTHER ACTION THAN ITS ARG-MAX EXECUTES ONE STEP MORE THAN IT COUNTS.  No draw touches the game's
+ * numpy stream.  The 64-decision guard (fault 28) is unchanged.  A rewind samples exactly as the first run did; a fork into
+ * slots with other seed0 samples differently per slot; two slots with equal seed0 and inverse temperature share their choices.
+ *
+ * WHICH KERNEL PLAYS.  The handle holds at most ONE opponent rule, uniform (monsoon_env_set_opponent_explore) or sampling
+ * (this call): while no opponent-2 env is loaded either call replaces whatever rule is held.  Which of the three kernels --
+ * plain, exploring, sampling -- plays the opponent is settled at monsoon_env_reset by the rule the handle then holds, and
+ * never changes under a captured step (still seven launches on one stream).
+ * DEVICE BUFFERS.  The inverse temperatures live beside the thresholds, in the buffer that the first call of either setter
+ * allocates for max_games slots and that is never moved.  The kernel parks every decision's scores in the slot's row of the
+ * handle's score table ([max_games][156] doubles, monsoon_decide's), which the first call allocates if monsoon_decide has
+ * not and which is never moved either; only the sampling kernel is handed it.  A call validates, copies behind everything
+ * already enqueued on the handle's stream and synchronises; it holds from the next decision on, also under a captured step.
+ * All thresholds 0 plays the plain env bit for bit.  monsoon_env_opponent_explored_dev counts the decisions whose draw said
+ * "sample" and serves both kinds.
+ *
+ * thresholds: HOST uint32[n]; inv_temperature: HOST double[n], 1 / T of slot i.  ex == NULL clears the rule (the other
+ * arguments are not read).
+ * MONSOON_ERR_ARG with nothing launched: whatever monsoon_env_set_opponent_explore refuses, a NULL inv_temperature with a
+ * non-NULL ex, an entry that is NaN, infinite or <= 0.
+ * MONSOON_ERR_STATE, for this call and for monsoon_env_set_opponent_explore alike: a non-NULL ex while an opponent-2 env
+ * is loaded that was reset under the OTHER kind of rule or under no rule; ex == NULL while an env that uses the rule is
+ * loaded. */
+int monsoon_env_set_opponent_sample(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds,
+                                    const double* inv_temperature, int32_t n);
+
 /* Schedule mode: the third source of episode decks, beside the reset decks and the pool.  The handle keeps ONE deck schedule
  * in a device buffer that is allocated by the first call and never moved while an env is loaded.  monsoon_env_reset with
  * decks == NULL and pool_n == 0 plays schedule mode if the handle holds a schedule (MONSOON_ERR_ARG otherwise); with decks

@@ -182,6 +182,8 @@ SIGNATURES = {
     "monsoon_env_set_opponents": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_env_set_opponent_explore": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvExplore), ctypes.c_void_p, ctypes.c_int32]),
     "monsoon_env_opponent_explored_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "monsoon_env_set_opponent_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(EnvExplore), ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_int32]),
     "monsoon_env_set_schedule": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DeckSchedule)]),
     "monsoon_env_decks_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "monsoon_env_reseed_time": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),

@@ -45,10 +45,18 @@ struct EnvOppOps : KernelOps {
 const EnvOppOps* monsoon_env_opp_ops();
 
 // k_env_opp_explore<U, W> (env_opp_explore.hip): the same turn, epsilon-greedy by the rule the handle holds
-// (kernels.h EnvExplore).  The host picks one of the two tables at monsoon_env_reset.
+// (kernels.h EnvExplore).  The host picks one of the tables at monsoon_env_reset.
 struct EnvOppExploreOps : KernelOps {
   void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list, EnvExplore ee);
 };
 const EnvOppExploreOps* monsoon_env_opp_explore_ops();
+
+// k_env_opp_sample<U, W> (env_opp_sample.hip): the same turn, sampling from the softmax over a decision's scores by the rule
+// the handle holds (kernels.h EnvSample); b.scores is the handle's score table.  The host picks one of the three tables at
+// monsoon_env_reset.
+struct EnvOppSampleOps : KernelOps {
+  void (*launch)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, EnvDev v, int list, EnvSample es);
+};
+const EnvOppSampleOps* monsoon_env_opp_sample_ops();
 
 }  // namespace msbk

@@ -516,6 +516,29 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
   }
 }
 
+// What play_game<U, true, false, false, false, true> needs beyond the EnvPolicy (k_env_opp_sample, env_opp_sample.hip;
+// include/monsoon.h monsoon_env_set_opponent_sample): the EnvExplore of the rule -- WHEN a decision leaves its arg-max is
+// env_explore_rank's conditions word for word -- and the slots' inverse temperatures, device words like the thresholds.  An
+// argument of that kernel alone; play_game sees it through its EnvExplore pointer, so no other form gains an argument.
+struct EnvSample : EnvExplore {
+  const double* inv_temperature;   // [n]: slot g's opponent weighs with inv_temperature[g] (finite, > 0)
+};
+// sample_draw for slot g's opponent at committed step k of its episode: does the decision leave its arg-max, and with which
+// draw1 and inverse temperature.  Every word is loaded anew and is wave-uniform (readfirstlane; the double as two halves).
+__device__ MSB_INL bool env_sample_draw(const EnvSample& es, const int g, const int k, const int n_legal, uint32_t& draw1, double& inv_t) {
+  draw1 = 0u;
+  inv_t = 0.0;
+  const int until_step = __builtin_amdgcn_readfirstlane((int)es.rule[1]);
+  if ((until_step > 0 && k >= until_step) || n_legal <= 0) return false;
+  const uint32_t seed = (uint32_t)__builtin_amdgcn_readfirstlane((int)es.rule[0]);
+  const uint32_t threshold = (uint32_t)__builtin_amdgcn_readfirstlane((int)es.thresholds[g]);
+  const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(es.seed0[g] + (uint32_t)es.episode[g] * es.stride));
+  if (explore_hash32(seed, s, (uint32_t)k, 0u) >= threshold) return false;
+  draw1 = explore_hash32(seed, s, (uint32_t)k, 1u);
+  inv_t = __longlong_as_double((long long)uni64((unsigned long long)__double_as_longlong(es.inv_temperature[g])));
+  return true;
+}
+
 // Up to `rounds` decisions of game g by the calling wavefront.  The record lives in registers from the first decision
 // to the last; HBM sees one read and one write of it per call.
 // ENV = false: the rollout (k_play).  ENV = true: the vector env's opponent turn -- it stops when the agent's side is to
@@ -531,12 +554,14 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
 // the r-th legal action (xt->r) instead of the arg-max.  Everything new is wave-uniform: the pass that holds rank r takes
 // lane r - base -- its record into v_best, its fault and feature flag, its features into wf[20..29], its score -- and on
 // such a decision the running arg-max moves run_a / run_s only, so v_best is written exactly once, in whichever pass.
-// SAMPLE = true (k_play_sample, play_sample.hip; with LOG = true and EXPLORE = false): the passes run as without a rule --
+// SAMPLE = true (k_play_sample, play_sample.hip, with LOG = true; k_env_opp_sample, env_opp_sample.hip, with ENV = true, the
+// draw of env_sample_draw and the slot's inverse temperature from `ee`, an EnvSample; EXPLORE = false): the passes run as without a rule --
 // the arg-max and its record in v_best -- and every candidate's score also goes to the game's row of b.scores.  After the
 // last pass a decision whose draw says so (sample_draw) draws an action from the softmax over those scores (sample_pick)
 // and, unless that is the arg-max, steps it once more from the parent record on column 0 (the clone carries the stream
 // window, so the step is the look-ahead's bit for bit): that successor, its fault and no features are what the commit takes.
-// The decision's scalars live and die in that one block in front of the commit; `sp` is the kernel's.
+// The decision's scalars live and die in that one block in front of the commit; `sp` is the kernel's.  The env's form logs
+// nothing: lane 0 counts the decision in ee->explored, and the commit, the end rules and the 64-decision guard are ENV's.
 //
 // MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
@@ -578,7 +603,8 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
                                   const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
                                   ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr, const PlaySample* const sp = nullptr) {
   static_assert(!EXPLORE || (LOG && !ENV) || (ENV && !VS && !LOG), "the exploring form is a logging rollout or the env's opponent");
-  static_assert(!SAMPLE || (LOG && !ENV && !EXPLORE), "the sampling form is a logging rollout with a rule of its own");
+  static_assert(!SAMPLE || (!EXPLORE && ((LOG && !ENV) || (ENV && !VS && !LOG))),
+                "the sampling form is a logging rollout with a rule of its own or the env's opponent");
   typedef PlayLds<U, (VS && !SAMPLE) ? PLAY_LDS_COLUMNS_BOT : PLAY_LDS_COLUMNS> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -841,13 +867,21 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
       __syncthreads();
       uint32_t draw1, total = 0u, taken_w = 0u;
-      const bool on = sample_draw(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
-                                  meta.steps, n_legal, draw1);
+      double slot_inv_t = 0.0;   // (ENV: the slot's own, read with the draw)
+      bool on;
+      if constexpr (ENV)
+        on = env_sample_draw(*static_cast<const EnvSample*>(ee), g, meta.steps, n_legal, draw1, slot_inv_t);
+      else
+        on = sample_draw(ex, (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
+                         meta.steps, n_legal, draw1);
       int take = run_a;
       double take_s = run_s;
       if (on) {   // (uniform)
         const double* row = b.scores + (size_t)g * MONSOON_NUM_ACTIONS;   // this decision's scores: the barriers above made them visible
-        const SamplePick pk = sample_pick(row, ls.mask[0], ls.mask[1], ls.mask[2], run_s, sp->inv_temperature, draw1, lane);
+        double inv_t;
+        if constexpr (ENV) inv_t = slot_inv_t;
+        else inv_t = sp->inv_temperature;
+        const SamplePick pk = sample_pick(row, ls.mask[0], ls.mask[1], ls.mask[2], run_s, inv_t, draw1, lane);
         total = pk.total;   // (0: the best score is NaN or infinite, the decision commits its arg-max)
         taken_w = pk.w;
         if (pk.total && pk.pos != run_a) {   // (the arg-max's record is in v_best already: nothing to step)
@@ -865,8 +899,12 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
           MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(0, gr_))
         }
       }
-      log_explore(ex, lg, g, lane, meta.steps, run_a, on, take_s);   // (greedy = the arg-max; run_s stays the decision's best score)
-      log_sample(*sp, lg, g, lane, meta.steps, total, taken_w);
+      if constexpr (ENV) {   // the env counts the slot's decisions whose draw said "sample", as k_env_opp_explore does
+        if (on && lane == 0) atomicAdd(&ee->explored[g], 1u);
+      } else {
+        log_explore(ex, lg, g, lane, meta.steps, run_a, on, take_s);   // (greedy = the arg-max; run_s stays the decision's best score)
+        log_sample(*sp, lg, g, lane, meta.steps, total, taken_w);
+      }
       run_a = take;
     }
     MSB_COMMIT_BEST()

@@ -757,6 +757,11 @@ struct monsoon {
   int opp_ex_n = 0;                     // slots the held rule has thresholds for, 0 = the handle holds no rule
   bool env_explore = false;             // the loaded opponent-2 env was reset with a rule: its steps launch k_env_opp_explore
   EnvExplore env_ex = {};               // ... with this argument
+  // the sampling kind of that rule (monsoon_env_set_opponent_sample): the handle holds at most one rule, uniform or sampling
+  double* d_opp_inv_t = nullptr;        // [max_games]: inside d_opp_ex's allocation, behind the thresholds
+  bool opp_ex_sample = false;           // the held rule samples (meaningful while opp_ex_n != 0)
+  bool env_sample = false;              // env_explore, and the rule the env was reset with samples: its steps launch k_env_opp_sample
+  EnvSample env_es = {};                // ... with this argument
   int after_grid = 0;         // k_env_after's grid (monsoon_env_afterstates_dev), likewise
   int after_waves = 0;        // resident wavefronts of k_env_after (queried once per handle)
   int snap_blocks = 0;        // resident workgroups of k_env_save / k_env_load (queried once per handle)
@@ -2348,7 +2353,11 @@ static int launch_env_opp(monsoon_t* h, int n, int list) {
   ob.weights = h->d_opp_w;
   ob.scores = nullptr;
   ob.best = nullptr;
-  if (h->env_explore) {   // (settled at monsoon_env_reset: a captured step never changes kernels)
+  if (h->env_sample) {   // (settled at monsoon_env_reset, like the next one: a captured step never changes kernels)
+    const EnvOppSampleOps* o = monsoon_env_opp_sample_ops();
+    ob.scores = h->b.scores;   // where this kernel alone parks a decision's scores
+    o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list, h->env_es);
+  } else if (h->env_explore) {
     const EnvOppExploreOps* o = monsoon_env_opp_explore_ops();
     o->launch(h->opp_grid, o->lds_bytes, h->stream, ob, h->env, list, h->env_ex);
   } else {
@@ -2390,38 +2399,67 @@ int monsoon_env_set_opponents(monsoon_t* h, const double* weights, int32_t n_ind
 // The rule's words and thresholds reach the device behind everything enqueued on the handle's stream; the kernel reads
 // them at every decision, so they hold from the next decision on, also under a captured step.
 constexpr int OPP_EX_RULE_WORDS = 16;   // thresholds start 64 bytes behind the rule's two words
-int monsoon_env_set_opponent_explore(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds, int32_t n) {
+// Where the inverse temperatures start inside d_opp_ex: behind the thresholds of max_games slots, 8-byte aligned.
+static size_t opp_ex_inv_t_at(const monsoon_t* h) { return (((size_t)OPP_EX_RULE_WORDS + (size_t)h->cfg.max_games) * 4 + 7) & ~(size_t)7; }
+// Both kinds of the opponent's rule (the handle holds at most one): inv_temperature null = the uniform rule of
+// monsoon_env_set_opponent_explore, else the sampling rule of monsoon_env_set_opponent_sample.
+static int env_set_opponent_rule(monsoon_t* h, const char* fn, bool sample, const monsoon_env_explore* ex, const uint32_t* thresholds,
+                                 const double* inv_temperature, int32_t n) {
   if (!h) return MONSOON_ERR_ARG;
   const bool opp2 = h->env_on && h->env.opponent == 2;
+  const auto state = [&](const char* what) {
+    h->err = std::string(fn) + ": " + what;
+    return MONSOON_ERR_STATE;
+  };
   if (!ex) {
-    if (opp2 && h->env_explore) {
-      h->err = "monsoon_env_set_opponent_explore: an env that was reset with a rule is loaded: its rule can be replaced (all thresholds 0 = silent), not cleared";
-      return MONSOON_ERR_STATE;
-    }
+    if (opp2 && h->env_explore)
+      return state("an env that was reset with a rule is loaded: its rule can be replaced (all thresholds 0 = silent), not cleared");
     h->opp_ex_n = 0;
+    h->opp_ex_sample = false;
     return MONSOON_OK;
   }
-  if (!thresholds || n <= 0 || n > h->cfg.max_games) return bad_arg(h, "monsoon_env_set_opponent_explore", "bad argument (thresholds, 1 <= n <= max_games)");
-  if (opp2 && !h->env_explore) {
-    h->err = "monsoon_env_set_opponent_explore: the loaded opponent-2 env was reset without a rule (set the rule, all thresholds 0 if need be, before monsoon_env_reset)";
-    return MONSOON_ERR_STATE;
+  if (!thresholds || n <= 0 || n > h->cfg.max_games) return bad_arg(h, fn, "bad argument (thresholds, 1 <= n <= max_games)");
+  if (sample) {
+    if (!inv_temperature) return bad_arg(h, fn, "inv_temperature is NULL");
+    for (int i = 0; i < n; i++)
+      if (!(inv_temperature[i] > 0.0) || !std::isfinite(inv_temperature[i])) return bad_arg(h, fn, "every inv_temperature must be finite and > 0");
   }
-  if (opp2 && n != h->env_n) return bad_arg(h, "monsoon_env_set_opponent_explore", "n differs from the loaded env's");
+  if (opp2 && !h->env_explore)
+    return state("the loaded opponent-2 env was reset without a rule (set the rule, all thresholds 0 if need be, before monsoon_env_reset)");
+  if (opp2 && h->env_sample != sample)
+    return state(sample ? "the loaded opponent-2 env was reset with the uniform rule (monsoon_env_set_opponent_explore retunes it)"
+                        : "the loaded opponent-2 env was reset with the sampling rule (monsoon_env_set_opponent_sample retunes it)");
+  if (opp2 && n != h->env_n) return bad_arg(h, fn, "n differs from the loaded env's");
   HIP_TRY(h, bind_device(h));
-  if (!h->d_opp_ex) {
-    HIP_TRY(h, h->mem.alloc(&h->d_opp_ex, ((size_t)OPP_EX_RULE_WORDS + (size_t)h->cfg.max_games) * 4));
-    HIP_TRY(h, hipMemsetAsync(h->d_opp_ex, 0, ((size_t)OPP_EX_RULE_WORDS + (size_t)h->cfg.max_games) * 4, h->stream));
+  if (!h->d_opp_ex) {   // the rule's words | thresholds[max_games] | inv_temperature[max_games]: one allocation, never moved
+    const size_t bytes = opp_ex_inv_t_at(h) + (size_t)h->cfg.max_games * 8;
+    uint8_t* p = nullptr;
+    HIP_TRY(h, h->mem.alloc(&p, bytes));
+    HIP_TRY(h, hipMemsetAsync(p, 0, bytes, h->stream));
+    h->d_opp_ex = (uint32_t*)p;
+    h->d_opp_inv_t = (double*)(p + opp_ex_inv_t_at(h));
   }
   if (!h->d_opp_explored) {
     HIP_TRY(h, h->mem.alloc(&h->d_opp_explored, (size_t)h->cfg.max_games * 4));
     HIP_TRY(h, hipMemsetAsync(h->d_opp_explored, 0, (size_t)h->cfg.max_games * 4, h->stream));
   }
+  // the sampling kernel parks every decision's scores in the slot's row of the score table (monsoon_decide's, allocated on first use)
+  if (sample && !h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
   const uint32_t rule[2] = {ex->seed, (uint32_t)ex->until_step};
   HIP_TRY(h, hipMemcpyAsync(h->d_opp_ex, rule, sizeof(rule), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(h->d_opp_ex + OPP_EX_RULE_WORDS, thresholds, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  if (sample) HIP_TRY(h, hipMemcpyAsync(h->d_opp_inv_t, inv_temperature, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->opp_ex_n = n;
+  h->opp_ex_sample = sample;
   return MONSOON_OK;
+}
+int monsoon_env_set_opponent_explore(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds, int32_t n) {
+  return env_set_opponent_rule(h, "monsoon_env_set_opponent_explore", false, ex, thresholds, nullptr, n);
+}
+int monsoon_env_set_opponent_sample(monsoon_t* h, const monsoon_env_explore* ex, const uint32_t* thresholds, const double* inv_temperature,
+                                    int32_t n) {
+  return env_set_opponent_rule(h, "monsoon_env_set_opponent_sample", true, ex, thresholds, inv_temperature, n);
 }
 
 // One device-to-device copy on the handle's stream: no allocation or synchronisation (graph-capturable).
@@ -2429,7 +2467,7 @@ int monsoon_env_opponent_explored_dev(monsoon_t* h, void* out_dev) {
   if (!h) return MONSOON_ERR_ARG;
   if (int rc = require_env(h, "monsoon_env_opponent_explored_dev")) return rc;
   if (!(h->env.opponent == 2 && h->env_explore)) {
-    h->err = "monsoon_env_opponent_explored_dev: the loaded env has no exploration rule (monsoon_env_set_opponent_explore before monsoon_env_reset)";
+    h->err = "monsoon_env_opponent_explored_dev: the loaded env has no exploration rule (monsoon_env_set_opponent_explore or _sample before monsoon_env_reset)";
     return MONSOON_ERR_STATE;
   }
   if (!out_dev) return bad_arg(h, "monsoon_env_opponent_explored_dev", "out_dev is NULL");
@@ -2528,7 +2566,8 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   else if (cfg->pool_n && decks) bad = "decks must be NULL with a pool (every episode draws its decks)";
   else if (((uintptr_t)views->obs | (uintptr_t)views->legal) & 3) bad = "views.obs and views.legal must be 4-byte aligned";
   else if (cfg->opponent == 2 && h->opp_n && h->opp_n != n) bad = "n differs from the n of monsoon_env_set_opponents";
-  else if (cfg->opponent == 2 && h->opp_ex_n && h->opp_ex_n != n) bad = "n differs from the n of monsoon_env_set_opponent_explore";
+  else if (cfg->opponent == 2 && h->opp_ex_n && h->opp_ex_n != n)
+    bad = h->opp_ex_sample ? "n differs from the n of monsoon_env_set_opponent_sample" : "n differs from the n of monsoon_env_set_opponent_explore";
   if (bad) return bad_arg(h, "monsoon_env_reset", bad);
   if (cfg->opponent == 2 && !h->opp_n) {
     h->err = "monsoon_env_reset: opponent 2 needs monsoon_env_set_opponents first";
@@ -2573,6 +2612,7 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
   v.opp_pop = nullptr;
   v.opp_lookahead = nullptr;
   h->env_explore = false;
+  h->env_sample = false;
   h->env_sched = EnvSched{};
   if (by_schedule) {
     h->env_sched = EnvSched{(const monsoon_deck_schedule*)h->d_sched, h->d_mt_init, (uint32_t*)(h->d_sched + sizeof(monsoon_deck_schedule))};
@@ -2585,11 +2625,16 @@ int monsoon_env_reset(monsoon_t* h, const monsoon_env_config* cfg, const monsoon
     v.opp_lookahead = (uint32_t*)(h->d_opp + ol.lookahead);
     v.opp_count = (int32_t*)(h->d_opp + ol.count);
     v.opp_pop = (int*)(h->d_opp + ol.pop);
-    // with a rule in the handle every step of this env launches k_env_opp_explore where it would launch k_env_opp
+    // with a rule in the handle every step of this env launches k_env_opp_explore, or k_env_opp_sample for a sampling rule,
+    // where it would launch k_env_opp
     h->env_explore = h->opp_ex_n != 0;
-    const KernelOps* o = h->env_explore ? (const KernelOps*)monsoon_env_opp_explore_ops() : (const KernelOps*)monsoon_env_opp_ops();
+    h->env_sample = h->env_explore && h->opp_ex_sample;
+    const KernelOps* o = h->env_sample    ? (const KernelOps*)monsoon_env_opp_sample_ops()
+                         : h->env_explore ? (const KernelOps*)monsoon_env_opp_explore_ops()
+                                          : (const KernelOps*)monsoon_env_opp_ops();
     if (h->env_explore) {
       h->env_ex = EnvExplore{h->d_opp_ex, h->d_opp_ex + OPP_EX_RULE_WORDS, h->d_opp_explored, v.seed0, v.episode, v.stride};
+      h->env_es = EnvSample{h->env_ex, h->d_opp_inv_t};
       HIP_TRY(h, hipMemsetAsync(h->d_opp_explored, 0, (size_t)n * 4, h->stream));
     }
     int waves = 0;

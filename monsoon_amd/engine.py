@@ -363,6 +363,21 @@ class BatchEngine:
         self._ck(self.lib.monsoon_env_set_opponent_explore(self.h, ctypes.byref(ex), _ptr(thresholds), len(thresholds)),
                  "monsoon_env_set_opponent_explore")
 
+    def env_set_opponent_sample(self, seed, until_step, thresholds, inv_temperatures):
+        """monsoon_env_set_opponent_sample: monsoon_env_set_opponent_explore's rule whose decisions draw from the softmax
+        over their scores, host inv_temperatures[n] float64 (1 / T of slot i, finite and > 0) beside the thresholds;
+        thresholds None clears the rule.  Synchronises."""
+        if thresholds is None:
+            self._ck(self.lib.monsoon_env_set_opponent_sample(self.h, None, None, None, 0), "monsoon_env_set_opponent_sample")
+            return
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        inv_temperatures = np.ascontiguousarray(inv_temperatures, dtype=np.float64)
+        if inv_temperatures.shape != thresholds.shape:
+            raise ValueError(f"inv_temperatures must be {thresholds.shape}, got {inv_temperatures.shape}")
+        ex = _lib.EnvExplore(int(seed) & 0xFFFFFFFF, int(until_step))
+        self._ck(self.lib.monsoon_env_set_opponent_sample(self.h, ctypes.byref(ex), _ptr(thresholds), _ptr(inv_temperatures), len(thresholds)),
+                 "monsoon_env_set_opponent_sample")
+
     def env_opponent_explored(self, out_ptr):
         """monsoon_env_opponent_explored_dev: the explored decisions of every slot's opponent since the env's reset,
         uint32[n], into device memory at out_ptr (asynchronous on the handle's stream)."""

@@ -6,7 +6,8 @@ legal_actions, reset, expert_agent as the opponent), each an endless sequence of
 re-seed, re-init, observation and legal mask -- and no host round trip, so it can be captured into a CUDA graph.  The
 opponent can also be the reference's HeuristicAgent with GA weights ("heuristic": seven launches per step).
 `OpponentExplore` makes that opponent epsilon-greedy with an epsilon per slot (`reset(opponent_explore=...)`,
-`set_opponent_explore` between steps, `opponent_explored` for the counts, `opponent_explore_draws` for the draws).
+`set_opponent_explore` between steps, `opponent_explored` for the counts, `opponent_explore_draws` for the draws); with
+`temperature=` its exploring decisions draw from the softmax over their scores, a temperature per slot.
 `snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device.
 Episode decks come from the reset decks, from a pool, or from a deck schedule (`reset(deck_schedule=...)`: the GA's
 exploit / explore / balance curriculum, drawn on the device per episode; `set_deck_schedule` moves its generation).
@@ -62,13 +63,39 @@ class OpponentExplore:
     a decision of slot i's opponent at step index k of its episode (k < until_step where until_step > 0) commits a uniformly
     drawn legal action instead of its arg-max with probability eps[i].  eps is a scalar (every slot) or one value per slot;
     threshold = min(int(eps * 2**32), 0xFFFFFFFF) as engine.Explore's.  The draws are hash32(seed, episode seed, k, .):
-    opponent_explore_draws recomputes them."""
+    opponent_explore_draws recomputes them.
+    temperature = a finite T > 0, a scalar (every slot) or one value per slot, selects the sampling rule instead
+    (monsoon_env_set_opponent_sample): such a decision commits an action drawn from the softmax over its scores,
+    exp((score - best) / T[i]) in 24-bit integer weights (game_log.sample_weights, game_log.sample_rank, as engine.Explore's
+    temperature); inv_temperatures(n) = 1.0 / T is what the device multiplies by.  Actions tied for the best score share
+    the probability equally.  temperature=None is the uniform rule, unchanged in every bit."""
 
-    def __init__(self, eps, seed, until_step=0):
+    def __init__(self, eps, seed, until_step=0, temperature=None):
         e = np.asarray(eps, dtype=np.float64)
         if e.ndim > 1 or not ((e >= 0.0) & (e <= 1.0)).all():   # (a NaN fails it too)
             raise ValueError(f"OpponentExplore: eps is a scalar or [n] with every value in [0, 1], got {eps!r}")
         self.eps, self.seed, self.until_step = e, int(seed) & 0xFFFFFFFF, int(until_step)
+        self.temperature = None
+        if temperature is not None:
+            t = np.asarray(temperature, dtype=np.float64)
+            with np.errstate(divide="ignore", over="ignore"):
+                ok = t.ndim <= 1 and bool(((t > 0.0) & np.isfinite(t) & np.isfinite(1.0 / np.where(t > 0.0, t, 1.0))).all())
+            if not ok:   # (a NaN fails it too, and a subnormal T whose 1 / T is not finite)
+                raise ValueError(f"OpponentExplore: temperature is a scalar or [n] with every value finite and > 0, got {temperature!r}")
+            self.temperature = t
+
+    @property
+    def samples(self):
+        """True for the sampling rule (a temperature), False for the uniform one."""
+        return self.temperature is not None
+
+    def inv_temperatures(self, n):
+        """float64 [n]: 1.0 / T of slot i, what monsoon_env_set_opponent_sample takes and the device multiplies by."""
+        if not self.samples:
+            raise ValueError("OpponentExplore: inv_temperatures needs a temperature (the sampling rule)")
+        if self.temperature.ndim == 1 and self.temperature.shape != (n,):
+            raise ValueError(f"OpponentExplore: temperature holds {len(self.temperature)} values, the env {n} slots")
+        return np.ascontiguousarray(1.0 / np.broadcast_to(self.temperature, (n,)), dtype=np.float64)
 
     def thresholds(self, n):
         """uint32 [n]: slot i's opponent explores iff its draw0 < thresholds[i]."""
@@ -125,6 +152,7 @@ class VecEnv:
         self.views = None
         self._heuristic = False   # an opponent-2 env is loaded
         self._explore = False     # ... that was reset with an exploration rule
+        self._samples = False     # ... of the sampling kind (OpponentExplore(temperature=)): the kind of the rule last set
         self._rows = None         # the rows last given to set_opponents / reset (None = row 0 for every slot)
         self._explored = None     # opponent_explored()'s tensor
         self._after = {}          # obs -> ((n, K), tensors, _lib.EnvAfter): the latest shape per obs flag, reused until it changes
@@ -181,7 +209,9 @@ class VecEnv:
         opponent_explore (an OpponentExplore; opponent "heuristic" only) makes the opponents epsilon-greedy from the first
         decision on, and lets set_opponent_explore retune them between steps -- eps 0 everywhere arms the env for that and
         plays the plain opponent bit for bit until then.  Without it the env plays the plain opponent's kernel and
-        set_opponent_explore raises."""
+        set_opponent_explore raises.  An OpponentExplore with a temperature plays the sampling opponent's kernel instead;
+        the library keeps one kind of rule per loaded heuristic env, so a reset that changes the kind on a VecEnv whose
+        heuristic env holds a rule raises MonsoonError (open another VecEnv)."""
         if opponent not in OPPONENTS:
             raise ValueError(f"opponent must be one of {sorted(OPPONENTS)}")
         seed0 = np.ascontiguousarray(seed0, dtype=np.uint32)
@@ -202,11 +232,13 @@ class VecEnv:
                 raise ValueError(f"a VecEnv with a heuristic opponent keeps its {self.n} slots: open another VecEnv for {n}")
         elif opponent_weights is not None or opponent_rows is not None or opponent_explore is not None:
             raise ValueError('opponent_weights / opponent_rows / opponent_explore need opponent="heuristic"')
-        thresholds = None
+        thresholds = inv_t = None
         if opponent_explore is not None:
             if not isinstance(opponent_explore, OpponentExplore):
                 raise ValueError("opponent_explore must be an OpponentExplore")
             thresholds = opponent_explore.thresholds(n)
+            if opponent_explore.samples:
+                inv_t = opponent_explore.inv_temperatures(n)
         cfg = EnvConfig()
         cfg.opponent = OPPONENTS[opponent]
         cfg.agent_side = int(agent_side)
@@ -228,9 +260,10 @@ class VecEnv:
                 self.engine.env_set_opponents(opp[0], opp[1], n)
             if opp is not None:
                 if thresholds is not None:
-                    self.engine.env_set_opponent_explore(opponent_explore.seed, opponent_explore.until_step, thresholds)
+                    self._set_rule(opponent_explore.seed, opponent_explore.until_step, thresholds, inv_t)
+                    self._samples = inv_t is not None
                 elif self._explore:   # the loaded env holds the handle's rule: it cannot be cleared, silent is the same play
-                    self.engine.env_set_opponent_explore(0, 0, np.zeros(n, dtype=np.uint32))
+                    self._set_rule(0, 0, np.zeros(n, dtype=np.uint32), np.ones(n) if self._samples else None)
             self._heuristic = False
             self._schedule = None
             if sched is not None:
@@ -281,9 +314,17 @@ class VecEnv:
             self.engine.env_set_opponents(w, r, self.n)
         self._rows = r
 
+    def _set_rule(self, seed, until_step, thresholds, inv_t):
+        """The setter of the rule's kind: inv_t None = the uniform rule, else the sampling one."""
+        if inv_t is None:
+            self.engine.env_set_opponent_explore(seed, until_step, thresholds)
+        else:
+            self.engine.env_set_opponent_sample(seed, until_step, thresholds, inv_t)
+
     def eps_by_row(self, eps_rows):
         """A per-individual epsilon [k] -> the per-slot values [n] for OpponentExplore, through the rows last given to
-        set_opponents / reset (slot i gets eps_rows[rows[i]]; no rows = row 0 for every slot)."""
+        set_opponents / reset (slot i gets eps_rows[rows[i]]; no rows = row 0 for every slot).  It maps any per-individual
+        vector: temperatures by row go through it too (OpponentExplore(eps_by_row(e), seed, temperature=eps_by_row(t)))."""
         e = np.asarray(eps_rows, dtype=np.float64)
         if e.ndim != 1 or len(e) == 0:
             raise ValueError(f"eps_rows must be [k], got {np.shape(eps_rows)}")
@@ -296,17 +337,24 @@ class VecEnv:
         """Retune the exploring opponents between steps (monsoon_env_set_opponent_explore): the OpponentExplore's seed,
         until_step and per-slot epsilons (eps_by_row makes them from per-individual ones) apply from the next decision; a
         captured step graph stays valid.  Needs reset(opponent="heuristic", opponent_explore=...) first (MonsoonError).
-        Synchronises the env's stream."""
+        A sampling rule (OpponentExplore(temperature=)) retunes the temperatures too (monsoon_env_set_opponent_sample); the
+        kind is the reset's -- the kernel was chosen there -- and a rule of the other kind raises MonsoonError before the
+        library is touched.  Synchronises the env's stream."""
         if not (self._heuristic and self._explore):
             raise MonsoonError('VecEnv.set_opponent_explore needs reset(opponent="heuristic", opponent_explore=...) first')
         if not isinstance(opponent_explore, OpponentExplore):
             raise ValueError("opponent_explore must be an OpponentExplore")
+        if opponent_explore.samples != self._samples:
+            raise MonsoonError("VecEnv.set_opponent_explore: the env was reset with the " + ("sampling" if self._samples else "uniform") +
+                               " rule; a rule " + ("without" if self._samples else "with") + " a temperature needs another reset")
         thresholds = opponent_explore.thresholds(self.n)
+        inv_t = opponent_explore.inv_temperatures(self.n) if self._samples else None
         with self._after_torch_stream():
-            self.engine.env_set_opponent_explore(opponent_explore.seed, opponent_explore.until_step, thresholds)
+            self._set_rule(opponent_explore.seed, opponent_explore.until_step, thresholds, inv_t)
 
     def opponent_explored(self):
-        """The decisions of every slot's opponent whose draw said "explore", since reset (monsoon_env_opponent_explored_dev):
+        """The decisions of every slot's opponent whose draw said "explore" (or "sample", under a rule with a temperature:
+        the counter serves both kinds), since reset (monsoon_env_opponent_explored_dev):
         an int32 CUDA tensor [n], allocated on the first call per n and overwritten in place by every later one (a later
         call allocates nothing and can be captured).  Stream ordering as in step."""
         import torch
