@@ -342,7 +342,8 @@ int monsoon_rollout_explore(monsoon_t* h, const double* weights, int32_t n_indiv
  * probability eps = threshold / 2**32, so the behaviour policy gave the committed action a
  *   mu(a) = (1 - eps) * [a == greedy] + eps * taken_weight / weight_total     where explored == 1 and weight_total > 0,
  * and for an entry with explored == 0 (action == greedy) mu(a) = (1 - eps) + eps * p_greedy, whose p_greedy the log does
- * not carry (weight_total is 0 there); with eps == 1 every covered decision sampled and mu is the ratio itself.
+ * not carry (weight_total is 0 there; monsoon_rollout_policies, below, writes the weights on those entries too); with
+ * eps == 1 every covered decision sampled and mu is the ratio itself.
  * sm == NULL or sm->rule.threshold == 0: no decision samples and every output of monsoon_rollout_logged is what that
  * call writes, bit for bit; greedy == action, explored == 0, taken_score == score on decisions, both weights 0.
  * Device log: an entry takes B = monsoon_rollout_explore's bytes + 4 [weight_total] + 4 [taken_weight], 1 .. 29, counting
@@ -359,6 +360,47 @@ int monsoon_rollout_sample(monsoon_t* h, const double* weights, int32_t n_indivi
                            int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
                            int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log,
                            const monsoon_sample* sm, const monsoon_explore_log* xlog, const monsoon_sample_log* slog);
+
+/* A logged rollout in which every individual explores by a rule of its own, with the behaviour probability of every
+ * decision in the log: monsoon_rollout_sample's contract word for word -- the draws and their hash32 keys, x_j, weight24,
+ * total, r and j*, the re-step of a drawn action that is not the arg-max, the counters, the faults, the batch cap by the log
+ * bytes asked for (1 .. 29 per entry), the score table kept on the device, THE COUNTS ARE NOT FITNESS -- with two changes.
+ *  1. THE ROW OF THE MOVER.  A heuristic decision reads pol->threshold[r] and pol->inv_temperature[r], r = match.p1 when
+ *     FIRST is to play and match.p2 when SECOND is: the row whose weights score the decision (a hall-of-fame row is a row
+ *     like any other).  seed, sides and until_step stay call-wide.  The scripted bot never explores.  So one call plays a
+ *     greedy champion (threshold 0) against the same weights played loosely, a uniformly exploring copy, a cold softmax.
+ *  2. WEIGHTS ON EVERY COVERED DECISION.  A decision is COVERED when its side's bit is set in pol->sides, until_step allows
+ *     its step k, and threshold[r] > 0.  Every covered decision writes weight_total = total and taken_weight, whether
+ *     draw0 < threshold[r] said "sample" or not; one that did not sample commits its arg-max, whose weight is weight24(0) =
+ *     2**24 where total > 0, and 0 otherwise.  explored still says what the draw said.  A decision that is not covered
+ *     writes 0 in both, as do bot steps and the padding.  With eps_r = threshold[r] / 2**32 the behaviour policy gave the
+ *     committed action of a covered decision with weight_total > 0
+ *       mu(a) = (1 - eps_r) * [a == greedy] + eps_r * taken_weight / weight_total
+ *     exactly, sampled or not (monsoon_amd/game_log.py behaviour_prob); every other decision committed its arg-max with
+ *     probability 1.
+ * inv_temperature[r] == 0.0 is the uniform rule through the same formulas, no branch: x_j = (s_j - best) * 0.0 weighs
+ * every finite score 2**24, so j* = ((draw1 * n_legal * 2**24) >> 32) >> 24 = (draw1 * n_legal) >> 32, which is
+ * monsoon_rollout_explore's rank.  With a NaN or infinite best score total is 0 and the decision commits its arg-max, as in
+ * monsoon_rollout_sample (there monsoon_rollout_explore would commit its rank).
+ * Every threshold 0: every output of monsoon_rollout_logged is what that call writes, bit for bit; greedy == action,
+ * explored == 0, taken_score == score on decisions, both weights 0 (without an array of xlog or slog the call is
+ * monsoon_rollout_logged itself, batch cap included).
+ * The two tables are copied to device buffers of the handle, grown on demand, once per call before the first batch.  The
+ * kernel is one more instantiation of the decision loop at the build's default variant (k_play_policy).
+ * MONSOON_ERR_ARG with nothing launched and the loaded games untouched: whatever monsoon_rollout_sample refuses; a NULL
+ * pol, threshold or inv_temperature; an inv_temperature[r] that is NaN, infinite or < 0 for any r < n_individuals, also
+ * where threshold[r] == 0. */
+typedef struct {
+  uint32_t seed;                  /* as monsoon_explore.seed */
+  uint32_t sides;                 /* as monsoon_explore.sides; a bit above bit 1: MONSOON_ERR_ARG */
+  int32_t  until_step;            /* as monsoon_explore.until_step */
+  const uint32_t* threshold;      /* HOST [n_individuals]; row r's decisions leave the arg-max iff draw0 < threshold[r]; 0 = never */
+  const double*   inv_temperature;/* HOST [n_individuals]; finite and >= 0; 0.0 = the uniform rule */
+} monsoon_policies;
+int monsoon_rollout_policies(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches,
+                             int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns,
+                             int32_t* out_counts, int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log,
+                             const monsoon_policies* pol, const monsoon_explore_log* xlog, const monsoon_sample_log* slog);
 
 /* Logged games played again on the device into the (state, action) rows a learner trains on: one row per kept log entry,
  * holding the state BEFORE that entry's step.  No decision is recomputed: every entry costs one committed step.

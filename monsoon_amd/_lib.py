@@ -90,6 +90,11 @@ class SampleLog(ctypes.Structure):      # monsoon_sample_log: caller-owned host 
     _fields_ = [(name, ctypes.c_void_p) for name in ("weight_total", "taken_weight")]
 
 
+class Policies(ctypes.Structure):       # monsoon_policies: the rule of monsoon_rollout_policies (host tables, a row per individual)
+    _fields_ = [("seed", ctypes.c_uint32), ("sides", ctypes.c_uint32), ("until_step", ctypes.c_int32), ("threshold", ctypes.c_void_p),
+                ("inv_temperature", ctypes.c_void_p)]
+
+
 class ReplayRows(ctypes.Structure):     # monsoon_replay_rows: caller-owned device buffers (NULL = not wanted, except action)
     _fields_ = [(name, ctypes.c_void_p) for name in ("obs", "legal", "obs_raises", "to_play", "action", "bot", "game", "step",
                                                       "state_hash")]
@@ -148,6 +153,10 @@ SIGNATURES = {
                                               ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.POINTER(RolloutLog), ctypes.POINTER(Sample),
                                               ctypes.POINTER(ExploreLog), ctypes.POINTER(SampleLog)]),
+    "monsoon_rollout_policies": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.POINTER(RolloutLog), ctypes.POINTER(Policies),
+                                                ctypes.POINTER(ExploreLog), ctypes.POINTER(SampleLog)]),
     "monsoon_debug_sample_kat": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 8),
     "monsoon_replay_logged_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,

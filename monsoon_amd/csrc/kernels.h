@@ -516,6 +516,34 @@ __device__ MSB_INL void log_sample(const PlaySample& sp, const PlayLog& lg, cons
   }
 }
 
+// What play_game<.., SAMPLE = true, POLICY = true> needs beyond the PlayLog and the PlayExplore (k_play_policy,
+// play_policy.hip; include/monsoon.h monsoon_rollout_policies): a threshold and an inverse temperature per weight row --
+// the decision reads those of the row that moves -- and the two weight arrays of the log (rows like the PlayLog's, each may
+// be null).  An argument of that kernel alone; play_game sees a pointer to it.  PlayExplore's threshold is not read.
+struct PlayPolicy {
+  const uint32_t* threshold;       // [n_individuals]: row r's decisions leave the arg-max iff draw0 < threshold[r]
+  const double* inv_temperature;   // [n_individuals]: finite, >= 0 (0: every finite score weighs 2**24, the uniform rule)
+  uint32_t* weight_total;          // [n][stride] sum of the decision's weights, on every decision the rule covers
+  uint32_t* taken_weight;          // [n][stride] weight of the committed action, likewise
+};
+// sample_draw with the mover's own threshold (weight row `row`, wave-uniform like every word loaded here): `covered` says
+// whether the side's bit, the step limit and a threshold > 0 let the decision leave its arg-max at all -- the decisions whose
+// weights the log carries -- and then inv_t is the row's inverse temperature; the result says whether draw0 did.
+__device__ MSB_INL bool policy_draw(const PlayPolicy& pp, const PlayExplore& ex, const int row, const uint32_t match_seed, const int side, const int k,
+                                    const int n_legal, bool& covered, uint32_t& draw1, double& inv_t) {
+  draw1 = 0u;
+  inv_t = 0.0;
+  covered = false;
+  if (!((ex.sides >> side) & 1u) || (ex.until_step > 0 && k >= ex.until_step) || n_legal <= 0) return false;
+  const uint32_t threshold = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp.threshold[row]);
+  if (!threshold) return false;
+  covered = true;
+  inv_t = __longlong_as_double((long long)uni64((unsigned long long)__double_as_longlong(pp.inv_temperature[row])));
+  if (explore_hash32(ex.seed, match_seed, (uint32_t)k, 0u) >= threshold) return false;
+  draw1 = explore_hash32(ex.seed, match_seed, (uint32_t)k, 1u);
+  return true;
+}
+
 // What play_game<U, true, false, false, false, true> needs beyond the EnvPolicy (k_env_opp_sample, env_opp_sample.hip;
 // include/monsoon.h monsoon_env_set_opponent_sample): the EnvExplore of the rule -- WHEN a decision leaves its arg-max is
 // env_explore_rank's conditions word for word -- and the slots' inverse temperatures, device words like the thresholds.  An
@@ -562,6 +590,9 @@ __device__ MSB_INL bool env_sample_draw(const EnvSample& es, const int g, const 
 // window, so the step is the look-ahead's bit for bit): that successor, its fault and no features are what the commit takes.
 // The decision's scalars live and die in that one block in front of the commit; `sp` is the kernel's.  The env's form logs
 // nothing: lane 0 counts the decision in ee->explored, and the commit, the end rules and the 64-decision guard are ENV's.
+// POLICY = true (k_play_policy, play_policy.hip, with SAMPLE and LOG): the sampling form whose threshold and inverse
+// temperature are those of the weight row that moves (`pp`, policy_draw), and which weighs the actions of every decision
+// the rule covers, drawn or not, so that the log carries the behaviour probability of every row.
 //
 // MSB_COMMIT_BEST is the commit: adapter = adapter.apply_action(best).  v_best becomes the record (column 0 and v_par);
 // the successor carries its own stream cursor (H_RNGPOS), so the cursor is committed and a used-up block refilled by the
@@ -598,13 +629,15 @@ __device__ MSB_INL bool env_sample_draw(const EnvSample& es, const int g, const 
   if (feat_ok && lane < 10) wf[20 + lane] = ((MSB_AS_LDS const double*)(uintptr_t)L::CF)[wl_ * 10 + lane]; \
   __syncthreads();                                                                                  \
   MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(wl_, gr_))
-template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false, bool SAMPLE = false>
+template <int U, bool ENV = false, bool VS = false, bool LOG = false, bool EXPLORE = false, bool SAMPLE = false, bool POLICY = false>
 __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int lane, int max_turns, int rounds, int write_scores,
                                   const EnvPolicy& pol, const PlayLog& lg = PlayLog{}, const PlayExplore& ex = PlayExplore{},
-                                  ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr, const PlaySample* const sp = nullptr) {
+                                  ExploreTake* const xt = nullptr, const EnvExplore* const ee = nullptr, const PlaySample* const sp = nullptr,
+                                  const PlayPolicy* const pp = nullptr) {
   static_assert(!EXPLORE || (LOG && !ENV) || (ENV && !VS && !LOG), "the exploring form is a logging rollout or the env's opponent");
   static_assert(!SAMPLE || (!EXPLORE && ((LOG && !ENV) || (ENV && !VS && !LOG))),
                 "the sampling form is a logging rollout with a rule of its own or the env's opponent");
+  static_assert(!POLICY || (SAMPLE && LOG && !ENV), "the per-row form is a sampling logged rollout");
   typedef PlayLds<U, (VS && !SAMPLE) ? PLAY_LDS_COLUMNS_BOT : PLAY_LDS_COLUMNS> L;
   GameMeta meta = b.meta[g];
   const uint32_t lookahead0 = meta.lookahead;
@@ -861,7 +894,47 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
       }
       PROF_MARK(6);   // argmax + new best into registers
     }
-    if constexpr (SAMPLE) {
+    if constexpr (POLICY) {
+      // The sampling block below with the mover's own rule (a block of its own: the existing forms keep their code).  The
+      // threshold and the inverse temperature are those of the weight row that scored this decision; every decision the rule
+      // covers weighs its actions and logs total and the committed action's weight -- 2**24 for an arg-max that was not
+      // drawn, weight24(0) -- and only a drawn action other than the arg-max is stepped once more.
+      __syncthreads();
+      MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
+      __syncthreads();
+      uint32_t draw1, total = 0u, taken_w = 0u;
+      double inv_t;
+      bool covered;
+      const bool on = policy_draw(*pp, ex, __builtin_amdgcn_readfirstlane(pe.local() == 0 ? meta.p1 : meta.p2),
+                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)ex.match_seed[g]), __builtin_amdgcn_readfirstlane(pe.local()),
+                                  meta.steps, n_legal, covered, draw1, inv_t);
+      int take = run_a;
+      double take_s = run_s;
+      if (covered) {   // (uniform)
+        const double* row = b.scores + (size_t)g * MONSOON_NUM_ACTIONS;   // this decision's scores: the barriers above made them visible
+        const SamplePick pk = sample_pick(row, ls.mask[0], ls.mask[1], ls.mask[2], run_s, inv_t, draw1, lane);
+        total = pk.total;   // (0: the best score is NaN or infinite, the decision commits its arg-max)
+        taken_w = !pk.total ? 0u : on ? pk.w : 1u << 24;
+        if (on && pk.total && pk.pos != run_a) {   // (the arg-max's record is in v_best already: nothing to step)
+          take = pk.pos;
+          take_s = row[take];
+          int fs = 0;
+          if (lane == 0) {   // (the other lanes wait at the barrier, as in the bot's round)
+            ce.step(take);
+            fs = ce.fault();
+            if (!fs && ce.observation_raises()) fs = FAULT_INT_CARD;
+          }
+          __syncthreads();
+          cfault = __builtin_amdgcn_readfirstlane(fs);
+          feat_ok = 0;   // the next decision computes its "before" side
+          MSB_EACH_GRANULE(L::GPL, lane, v_best[j_] = *L::gran(0, gr_))
+        }
+      }
+      log_explore(ex, lg, g, lane, meta.steps, run_a, on, take_s);
+      log_sample(PlaySample{0.0, pp->weight_total, pp->taken_weight}, lg, g, lane, meta.steps, total, taken_w);
+      run_a = take;
+    }
+    if constexpr (SAMPLE && !POLICY) {
       // column 0 is the current record again: the rule asks whose turn it is, and a sampled action is stepped from it
       __syncthreads();
       MSB_EACH_GRANULE(L::GPL, lane, *L::gran(0, gr_) = v_par[j_])
@@ -979,7 +1052,7 @@ __device__ MSB_INL void play_game(const DevBuffers& b, const int g, const int la
 // fewer launches in flight at once, on a stream each: sub-batch `half` has its own pair of counter sets and its own
 // overflow blocks behind those of the sub-batches before it, so no two launches in flight share or clear anything.
 constexpr int POP_PARTS = 8, POP_STRIDE = 32, SPLIT_MAX = 2;
-// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_play_explore, k_play_sample, k_replay_log, k_env_opp, k_env_opp_explore): `mine` / `other` are this launch's counter
+// The loop itself, for every persistent kernel (k_play, k_play_vs, k_play_log, k_play_explore, k_play_sample, k_play_policy, k_replay_log, k_env_opp, k_env_opp_explore): `mine` / `other` are this launch's counter
 // set and the one it clears, the indices are [g0, g0 + n), and play(t) plays index t.  A wavefront whose range holds
 // nothing for it leaves before enter(), which runs once ahead of the first game.
 template <class Enter, class Play>
@@ -1040,11 +1113,13 @@ const VariantOps* monsoon_vs_expert_ops();
 // The three logging kernels, one launcher type: k_play_log<DEFAULT_U, DEFAULT_W> (play_log.hip) is k_play_vs that writes
 // every committed step into a PlayLog, k_play_explore (play_explore.hip) is k_play_log whose decisions may explore
 // (PlayExplore), k_play_sample (play_sample.hip) is k_play_log whose decisions may sample (PlayExplore's rule, PlaySample).
+// k_play_policy (play_policy.hip) is k_play_sample whose rule is the moving row's own (PlayPolicy) -- a fourth logging kernel.
 // The host hands every one of them the same PlayLogged; each file's stub passes its kernel the members it takes.
 struct PlayLogged {
   PlayLog lg;
   PlayExplore ex;
   PlaySample sp;
+  PlayPolicy pp;
 };
 struct LoggedOps : KernelOps {
   void (*play)(int grid, int lds_bytes, hipStream_t stream, DevBuffers b, int n, int max_turns, int rounds, int persistent, int parity,
@@ -1053,6 +1128,7 @@ struct LoggedOps : KernelOps {
 const LoggedOps* monsoon_play_log_ops();
 const LoggedOps* monsoon_play_explore_ops();
 const LoggedOps* monsoon_play_sample_ops();
+const LoggedOps* monsoon_play_policy_ops();
 
 // k_sample_kat (play_sample.hip): sample_pick on caller-given rows (monsoon_debug_sample_kat), one wavefront per row.
 void monsoon_sample_kat_launch(hipStream_t stream, int m, const double* scores, const int32_t* n_legal, const double* best, const double* inv_t,

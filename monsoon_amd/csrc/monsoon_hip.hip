@@ -671,8 +671,9 @@ __global__ void k_ga_select(const double* fitness, int n, int* out_order) {
 // ================================================================================================
 // What launch_play launches: k_play of the handle's variant, k_play_vs (the kernel that knows the scripted bot, the
 // build's default variant), k_play_log (k_play_vs that writes every committed step into a log) or k_play_explore (k_play_log
-// whose decisions may explore) or k_play_sample (k_play_log whose decisions may sample).
-enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_EXPLORE = 3, PLAY_SAMPLE = 4, PLAY_KINDS = 5 };
+// whose decisions may explore) or k_play_sample (k_play_log whose decisions may sample) or k_play_policy (k_play_sample whose
+// rule is the moving row's own).
+enum PlayKind { PLAY = 0, PLAY_VS = 1, PLAY_LOG = 2, PLAY_EXPLORE = 3, PLAY_SAMPLE = 4, PLAY_POLICY = 5, PLAY_KINDS = 6 };
 
 // Device memory: everything the handle allocates is recorded in `mem` when it is allocated and freed from that record by
 // monsoon_destroy; the pointers below and in `b`, `env` and `env_sched` only refer to it.  Events and the split streams
@@ -726,6 +727,10 @@ struct monsoon {
   // monsoon_rollout_logged / _explore / _sample: the log of one batch (layout::log_layout), grown on demand
   uint8_t* d_log = nullptr;
   size_t log_cap = 0;   // bytes
+  // monsoon_rollout_policies: the call's threshold and inverse temperature per weight row, grown on demand
+  uint32_t* d_pol_threshold = nullptr;
+  double* d_pol_inv_t = nullptr;
+  size_t pol_cap = 0, pol_inv_t_cap = 0;   // rows
   // monsoon_replay_logged_dev: one batch's log, keep mask, row bases and outcome (layout::replay), grown on demand
   uint8_t* d_replay = nullptr;
   size_t replay_cap = 0;   // bytes
@@ -1672,15 +1677,20 @@ struct PlayCall {
   bool write_scores = false;     // every candidate's score goes to b.scores
   bool timed = false;            // an event pair of the handle round the call (kernel_ms)
   bool split = false;            // PLAY only (monsoon_play_rounds_dev, monsoon_decide_round_dev): the call may be split, see below
-  const PlayLogged* logged = nullptr;   // PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE (monsoon_rollout_logged / _explore / _sample): where every
-                                        // committed step is written, the exploration rule and the batch's match seeds, the inverse temperature
+  const PlayLogged* logged = nullptr;   // PLAY_LOG, PLAY_EXPLORE, PLAY_SAMPLE and PLAY_POLICY (monsoon_rollout_logged / _explore / _sample /
+                                        // _policies): where every committed step is written, the exploration rule and the batch's match
+                                        // seeds, the inverse temperature, the per-row tables
 };
 // The launcher of a logging kind (kernels.h LoggedOps), null for PLAY and PLAY_VS.
 static const LoggedOps* logged_ops(PlayKind kind) {
-  return kind == PLAY_LOG ? monsoon_play_log_ops() : kind == PLAY_EXPLORE ? monsoon_play_explore_ops() : kind == PLAY_SAMPLE ? monsoon_play_sample_ops() : nullptr;
+  return kind == PLAY_LOG       ? monsoon_play_log_ops()
+         : kind == PLAY_EXPLORE ? monsoon_play_explore_ops()
+         : kind == PLAY_SAMPLE  ? monsoon_play_sample_ops()
+         : kind == PLAY_POLICY  ? monsoon_play_policy_ops()
+                                : nullptr;
 }
 
-// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG, PLAY_EXPLORE and PLAY_SAMPLE are never split.
+// `rounds` decisions of every loaded game in ONE launch.  PLAY_VS, PLAY_LOG, PLAY_EXPLORE, PLAY_SAMPLE and PLAY_POLICY are never split.
 static int launch_play(monsoon_t* h, int n, const PlayCall& call) {
   bool timed = call.timed;
   if (h->bot_rows && call.kind == PLAY) {   // (a weight row of -1 must never reach k_play)
@@ -1895,11 +1905,14 @@ static int rollout_batch(monsoon_t* h, int base, int n, int min_row, int32_t max
 // monsoon_rollout (min_row = 0), monsoon_rollout_vs_expert (min_row = MONSOON_PLAYER_EXPERT: a side may be the bot) and the
 // logged calls (log non-null: the latter, played by the kernel of `kind`, every batch's log copied to row `base` of the
 // caller's arrays): PLAY_LOG is monsoon_rollout_logged, PLAY_EXPLORE monsoon_rollout_explore (rule->rule is the exploration
-// rule, xlog's arrays are logged too), PLAY_SAMPLE monsoon_rollout_sample (all of *rule, slog's arrays too)
+// rule, xlog's arrays are logged too), PLAY_SAMPLE monsoon_rollout_sample (all of *rule, slog's arrays too), PLAY_POLICY
+// monsoon_rollout_policies (rule->rule's seed, sides and until_step; pol's two tables, uploaded here once the schedule and the
+// decks have passed their checks; slog's arrays too)
 static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                         int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
                         int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log = nullptr, PlayKind kind = PLAY,
-                        const monsoon_sample* rule = nullptr, const monsoon_explore_log* xlog = nullptr, const monsoon_sample_log* slog = nullptr) {
+                        const monsoon_sample* rule = nullptr, const monsoon_explore_log* xlog = nullptr, const monsoon_sample_log* slog = nullptr,
+                        const monsoon_policies* pol = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   h->env_on = false;
   if (!weights || !matches || !deck_pairs || !out_counts || n_matches <= 0 || n_individuals <= 0 || n_decks <= 0 || max_turns <= 0 ||
@@ -1923,6 +1936,14 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
     HIP_TRY(h, h->mem.grow(h->d_results, h->results_cap, (size_t)n_matches, layout::results((size_t)n_matches).total, Grow::Replace));
     HIP_TRY(h, h->mem.grow(h->d_steps, h->steps_cap, (size_t)n_matches, (size_t)n_matches * 4, Grow::Replace));
   }
+  if (kind == PLAY_POLICY) {   // (the stream is idle: nothing reads the tables that a grow frees)
+    const size_t rows = (size_t)n_individuals;
+    HIP_TRY(h, h->mem.grow(h->d_pol_threshold, h->pol_cap, rows, rows * 4, Grow::Replace));
+    HIP_TRY(h, h->mem.grow(h->d_pol_inv_t, h->pol_inv_t_cap, rows, rows * 8, Grow::Replace));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pol_threshold, pol->threshold, rows * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pol_inv_t, pol->inv_temperature, rows * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the caller's tables are pageable host memory: read before the call goes on)
+  }
   HIP_TRY(h, hipMemsetAsync(h->d_counts, 0, (size_t)n_individuals * 12, h->stream));
   h->rollout_matches = 0;
   int cap = h->cfg.max_games;
@@ -1933,7 +1954,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
     lc.col[LOG_ACTION].host = log->action, lc.col[LOG_SCORE].host = log->score, lc.col[LOG_N_LEGAL].host = log->n_legal;
     if (kind != PLAY_LOG && xlog)
       lc.col[LOG_GREEDY].host = xlog->greedy, lc.col[LOG_EXPLORED].host = xlog->explored, lc.col[LOG_TAKEN_SCORE].host = xlog->taken_score;
-    if (kind == PLAY_SAMPLE && slog) lc.col[LOG_WEIGHT_TOTAL].host = slog->weight_total, lc.col[LOG_TAKEN_WEIGHT].host = slog->taken_weight;
+    if ((kind == PLAY_SAMPLE || kind == PLAY_POLICY) && slog) lc.col[LOG_WEIGHT_TOTAL].host = slog->weight_total, lc.col[LOG_TAKEN_WEIGHT].host = slog->taken_weight;
     unsigned mask = 0;
     for (int c = 0; c < LOG_COLUMNS; c++)
       if (lc.col[c].host) mask |= log_bit((LogColumn)c);
@@ -1944,7 +1965,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
     const Log l = log_layout((size_t)std::min(cap, n_matches) * max_turns, mask);
     HIP_TRY(h, h->mem.grow(h->d_log, h->log_cap, l.total, l.total, Grow::Replace));
     // a sampling kernel parks every decision's scores in the game's row of the score table (monsoon_decide's, allocated on first use)
-    if (kind == PLAY_SAMPLE && !h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
+    if ((kind == PLAY_SAMPLE || kind == PLAY_POLICY) && !h->b.scores) HIP_TRY(h, h->mem.alloc(&h->b.scores, (size_t)h->cfg.max_games * MONSOON_NUM_ACTIONS * 8));
     for (int c = 0; c < LOG_COLUMNS; c++) lc.col[c].dev = lc.col[c].host ? h->d_log + l.at[c] : nullptr;
     const auto dev = [&](LogColumn c) { return lc.col[c].dev; };
     lc.args.lg = {dev(LOG_ACTION), (double*)dev(LOG_SCORE), (int16_t*)dev(LOG_N_LEGAL), max_turns};
@@ -1952,6 +1973,7 @@ static int rollout_impl(monsoon_t* h, const char* who, int min_row, const double
       const monsoon_explore& ex = rule->rule;
       lc.args.ex = {ex.seed, ex.threshold, ex.sides, ex.until_step, nullptr, dev(LOG_GREEDY), dev(LOG_EXPLORED), (double*)dev(LOG_TAKEN_SCORE)};
       lc.args.sp = {rule->inv_temperature, (uint32_t*)dev(LOG_WEIGHT_TOTAL), (uint32_t*)dev(LOG_TAKEN_WEIGHT)};
+      lc.args.pp = {h->d_pol_threshold, h->d_pol_inv_t, lc.args.sp.weight_total, lc.args.sp.taken_weight};   // (read by PLAY_POLICY only)
     }
   }
   std::vector<uint32_t> seeds;
@@ -1996,14 +2018,15 @@ int monsoon_rollout_vs_expert(monsoon_t* h, const double* weights, int32_t n_ind
                       max_turns, out_counts, out_results, out_steps);
 }
 
-// What the three logged entry points share: the log that must be there, the rule's checks, and which kernel plays.  A rule
+// What the four logged entry points share (monsoon_rollout_policies hands over its tables in `pol`, checked already): the log
+// that must be there, the rule's checks, and which kernel plays.  A rule
 // that never fires (none, or threshold 0) still goes through the entry's kernel where one of xlog's or slog's arrays is
 // asked for (the kernel fills them: greedy = action, taken_score = score on decisions, both weights 0); without any the
 // call is the logged call itself, batch cap included.
 static int rollout_logged_impl(monsoon_t* h, const char* who, PlayKind kind, const double* weights, int32_t n_individuals, const monsoon_match* matches,
                                int32_t n_matches, const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts,
                                int8_t* out_results, int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_sample* sm,
-                               const monsoon_explore_log* xlog, const monsoon_sample_log* slog) {
+                               const monsoon_explore_log* xlog, const monsoon_sample_log* slog, const monsoon_policies* pol = nullptr) {
   if (!h) return MONSOON_ERR_ARG;
   if (!log || !log->action) return bad_arg(h, who, "log and log->action are required");
   if (sm && (sm->rule.sides & ~3u)) return bad_arg(h, who, "sides holds a bit above bit 1");
@@ -2013,7 +2036,7 @@ static int rollout_logged_impl(monsoon_t* h, const char* who, PlayKind kind, con
   const bool wants = (xlog && (xlog->greedy || xlog->explored || xlog->taken_score)) || (slog && (slog->weight_total || slog->taken_weight));
   const monsoon_sample* rule = (sm && sm->rule.threshold) ? sm : wants ? &never : nullptr;
   return rollout_impl(h, who, MONSOON_PLAYER_EXPERT, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns, out_counts,
-                      out_results, out_steps, log, rule ? kind : PLAY_LOG, rule, xlog, slog);
+                      out_results, out_steps, log, rule ? kind : PLAY_LOG, rule, xlog, slog, pol);
 }
 
 int monsoon_rollout_logged(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
@@ -2039,6 +2062,28 @@ int monsoon_rollout_sample(monsoon_t* h, const double* weights, int32_t n_indivi
                            const monsoon_sample_log* slog) {
   return rollout_logged_impl(h, "monsoon_rollout_sample", PLAY_SAMPLE, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns,
                              out_counts, out_results, out_steps, log, sm, xlog, slog);
+}
+
+// monsoon_rollout_sample's call with the rule of the row that moves: the tables' checks, then rollout_logged_impl's decision
+// which kernel plays -- a call whose thresholds are all 0 is one whose rule never fires.
+int monsoon_rollout_policies(monsoon_t* h, const double* weights, int32_t n_individuals, const monsoon_match* matches, int32_t n_matches,
+                             const uint8_t* deck_pairs, int32_t n_decks, int32_t max_turns, int32_t* out_counts, int8_t* out_results,
+                             int32_t* out_steps, const monsoon_rollout_log* log, const monsoon_policies* pol, const monsoon_explore_log* xlog,
+                             const monsoon_sample_log* slog) {
+  const char* who = "monsoon_rollout_policies";
+  if (!h) return MONSOON_ERR_ARG;
+  if (!pol || !pol->threshold || !pol->inv_temperature) return bad_arg(h, who, "pol, pol->threshold and pol->inv_temperature are required");
+  if (n_individuals <= 0) return bad_arg(h, who, "bad argument");
+  bool fires = false;
+  for (int r = 0; r < n_individuals; r++) {
+    if (!(pol->inv_temperature[r] >= 0.0 && pol->inv_temperature[r] < INFINITY))   // (a NaN fails the first test)
+      return bad_arg(h, who, "inv_temperature[" + std::to_string(r) + "] must be finite and >= 0");
+    fires |= pol->threshold[r] != 0;
+  }
+  // (threshold: "some row's is not 0" -- all that the choice of the kernel reads; the kernel reads the tables)
+  const monsoon_sample sm = {{pol->seed, fires ? 1u : 0u, pol->sides, pol->until_step}, 1.0};
+  return rollout_logged_impl(h, who, PLAY_POLICY, weights, n_individuals, matches, n_matches, deck_pairs, n_decks, max_turns, out_counts,
+                             out_results, out_steps, log, &sm, xlog, slog, pol);
 }
 
 // Matches [base, base + n) of a replay: load them, one launch plays every game's entries, the outcome comes back.

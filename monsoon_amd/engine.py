@@ -20,7 +20,8 @@ LOG_ARRAYS = (("action", np.uint8, 255, 1, "monsoon_rollout_logged"),
               ("taken_score", np.float64, np.nan, 8, "monsoon_rollout_explore"),
               ("weight_total", np.uint32, 0, 4, "monsoon_rollout_sample"),
               ("taken_weight", np.uint32, 0, 4, "monsoon_rollout_sample"))
-_LOG_ENTRIES = ("monsoon_rollout_logged", "monsoon_rollout_explore", "monsoon_rollout_sample")
+# ... in the order in which each logs its predecessors' arrays too; monsoon_rollout_policies introduces none of its own
+_LOG_ENTRIES = ("monsoon_rollout_logged", "monsoon_rollout_explore", "monsoon_rollout_sample", "monsoon_rollout_policies")
 
 
 def _log_arrays(entry):
@@ -93,6 +94,57 @@ class Explore:
         return _lib.Sample(self.c_struct(), self.inv_temperature)
 
 
+class Policies:
+    """An exploration rule per individual of a logged rollout (monsoon_policies, include/monsoon.h): a heuristic decision
+    reads eps and temperature of the weight row that moves -- match p1 when FIRST is to play, p2 when SECOND is.  eps and
+    temperature are array-likes with one entry per row of the weight table: eps in [0, 1] (0: the row plays greedily),
+    temperature > 0, numpy.inf the uniform rule (inv_temperature 0.0: every legal action weighs the same).  seed, sides and
+    until_step are call-wide, as on Explore.  The log carries weight_total and taken_weight on every decision the rule covers
+    -- the side's bit, the step limit, eps > 0 -- sampled or not: game_log.behaviour_prob is the exact probability the
+    behaviour policy gave every committed action."""
+    SIDES = Explore.SIDES
+    samples = True          # the log carries weight_total and taken_weight
+    per_individual = True   # the rule is a table over the weight rows
+
+    def __init__(self, eps, temperature, seed, sides="both", until_step=0):
+        eps, temperature = np.asarray(eps, dtype=np.float64), np.asarray(temperature, dtype=np.float64)
+        if eps.ndim != 1 or temperature.shape != eps.shape:
+            raise ValueError(f"Policies: eps and temperature are one-dimensional and equally long, got shapes {eps.shape} and {temperature.shape}")
+        if not ((eps >= 0.0) & (eps <= 1.0)).all():   # (a NaN fails it too)
+            raise ValueError("Policies: every eps must lie in [0, 1]")
+        if not (temperature > 0.0).all():   # (likewise)
+            raise ValueError("Policies: every temperature must be > 0 (numpy.inf: the uniform rule)")
+        if sides not in self.SIDES:
+            raise ValueError(f"Policies: sides is one of {tuple(self.SIDES)}, got {sides!r}")
+        with np.errstate(over="ignore"):
+            inv = 1.0 / temperature
+        if not np.isfinite(inv).all():   # (a subnormal T)
+            raise ValueError("Policies: 1 / temperature is not finite for every row")
+        self.eps, self.temperature, self._inv = eps.copy(), temperature.copy(), np.ascontiguousarray(inv)
+        self._thresholds = np.minimum(np.floor(eps * 2.0**32), float(0xFFFFFFFF)).astype(np.uint32)   # (Explore.threshold per row: exact in float64)
+        self.seed, self.sides, self.until_step = int(seed) & 0xFFFFFFFF, sides, int(until_step)
+        self.side_bits = self.SIDES[sides]
+
+    def __len__(self):
+        return len(self._thresholds)
+
+    @property
+    def thresholds(self):
+        """uint32[n_individuals]: row r's decisions leave the arg-max iff draw0 < thresholds[r]."""
+        return self._thresholds
+
+    @property
+    def inv_temperatures(self):
+        """float64[n_individuals]: 1 / temperature, what the device multiplies by (0.0 for numpy.inf)."""
+        return self._inv
+
+    may_explore = Explore.may_explore
+
+    def c_struct(self):
+        """monsoon_policies over this object's two tables (which it keeps alive)."""
+        return _lib.Policies(self.seed, self.side_bits, self.until_step, _ptr(self._thresholds), _ptr(self._inv))
+
+
 class RolloutLog:
     """What a logged rollout played (monsoon_rollout_logged): entry k of row i is game i's k-th committed step.
     action uint8[n][max_turns] (255 behind the last step), score float64[n][max_turns] or None (the decision's best score;
@@ -104,7 +156,9 @@ class RolloutLog:
     step and behind); None otherwise.
     A rollout with a sampling rule (Explore(temperature=), monsoon_rollout_sample) adds to those weight_total
     uint32[n][max_turns] (the sum of the decision's 24-bit softmax weights) and taken_weight uint32[n][max_turns] (the weight
-    of the committed action); both 0 for a bot step, a decision that did not sample, and behind; None otherwise."""
+    of the committed action); both 0 for a bot step, a decision that did not sample, and behind; None otherwise.
+    A rollout with a Policies table (monsoon_rollout_policies) has the same arrays; weight_total and taken_weight are there
+    written on every decision the rule covers, sampled or not (game_log.behaviour_prob)."""
 
     def __init__(self, action, score, n_legal, steps, greedy=None, explored=None, taken_score=None, weight_total=None, taken_weight=None):
         self.action, self.score, self.n_legal, self.steps = action, score, n_legal, steps
@@ -468,10 +522,16 @@ class BatchEngine:
         explore = an Explore: monsoon_rollout_explore, the same call whose heuristic decisions may commit a drawn legal
         action; the log also carries greedy, explored and taken_score, and the counts describe the games that were played --
         they are not fitness.  An Explore with a temperature: monsoon_rollout_sample, whose decisions draw from the softmax
-        over their scores; the log carries weight_total and taken_weight too (RolloutLog.taken_prob)."""
+        over their scores; the log carries weight_total and taken_weight too (RolloutLog.taken_prob).  A Policies:
+        monsoon_rollout_policies, the sampling call with the rule of the row that moves; its table has a row per row of
+        `weights` (ValueError otherwise)."""
         sample = explore is not None and explore.samples
+        table = getattr(explore, "per_individual", False)
+        if table and len(explore) != len(weights):
+            raise ValueError(f"rollout_logged: the Policies table has {len(explore)} rows, the weight table {len(weights)}")
         log = RolloutLog.empty(len(matches), max_turns, scores, n_legal, explore is not None, sample)
-        entry = "monsoon_rollout_logged" if explore is None else "monsoon_rollout_sample" if sample else "monsoon_rollout_explore"
+        entry = ("monsoon_rollout_logged" if explore is None else "monsoon_rollout_policies" if table else "monsoon_rollout_sample" if sample
+                 else "monsoon_rollout_explore")
         return self._rollout(entry, weights, matches, deck_pairs, max_turns, True, log, explore) + (log,)
 
     @staticmethod
@@ -502,7 +562,7 @@ class BatchEngine:
             extra = (ctypes.byref(c_logs[0]),)
             entry_bytes = 11   # a logged call's batches are cut by the log's budget too ...
             if explore is not None:   # ... an exploring or sampling call's by the arrays it asks for (include/monsoon.h)
-                c_ex = explore.c_sample() if explore.samples else explore.c_struct()
+                c_ex = explore.c_struct() if not explore.samples or getattr(explore, "per_individual", False) else explore.c_sample()
                 extra += (ctypes.byref(c_ex),) + tuple(ctypes.byref(c) for c in c_logs[1:_LOG_ENTRIES.index(entry) + 1])
                 entry_bytes = _entry_bytes(**{name: getattr(log, name) is not None for name in _log_arrays(entry)})
             batch = min(batch, max(1, LOG_BUDGET // (entry_bytes * max_turns)))

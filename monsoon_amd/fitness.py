@@ -318,6 +318,7 @@ class FitnessEvaluator:
         """The games of a schedule with their logs, on this evaluator's engines (game_log.logged_rollout): what a
         champion played, step by step.  deck_pairs None: config.deck on both sides.  explore = an engine.Explore: the
         games leave the champion's line where its draws say so, and the log keeps the champion's choice (log.greedy).
+        An engine.Policies (a rule per row of `weights`) passes through unchanged: sub-schedules keep their row indices.
         Returns (counts, results, steps, faults, log); the evaluator's statistics are left alone."""
         from .game_log import logged_rollout
         if deck_pairs is None:

@@ -8,7 +8,8 @@ candidate column (CANDIDATE_COLUMNS) every row also carries the afterstates of i
 which candidates / candidate_mask hand to vec_env.select_actions and to a learner over afterstate features.  A rollout
 with an engine.Explore rule logs games that leave the champion's line; its log keeps the arg-max of every decision
 (greedy) and which decisions explored, explore_draws recomputes the draws, and dataset hands both out as row columns
-(LOG_COLUMNS).
+(LOG_COLUMNS).  A rollout with an engine.Policies table (a rule per individual) logs the softmax weights of every decision
+its rule covers; behaviour_prob turns them into the probability the behaviour policy gave each committed action.
 """
 import numpy as np
 
@@ -73,7 +74,8 @@ def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, exp
     explore = an engine.Explore: every tier plays with that rule (the draws are keyed by the match's seed and the step, so a
     game played again on a larger record explores as it did on the smaller one) and the log carries greedy, explored and
     taken_score; the counts then describe explored games, not fitness.  A rule with a temperature (the sampling rule) goes
-    through the tiers the same way, and the log carries weight_total and taken_weight too.
+    through the tiers the same way, and the log carries weight_total and taken_weight too.  An engine.Policies (a rule per
+    row of `weights`, monsoon_rollout_policies) likewise: a sub-schedule keeps its row indices, so every tier reads the same table.
     Returns (counts[n_rows][3], results, steps, faults, log)."""
     log = RolloutLog.empty(len(matches), max_turns, explore=explore is not None,
                            sample=explore is not None and getattr(explore, "samples", False))
@@ -84,6 +86,37 @@ def logged_rollout(engine_for_tier, weights, matches, deck_pairs, max_turns, exp
         c, r, s, lg = eng.rollout_logged(weights, sub, sub_pairs, max_turns, **how)
         return c, r, s, eng.rollout_faults(len(sub)), lg
     return _ladder(play, len(weights), matches, deck_pairs, put=log.put)[:4] + (log,)
+
+
+def behaviour_prob(policies, matches, log, sides):
+    """float64[n][max_turns]: the probability with which the behaviour policy of a rollout under `policies` (an
+    engine.Policies) committed each logged action.  sides = (to_play, bot) as step_sides returns them.  A decision of weight
+    row r (p1 of its match when FIRST played, p2 when SECOND did) that the rule covers -- the side's bit, the step limit,
+    thresholds[r] > 0 -- with weight_total > 0 has, with eps_r = thresholds[r] / 2**32,
+        mu = (1 - eps_r) * [action == greedy] + eps_r * taken_weight / weight_total,
+    sampled or not (include/monsoon.h monsoon_rollout_policies).  Every other decision committed its arg-max: 1.0.  Steps of
+    the scripted bot, entries the replay did not reach and the padding are NaN."""
+    if not getattr(policies, "per_individual", False) or log.weight_total is None or log.taken_weight is None or log.greedy is None:
+        raise ValueError("behaviour_prob needs an engine.Policies and the log of a rollout under it")
+    to_play, bot = (np.asarray(a) for a in sides)
+    matches = np.asarray(matches)
+    if to_play.shape != log.action.shape or bot.shape != log.action.shape or len(matches) != len(to_play):
+        raise ValueError("behaviour_prob: sides has the shape of the log, one row per match")
+    k = np.arange(log.action.shape[1])[None, :]
+    decision = (to_play >= 0) & ~bot.astype(bool) & (k < np.asarray(log.steps)[:, None])
+    row = np.where(to_play == 0, matches["p1"][:, None], matches["p2"][:, None])
+    row = np.where(decision, row, 0)   # (a bot's -1 indexes nothing)
+    if decision.any() and not (0 <= row[decision].min() and row[decision].max() < len(policies)):
+        raise ValueError("behaviour_prob: a match names a row outside the Policies table")
+    threshold = policies.thresholds[row]
+    covered = decision & policies.may_explore(np.maximum(to_play, 0), k) & (threshold > 0) & (log.weight_total > 0)
+    eps = threshold.astype(np.float64) / 2.0**32
+    ratio = np.zeros(log.action.shape)
+    np.divide(log.taken_weight, log.weight_total, out=ratio, where=covered)
+    out = np.full(log.action.shape, np.nan)
+    out[decision] = 1.0
+    out[covered] = ((1.0 - eps) * (log.action == log.greedy) + eps * ratio)[covered]
+    return out
 
 
 def replay(engine, matches, deck_pairs, log):
@@ -126,7 +159,7 @@ COLUMNS = {"obs": ("int32", (27, 5, 4)), "legal": ("uint8", (156,)), "obs_raises
 ROW_BYTES = {"obs": 2160, "legal": 156, "obs_raises": 1, "to_play": 1, "action": 1, "bot": 1, "game": 4, "step": 4, "state_hash": 8}
 # ... those gathered on the host from the arrays of an exploring rollout's log at the kept entries (no replay involved):
 # greedy is the teacher's label of a row whose action was explored, explored marks such rows
-# ; weight_total and taken_weight are a sampling rollout's (the log's uint32 values, as int64 tensors)
+# ; weight_total and taken_weight are a sampling rollout's or a Policies rollout's (the log's uint32 values, as int64 tensors)
 LOG_COLUMNS = {"greedy": ("uint8", ()), "explored": ("uint8", ()), "weight_total": ("int64", ()), "taken_weight": ("int64", ())}
 # ... and of monsoon_replay_after, "K" = max_after: the candidates the row's choice was made among, entry k the k-th legal
 # action in ascending order.  Naming one of them turns the look-ahead on; _CANDIDATE_BASE comes along, as action does.
@@ -229,7 +262,7 @@ def _log_columns(log, names):
     missing = [c for c in want if getattr(log, c, None) is None]
     if missing:
         raise ValueError(f"column(s) {missing} need the log of a rollout with an Explore rule (rollout_logged(..., explore=); "
-                         "weight_total / taken_weight: one with a temperature)")
+                         "weight_total / taken_weight: one with a temperature or a Policies table)")
     return want
 
 
