@@ -76,7 +76,7 @@ enum {
   PS_STEP, PS_PLAYER_PLAY, PS_NEW_ENTITY, PS_RUN_ABILITY, PS_ABILITY_ENTITY, PS_ABILITY_SPELL, PS_GET_TARGETS, PS_SHAPE_TILES,
   PS_SHAPE_TARGETS, PS_DEAL_DAMAGE, PS_DESTROY, PS_FRONT_LINE, PS_SET_PATH, PS_MOVE, PS_COMMAND, PS_FORCE_ATTACK, PS_DRAW,
   PS_FLIP, PS_NEXT_TURN, PS_LEGAL, PS_SHUFFLE, PS_SORTED_HEAD, PS_SPAWN, PS_RESPAWN, PS_TELEPORT, PS_PUSH_PULL, PS_EMPTY_FRONT,
-  PS_BEGIN_STEP, PS_OBS_RAISES, PS_FEATURES, PS_COUNT
+  PS_BEGIN_STEP, PS_OBS_RAISES, PS_FEATURES, PS_DISCARD, PS_COUNT
 };
 
 

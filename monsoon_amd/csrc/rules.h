@@ -429,6 +429,145 @@ struct Engine {
 #endif
     m.st8(pl(o, P_DECK_N), n + 1);
   }
+#if !(defined(MSB_EXT) && MSB_EXT)
+  // ---- the lists on whole words (state.h MSB_WIDE_LISTS) ---------------------------------------------------------
+  // The standard record's player block is six granules: {base, mana, max_mana, front, flags | faction, hand_n, deck_n, pad |
+  // hand[0]}, hand[1..4], deck[0..3], deck[4..7], deck[8..11], {ages 0..11, pad}.  A discard and the tail of a draw read the
+  // granules they need at once, compute the lists in registers and write them back: the same bytes as the loops above leave,
+  // also where the call faults, without a dependent LDS round trip per entry.
+  static_assert(P_FACTION == 8 && P_HAND_N == 9 && P_DECK_N == 10 && P_HAND == 12 && P_DECK == 32 && P_AGE == 80 && PL_SIZE == 96 &&
+                    HAND_CAP == 5 && DECK_CAP == 12,
+                "the six granules of a player block");
+  // 0xFF in byte k of the result for every set bit k of the low four bits
+  MSB_HD MSB_INL static uint32_t bits_to_bytes(uint32_t bits) { return (((bits & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu; }
+  MSB_HD MSB_INL static uint32_t pl_counts(uint32_t hdr, int hand_n, int deck_n) {   // the {faction, hand_n, deck_n, pad} word
+    return (hdr & 0xff0000ffu) | ((uint32_t)(hand_n & 0xff) << 8) | ((uint32_t)(deck_n & 0xff) << 16);
+  }
+  // what first_equal() decides about the earliest earlier entry `first` of the same card (its flags in bits 16..23), for a
+  // chosen entry that is `positioned`: 0 = it is the equal one, else the fault code
+  MSB_HD MSB_INL static int first_equal_fault(uint32_t first, int positioned) {
+    const int pi = (int)(first >> 16) & (CF_ALIAS | CF_STR);
+    if (!pi && !positioned) return 0;
+    return (pi && positioned) ? FAULT_UNSUPPORTED : FAULT_PY_EXCEPTION;
+  }
+  // Player.discard of hand entry idx, whose four bytes are `target`.  Returns false if the step has faulted.
+  MSB_HD MSB_INL bool discard_wide(int o, int idx, uint32_t target) {
+    const int g = pg(o);
+    msb_u32x4 g0 = m.ld128g(g), g1 = m.ld128g(g + 1);
+    const msb_u32x4 ga = m.ld128g(g + 5);
+    const int faulted = fault();   // (a fault from before the call: the loops stop behind reweight then)
+    const int hn = (int)(g0[2] >> 8) & 0xff, dn = (int)(g0[2] >> 16) & 0xff;
+    // reweight: the words below the first one that holds an age at AGE_MAX gain their ones, that one and the rest stay
+    uint32_t a[3] = {ga[0], ga[1], ga[2]};
+    bool stop = false;
+    for (int w = 0; w < 3; w++) {
+      const int k = dn - 4 * w;
+      const uint32_t t = ~a[w];   // a byte of a[w] is 0xFF <=> that byte of t is 0
+      stop = stop || (k > 0 && ((t - 0x01010101u) & ~t & 0x80808080u) != 0);
+      const uint32_t one = k >= 4 ? 0x01010101u : (k > 0 ? (0x01010101u >> (8 * (4 - k))) : 0u);
+      a[w] = stop ? a[w] : a[w] + one;
+    }
+    if (stop || faulted) {
+      m.st128g(g + 5, msb_u32x4{a[0], a[1], a[2], ga[3]});
+      if (stop) set_fault(FAULT_CAP_DECK);
+      return false;
+    }
+    // hand.remove(target): the first equal entry.  Spells compare by identity, and the same object is never listed earlier
+    const uint32_t h[5] = {g0[3], g1[0], g1[1], g1[2], g1[3]};
+    const uint32_t card = target & 0xffu;
+    uint32_t eq = 0;
+    for (int i = 0; i < 5; i++) eq |= (uint32_t)((h[i] & 0xffu) == card) << i;
+    eq &= (1u << idx) - 1u;
+    int j = idx;
+    if (eq != 0 && card_eq_by_id((int)card)) {
+      j = __builtin_ctz(eq);
+      const uint32_t first = j == 0 ? h[0] : (j == 1 ? h[1] : (j == 2 ? h[2] : h[3]));
+      const int code = first_equal_fault(first, (int)(target >> 16) & (CF_ALIAS | CF_STR));
+      if (code) {
+        m.st128g(g + 5, msb_u32x4{a[0], a[1], a[2], ga[3]});
+        set_fault(code);
+        return false;
+      }
+    }
+    // del hand[j]: entries j.. move down, the one past the new end keeps its bytes
+    uint32_t nh[5];
+    for (int i = 0; i < 4; i++) nh[i] = (i >= j && i + 1 < hn) ? h[i + 1] : h[i];
+    nh[4] = h[4];
+    // deck.append(target) with weight 1, unless the card is single use
+    int dn2 = dn;
+    bool full = false;
+    if (!((target >> 16) & CF_SINGLE_USE)) {
+      full = dn >= DECK_CAP;
+      if (!full) {
+        m.st32(pl(o, P_DECK + 4 * dn), target);
+        const uint32_t keep = ~(0xffu << (8 * (dn & 3)));
+        for (int w = 0; w < 3; w++) a[w] = (dn >> 2) == w ? (a[w] & keep) : a[w];
+        dn2 = dn + 1;
+      }
+    }
+    g0[2] = pl_counts(g0[2], hn - 1, dn2);
+    g0[3] = nh[0];
+    m.st128g(g, g0);
+    m.st128g(g + 1, msb_u32x4{nh[1], nh[2], nh[3], nh[4]});
+    m.st128g(g + 5, msb_u32x4{a[0], a[1], a[2], ga[3]});
+    if (full) set_fault(FAULT_CAP_DECK);
+    return !full;
+  }
+  // The tail of a draw that chose deck entry idx: choice.weight = 1, hand.append(choice), deck.remove(choice).  Returns false
+  // if the step has faulted.
+  MSB_HD MSB_INL bool draw_take_wide(int o, int idx) {
+    const int g = pg(o);
+    const uint32_t hdr = m.ld32g(g, P_FACTION);
+    const uint32_t choice = m.ld32(pl(o, P_DECK + 4 * idx));
+    const msb_u32x4 d0 = m.ld128g(g + 2), d1 = m.ld128g(g + 3), d2 = m.ld128g(g + 4), ga = m.ld128g(g + 5);
+    const int faulted = fault();   // (a fault from before the call: the loops stop behind the append then)
+    const int hn = (int)(hdr >> 8) & 0xff, n = (int)(hdr >> 16) & 0xff;
+    uint32_t a[3] = {ga[0], ga[1], ga[2]};
+    {
+      const uint32_t keep = ~(0xffu << (8 * (idx & 3)));
+      for (int w = 0; w < 3; w++) a[w] = (idx >> 2) == w ? (a[w] & keep) : a[w];
+    }
+    if (hn >= HAND_CAP) {
+      m.st128g(g + 5, msb_u32x4{a[0], a[1], a[2], ga[3]});
+      set_fault(FAULT_CAP_HAND);
+      return false;
+    }
+    m.st32(pl(o, P_HAND + 4 * hn), choice);
+    const uint32_t d[12] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3], d2[0], d2[1], d2[2], d2[3]};
+    const uint32_t card = choice & 0xffu;
+    uint32_t eq = 0;
+    for (int i = 0; i < 12; i++) eq |= (uint32_t)((d[i] & 0xffu) == card) << i;
+    eq &= (1u << idx) - 1u;
+    int j = idx, code = 0;
+    if (!faulted && eq != 0 && card_eq_by_id((int)card)) {
+      j = __builtin_ctz(eq);
+      code = first_equal_fault(m.ld32(pl(o, P_DECK + 4 * j)), (int)(choice >> 16) & (CF_ALIAS | CF_STR));
+    }
+    if (faulted || code) {
+      m.st32g(g, P_FACTION, pl_counts(hdr, hn + 1, n));
+      m.st128g(g + 5, msb_u32x4{a[0], a[1], a[2], ga[3]});
+      if (code) set_fault(code);
+      return false;
+    }
+    // del deck[j]: entries and ages j.. move down, the age past the new end is 0, everything behind it keeps its bytes
+    const uint32_t take = ((1u << (n - 1)) - 1u) & ~((1u << j) - 1u), zero = 1u << (n - 1);
+    uint32_t nd[12];
+    for (int i = 0; i < 11; i++) nd[i] = ((take >> i) & 1u) ? d[i + 1] : d[i];
+    nd[11] = d[11];
+    uint32_t na[3];
+    for (int w = 0; w < 3; w++) {
+      const uint32_t down = (a[w] >> 8) | (w < 2 ? a[w < 2 ? w + 1 : 2] << 24 : 0u);
+      const uint32_t tb = bits_to_bytes(take >> (4 * w)), zb = bits_to_bytes(zero >> (4 * w));
+      na[w] = (a[w] & ~(tb | zb)) | (down & tb);
+    }
+    m.st128g(g + 2, msb_u32x4{nd[0], nd[1], nd[2], nd[3]});
+    m.st128g(g + 3, msb_u32x4{nd[4], nd[5], nd[6], nd[7]});
+    m.st128g(g + 4, msb_u32x4{nd[8], nd[9], nd[10], nd[11]});
+    m.st128g(g + 5, msb_u32x4{na[0], na[1], na[2], ga[3]});
+    m.st32g(g, P_FACTION, pl_counts(hdr, hn + 1, n - 1));
+    return true;
+  }
+#endif
   // a brand-new card object (ua20's copy, b305's returning structure) appended to the deck / hand
   MSB_HD MSB_NOINLINE void push_new_instance(int o, bool to_hand, int card, int cost, int fl, int x) {
     int n = to_hand ? pl_hand_n(o) : pl_deck_n(o);
@@ -1732,6 +1871,80 @@ struct Engine {
   }
   MSB_HD MSB_A_SETPATH void set_path_impl(int e, bool on_play) {
     MSB_SCOPE(PS_SET_PATH);
+#if MSB_WIDE_PATH
+    // The first word of the unit's granule once for its position, movement and flags (one more byte for the confused count: the
+    // whole granule as a 16-byte read cost the extended and large builds scratch instructions); the tiles ahead and beside it out of
+    // two board-row words (the unit's own row holds both neighbours); the owners of the up to three entities there read
+    // together; "already a destination" asked of a tile mask kept beside the packed list.  A row off the board reads as empty.
+    static_assert(EO_CARD == 0 && EO_FLAGS == 1 && EO_POS == 2 && EO_MOV == 3, "word 0 of an entity");
+    const uint32_t ge = m.ld32g(eg(e), 0);   // {card, flags, pos, mov}
+    P position = tile_p((int)(ge >> 16) & 0xff);
+    int confused_cached = e_st(e, ST_CONFUSED);
+    const int owner = (int)(ge >> 8) & EF_OWNER;
+    const bool ff = ((ge >> 8) & EF_FF) != 0;
+    const bool is_local = owner == local();
+    const int steps = on_play ? (int)(ge >> 24) : 1;
+    uint32_t packed = 0;
+    int n = 0, nd = 0;
+    uint32_t seen = 0;   // the tiles among the first 8 destinations
+    for (int k = 0; k < steps; k++) {
+      P dest{position.x, position.y + (is_local ? -1 : 1)};
+      if (confused_cached > 0) {
+        int dx;
+        if (position.x == 0)
+          dx = 1;                                  // choice([1]): no draw
+        else if (position.x == 3)
+          dx = -1;                                 // choice([-1]): no draw
+        else
+          dx = rng_randint(0, 2) ? 1 : -1;         // choice([-1, 1])
+        dest = P{position.x + dx, position.y};
+        confused_cached--;
+      } else if (on_play && !ff && dest.y != (is_local ? -1 : 5)) {
+        const uint32_t row = (position.y >= 0 && position.y <= 4) ? board_row(position.y) : 0xffffffffu;
+        const uint32_t ahead = (dest.y >= 0 && dest.y <= 4) ? board_row(dest.y) : 0xffffffffu;
+        const int x = position.x;   // 0..3: a unit starts on the board and a confused step stays on its row
+        const int nxt = (int)(ahead >> (8 * x)) & 0xff;
+        const int left = x > 0 ? (int)(row >> (8 * (x > 0 ? x - 1 : 0))) & 0xff : SLOT_NONE;
+        const int right = x < 3 ? (int)(row >> (8 * (x < 3 ? x + 1 : 3))) & 0xff : SLOT_NONE;
+        // (an empty tile reads the unit's own flags: its owner is then not asked)
+        const int fn = m.ld8g(eg(nxt == SLOT_NONE ? e : nxt), EO_FLAGS), fl = m.ld8g(eg(left == SLOT_NONE ? e : left), EO_FLAGS),
+                  fr = m.ld8g(eg(right == SLOT_NONE ? e : right), EO_FLAGS);
+        if (nxt == SLOT_NONE || (fn & EF_OWNER) == owner) {
+          const bool left_ok = left != SLOT_NONE && (fl & EF_OWNER) != owner && !((seen >> ((position.y * 4 + x - 1) & 31)) & 1u);
+          const bool right_ok = right != SLOT_NONE && (fr & EF_OWNER) != owner && !((seen >> ((position.y * 4 + x + 1) & 31)) & 1u);
+          if (x <= 1) {
+            if (right_ok)
+              dest = P{x + 1, position.y};
+            else if (left_ok)
+              dest = P{x - 1, position.y};
+          } else {
+            if (left_ok)
+              dest = P{x - 1, position.y};
+            else if (right_ok)
+              dest = P{x + 1, position.y};
+          }
+        }
+      }
+      // Destinations past the first off-board one are never read (move returns at the base hit);
+      // they are clamped so that they stay encodable.
+      P enc = dest;
+      if (enc.y < -1) enc.y = -1;
+      if (enc.y > 5) enc.y = 5;
+      if (nd < 8) {
+        if (p_valid(enc)) seen |= 1u << p_tile(enc);
+        nd++;
+      }
+      if (n < PATH_CAP) {
+        packed |= (uint32_t)p_pack(enc) << (8 * n);
+        n++;
+      } else {
+        set_fault(FAULT_CAP_PATH);
+      }
+      position = dest;
+    }
+    e_set_path(e, packed);
+    m.st8g(eg(e), EO_PATHN, n);
+#else
     P position = e_pos(e);
     int confused_cached = e_st(e, ST_CONFUSED);
     int owner = e_owner(e);
@@ -1796,6 +2009,7 @@ struct Engine {
     }
     e_set_path(e, packed);
     m.st8g(eg(e), EO_PATHN, n);
+#endif
   }
 
   // Unit.move, unit.py:124-203.  Frame F_MOVE {hdr: state, e, recursion depth outside | MV_PLAYED; w1: the path list
@@ -2272,12 +2486,16 @@ struct Engine {
         set_fault(FAULT_PY_EXCEPTION);
         return;
       }
+#if MSB_WIDE_LISTS && !(defined(MSB_EXT) && MSB_EXT)
+      if (!draw_take_wide(o, idx)) return;
+#else
       set_deck_age(o, idx, 0);             // choice.weight = 1
       hand_push_from_deck(o, idx);         // self.hand.append(choice)
       if (fault()) return;
       int j = first_equal(o, false, idx);  // self.deck.remove(choice): first EQUAL element
       if (fault()) return;
       deck_remove_at(o, j);
+#endif
     }
   }
   // Player.fill_hand, player.py:54-55
@@ -2286,7 +2504,17 @@ struct Engine {
     if (need > 0) draw(o, need);
   }
   // Player.discard, player.py:57-66 (reweight: w*1.6+100 for every deck card)
+#if MSB_WIDE_LISTS && !(defined(MSB_EXT) && MSB_EXT)
+  // entry: the four bytes {card, cost, flags, x} of hand[hand_index], which the caller has read.  Returns false if the step
+  // has faulted.
+  MSB_HD MSB_INL bool discard(int o, int hand_index, uint32_t entry) {
+    MSB_SCOPE(PS_DISCARD);
+    return discard_wide(o, hand_index, entry);
+  }
+  MSB_HD MSB_INL void discard(int o, int hand_index) { discard(o, hand_index, hand_handle(o, hand_index)); }
+#else
   MSB_HD MSB_INL void discard(int o, int hand_index) {
+    MSB_SCOPE(PS_DISCARD);
     reweight(o);
     if (fault()) return;
     uint32_t target = hand_handle(o, hand_index);
@@ -2296,6 +2524,7 @@ struct Engine {
     hand_remove_at(o, j);
     if (!(fl & CF_SINGLE_USE)) deck_push_handle(o, target);
   }
+#endif
   // Board.add_to_history, board.py:324-325 (only the last four are observable)
   MSB_HD MSB_INL void add_history(int owner, int card) {
     // four {owner, card} byte pairs, oldest first, as one 64-bit word: append, or drop the oldest and append
@@ -2311,6 +2540,19 @@ struct Engine {
     m.st64(H_HIST, h);
   }
   // Player.play, player.py:68-77.  has_pos=false <=> position None
+  // (-DMSB_WIDE_LISTS=0: the entry's fields byte by byte, the discard by its loops)
+#if MSB_WIDE_LISTS && !(defined(MSB_EXT) && MSB_EXT)
+  MSB_HD MSB_INL void call_player_play(Wk& k, int o, int index, P position, bool has_pos) {
+    call_player_play(k, o, index, hand_handle(o, index), position, has_pos);
+  }
+  // entry: the four bytes {card, cost, flags, x} of hand[index], which the caller has read
+  MSB_HD MSB_INL void call_player_play(Wk& k, int o, int index, uint32_t entry, P position, bool has_pos) {
+    MSB_SCOPE(PS_PLAYER_PLAY);
+    int card = (int)(entry & 0xffu), fl = (int)(entry >> 16) & 0xff;
+    int strength = inst_strength(card, fl, (int)(entry >> 24));   // target.copy() copies the instance's strength
+    add_history(o, card);
+    if (!discard(o, index, entry)) return;
+#else
   MSB_HD MSB_INL void call_player_play(Wk& k, int o, int index, P position, bool has_pos) {
     MSB_SCOPE(PS_PLAYER_PLAY);
     int card = hand_card(o, index), fl = hand_flags(o, index);
@@ -2318,6 +2560,7 @@ struct Engine {
     add_history(o, card);
     discard(o, index);
     if (fault()) return;
+#endif
     const CardInfo& ci = g_cards[card];
     if (ci.kind == KIND_UNIT) {
       int e = new_entity(card, o, strength, ci.movement, (fl & CF_FF) != 0);   // target.copy()
@@ -2360,9 +2603,15 @@ struct Engine {
 #if MSB_COOP_DRAW && !(defined(MSB_EXT) && MSB_EXT)
     // what the wave resolved for this decision's REPLACE candidates (0 where it did not, and in every other kernel):
     // byte 0 for a replaced card that goes back to the deck, byte 1 for a single-use card, which does not
+#if MSB_WIDE_LISTS
+    const uint32_t entry = hand_handle(o, hand_index);
+    const int appended = !((entry >> 16) & CF_SINGLE_USE);
+    if (!discard(o, hand_index, entry)) return;
+#else
     const int appended = !(hand_flags(o, hand_index) & CF_SINGLE_USE);
     discard(o, hand_index);
     if (fault()) return;
+#endif
     draw(o, 1, (int)((M::draw_hint() >> (appended ? 0 : 8)) & 0xff));
 #else
     discard(o, hand_index);
@@ -2554,9 +2803,16 @@ struct Engine {
       int idx = place ? action & 15 : (action - 64) % 21;
       if (idx < 20) {
         P pos{idx & 3, 4 - (idx >> 2)};
+#if MSB_WIDE_LISTS && !(defined(MSB_EXT) && MSB_EXT)
+        const uint32_t entry = hand_handle(lo, ci);   // {card, cost, flags, x}: one read for the play
+        bool has_pos = place || g_cards[entry & 0xffu].tgt.has != 0;
+        set_pl_mana(lo, pl_mana(lo) - (int)((entry >> 8) & 0xffu));
+        call_player_play(k, lo, ci, entry, pos, has_pos);
+#else
         bool has_pos = place || g_cards[hand_card(lo, ci)].tgt.has != 0;
         set_pl_mana(lo, pl_mana(lo) - hand_cost(lo, ci));
         call_player_play(k, lo, ci, pos, has_pos);
+#endif
       }
     } else if (action < 152) {
       cycle(lo, action - 148);

@@ -191,6 +191,20 @@ constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
 #ifndef MSB_TARGET_SCAN
 #define MSB_TARGET_SCAN 1
 #endif
+// The hand, deck and age bookkeeping of a play or a REPLACE on whole words and granules (rules.h discard_wide, draw_take_wide,
+// the hand entry read once per play): standard record only, whose player block is six granules -- hand[0] is word 3 of granule 0,
+// hand[1..4] granule 1, the twelve deck entries granules 2..4, the twelve ages words 0..2 of granule 5.  The extended and large
+// records list object ids, an object may be listed twice and their blocks are not granule-aligned: they keep the loops.
+// 0 builds the per-entry loops everywhere; tests/wide_lists_check.cpp compiles the core once with each text into one program and
+// holds one against the other, so the 0 text always compiles.
+#ifndef MSB_WIDE_LISTS
+#define MSB_WIDE_LISTS 1
+#endif
+// Unit.set_path on the first word of the entity's granule and the board's row words (rules.h set_path_impl): every record
+// build.  0 builds the per-tile reads everywhere; the same program holds one text against the other.
+#ifndef MSB_WIDE_PATH
+#define MSB_WIDE_PATH 1
+#endif
 constexpr int LDS_RECORDS = WK_OVF_LDS + 16;        // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before

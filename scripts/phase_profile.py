@@ -72,7 +72,7 @@ def main():
 SCOPES = ["step", "player_play", "new_entity", "run_ability", "ability_entity", "ability_spell", "get_targets", "shape_tiles",
           "shape_targets", "deal_damage", "destroy", "front_line", "set_path", "move", "run() loop", "F_EACH", "draw",
           "next_turn prefix", "F_TURN", "legal_mask", "shuffle", "sorted_head", "spawn", "respawn", "teleport", "push_pull", "empty_front",
-          "begin_step", "obs_raises", "features"]
+          "begin_step", "obs_raises", "features", "discard"]
 
 
 if __name__ == "__main__":
