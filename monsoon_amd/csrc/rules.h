@@ -671,6 +671,79 @@ struct Engine {
   MSB_HD MSB_INL bool e_confused(int e) const { return e_st(e, ST_CONFUSED) > 0; }
   MSB_HD MSB_INL bool e_frozen(int e) const { return e_st(e, ST_FROZEN) > 0; }
 
+#if MSB_WE_ANY
+  // ---- the header word and the entity image (state.h MSB_WIDE_ENT; standard record) ---------------------------------------
+  // hdr_word(): bytes 0..7 of the record, one 64-bit read; hw_*(h): its fields.  INVARIANT: a header value is valid until the
+  // next call that can store to bytes 0..7 -- set_fault, any call_*, push_trigger / pop_trigger, a store of H_DEPTH, H_TRIG_N or
+  // H_RESOLVING (and ctx_enter / ctx_leave on the records with worlds, which is why those records do not build this text) -- and is
+  // read again after every such call; where the holder itself made the store it knows the new byte.  fault() after a nested call
+  // is the re-read header.  ei_load(e): entity e's granule, one 16-byte read; ei_*(g, e): its fields.  An image is valid until the
+  // next nested call; the holder's own stores to the granule are repeated on the image.
+  // THE DEFAULT BUILD DOES NOT HOLD A HEADER VALUE (MSB_WIDE_ENT_HDR is 0, state.h: measured, and left out next to the image):
+  // there hdr_word() reads nothing, the `h` a handler passes along is a placeholder, and hw_fault(h), hw_depth(h), hw_trig_n(h),
+  // hw_resolving(h), hw_cp(h), hw_local(h) each read their own byte at the place where they stand, as the per-field text does --
+  // nothing is held across a store.  The invariant above is the one the -DMSB_WIDE_ENT_HDR=1 text keeps, which
+  // tests/wide_ent_check.cpp builds and holds against the other two.  Each use site below says so again.
+  static_assert(H_TOPLAY == 0 && H_FAULT == 1 && H_HIST_N == 2 && H_TRIG_N == 3 && H_RESOLVING == 4 && H_PHASE == 5 && H_DEPTH == 6 && H_CP == 7,
+                "the header word");
+  static_assert(EO_FLAGS == 1 && EO_POS == 2 && EO_ST == 4 && EO_MOVEID == 9 && EO_STR == 10 && EO_PATHN == 14 && EO_KIND == 15, "the entity image");
+#if MSB_WE_HDR
+  MSB_HD MSB_INL uint64_t hdr_word() const { return m.ld64(0); }
+  MSB_HD MSB_INL int hw_local(uint64_t h) const { return (int)(h & 0xff); }
+  MSB_HD MSB_INL int hw_fault(uint64_t h) const { return (int)(h >> 8) & 0xff; }
+  MSB_HD MSB_INL int hw_trig_n(uint64_t h) const { return (int)(h >> 24) & 0xff; }
+  MSB_HD MSB_INL int hw_resolving(uint64_t h) const { return (int)(h >> 32) & 0xff; }
+  MSB_HD MSB_INL int hw_phase(uint64_t h) const { return (int)(h >> 40) & 0xff; }
+  MSB_HD MSB_INL int hw_depth(uint64_t h) const { return (int)(h >> 48) & 0xff; }
+  MSB_HD MSB_INL int hw_cp(uint64_t h) const { return (int)(h >> 56); }
+#else
+  MSB_HD MSB_INL uint64_t hdr_word() const { return 0; }
+  MSB_HD MSB_INL int hw_local(uint64_t) const { return local(); }
+  MSB_HD MSB_INL int hw_fault(uint64_t) const { return fault(); }
+  MSB_HD MSB_INL int hw_trig_n(uint64_t) const { return m.ld8(H_TRIG_N); }
+  MSB_HD MSB_INL int hw_resolving(uint64_t) const { return m.ld8(H_RESOLVING); }
+  MSB_HD MSB_INL int hw_phase(uint64_t) const { return phase(); }
+  MSB_HD MSB_INL int hw_depth(uint64_t) const { return m.ld8(H_DEPTH); }
+  MSB_HD MSB_INL int hw_cp(uint64_t) const { return cp(); }
+#endif
+  MSB_HD MSB_INL int hw_remote(uint64_t h) const { return hw_local(h) ^ 1; }
+  // (four words, not one 16-byte value: each word lives in a register of its own and dies where its last field is asked for)
+  struct EImg {
+    uint32_t w0, w1, w2, w3;
+  };
+#if MSB_WE_IMG
+  MSB_HD MSB_INL EImg ei_load(int e) const {
+    const msb_u32x4 v = m.ld128g(eg(e));
+    return EImg{v[0], v[1], v[2], v[3]};
+  }
+  MSB_HD MSB_INL int ei_flags(const EImg& g, int) const { return (int)(g.w0 >> 8) & 0xff; }
+  MSB_HD MSB_INL int ei_tile(const EImg& g, int) const { return (int)(g.w0 >> 16) & 0xff; }
+  MSB_HD MSB_INL int ei_st(const EImg& g, int, int s) const { return s < 4 ? (int)(g.w1 >> (8 * s)) & 0xff : (int)(g.w2 & 0xff); }
+  MSB_HD MSB_INL int ei_moveid(const EImg& g, int) const { return (int)(g.w2 >> 8) & 0xff; }
+  MSB_HD MSB_INL int ei_str(const EImg& g, int) const { return (int)(int16_t)(g.w2 >> 16); }
+  MSB_HD MSB_INL int ei_pathn(const EImg& g, int) const { return (int)(g.w3 >> 16) & 0xff; }
+  MSB_HD MSB_INL int ei_kind(const EImg& g, int) const { return (int)(g.w3 >> 24); }
+#else
+  MSB_HD MSB_INL EImg ei_load(int) const { return EImg{0, 0, 0, 0}; }
+  MSB_HD MSB_INL int ei_flags(const EImg&, int e) const { return e_flags(e); }
+  MSB_HD MSB_INL int ei_tile(const EImg&, int e) const { return m.ld8g(eg(e), EO_POS); }
+  MSB_HD MSB_INL int ei_st(const EImg&, int e, int s) const { return e_st(e, s); }
+  MSB_HD MSB_INL int ei_moveid(const EImg&, int e) const { return m.ld8g(eg(e), EO_MOVEID); }
+  MSB_HD MSB_INL int ei_str(const EImg&, int e) const { return e_str(e); }
+  MSB_HD MSB_INL int ei_pathn(const EImg&, int e) const { return m.ld8g(eg(e), EO_PATHN); }
+  MSB_HD MSB_INL int ei_kind(const EImg&, int e) const { return e_kind(e); }
+#endif
+  // the holder's own stores, repeated on the image
+  MSB_HD MSB_INL static void ei_put8(EImg& g, int byte, int v) {
+    const int w = byte >> 2, sh = 8 * (byte & 3);
+    uint32_t& x = w == 0 ? g.w0 : (w == 1 ? g.w1 : (w == 2 ? g.w2 : g.w3));
+    x = (x & ~(0xffu << sh)) | ((uint32_t)(v & 0xff) << sh);
+  }
+  MSB_HD MSB_INL static void ei_put_str(EImg& g, int v) { g.w2 = (g.w2 & 0xffffu) | ((uint32_t)(v & 0xffff) << 16); }
+  MSB_HD MSB_INL static int kind_trigger(int k) { return (k & EK_UNIT) ? ((k >> 2) & 15) - 1 : TR_NONE; }   // e_trigger
+  MSB_HD MSB_INL static int kind_card_trigger(int k) { return ((k >> 2) & 15) - 1; }                        // e_card_trigger
+#endif
+
   // ------------------------------------------------------------------------------------------
   // Board primitives
   // ------------------------------------------------------------------------------------------
@@ -1201,6 +1274,35 @@ struct Engine {
 
   // Board.calculate_front_line, board.py:78-92.  `player` is an order; the reference compares
   // Player objects by order (player.py:39-40).
+#if MSB_WE_ANY
+  MSB_HD MSB_A_FRONT void calculate_front_line(int player) { front_line_core(player, local()); }
+  // `lo` = board.local's order, which a caller that has read it passes on.  An order is 0 or 1, so the player whose line this is
+  // is `lo` where it is the local one and the other one where it is not: the line is stored under `player` either way.
+  MSB_HD MSB_INL void front_line_core(int player, int lo) {
+    // any(board[y][x] is not None and board[y][x].player == player for x in range(4)) per row: the first
+    // (local: lowest y, remote: highest y) row holding one of the player's entities; only occupied tiles are read
+    const uint32_t r0 = board_row(0), r1 = board_row(1), r2 = board_row(2), r3 = board_row(3), r4 = board_row(4);
+    uint32_t occ = row_occ4(r0) | (row_occ4(r1) << 4) | (row_occ4(r2) << 8) | (row_occ4(r3) << 12) | (row_occ4(r4) << 16);
+    const unsigned long long b01 = (unsigned long long)r0 | ((unsigned long long)r1 << 32);
+    const unsigned long long b23 = (unsigned long long)r2 | ((unsigned long long)r3 << 32);
+    const bool is_local = player == lo;
+    int found = -1;
+    while (occ) {
+      const int t = is_local ? __builtin_ctz(occ) : 31 - __builtin_clz(occ);
+      occ &= ~(1u << t);
+      const unsigned long long bw = t < 8 ? b01 : (t < 16 ? b23 : (unsigned long long)r4);
+      const int s = (int)((bw >> (8 * (t & 7))) & 0xff);
+      if (e_owner(s) == player) {
+        found = t >> 2;
+        break;
+      }
+    }
+    if (is_local)
+      set_pl_front(player, found < 0 ? 4 : (found > 1 ? found : 1));
+    else
+      set_pl_front(player, found < 0 ? 0 : (found < 3 ? found : 3));
+  }
+#else
   MSB_HD MSB_A_FRONT void calculate_front_line(int player) {
     // any(board[y][x] is not None and board[y][x].player == player for x in range(4)) per row: the first
     // (local: lowest y, remote: highest y) row holding one of the player's entities; only occupied tiles are read
@@ -1225,6 +1327,7 @@ struct Engine {
     else
       set_pl_front(remote(), found < 0 ? 0 : (found < 3 ? found : 3));
   }
+#endif
   // board.calculate_front_line(board.current_player.opponent), unit.py:231 / structure.py:69.
   // Player.opponent (player.py:42-44) is board.remote for the FIRST player, board.local for the
   // SECOND -- i.e. the second player's "opponent" is itself while it is the mover (fact #3).
@@ -1684,22 +1787,43 @@ struct Engine {
   MSB_HD MSB_INL int trig_slot(int i) const { return m.ld8(OFF_TRIG + i) & TRIG_SLOT; }
   MSB_HD MSB_INL bool trig_src(int i) const { return TRIG_WIDE ? ((m.ld32(X_TRIGSRC) >> i) & 1u) != 0 : (m.ld8(OFF_TRIG + i) & 0x80) != 0; }
   MSB_HD MSB_INL void call_pop_trigger(Wk& k) {
+#if MSB_WE_ANY
+    // (default build: h is a placeholder, every hw_* below reads its byte where it stands; with the header word: count, resolving,
+    // and the fault and depth of the call, which the count's store leaves)
+    const uint64_t h = hdr_word();
+    const int n = hw_trig_n(h);
+    if (n == 0 || hw_resolving(h)) return;
+    int e = trig_slot(n - 1);
+    bool src = trig_src(n - 1);
+    m.st8(H_TRIG_N, n - 1);
+    run_ability_enter(k, e, -1, PK_NONE, src, h);
+#else
     int n = m.ld8(H_TRIG_N);
     if (n == 0 || m.ld8(H_RESOLVING)) return;
     int e = trig_slot(n - 1);
     bool src = trig_src(n - 1);
     m.st8(H_TRIG_N, n - 1);
     call_run_ability(k, e, -1, PK_NONE, src);
+#endif
   }
   // wrapped activate_ability (card.py:48-62).  e >= 0: entity slot; e < 0: a spell, `spell` = card | owner << 8.
   // Frame F_RUNAB {hdr: state, e (0xFF = a spell), recursion depth outside | src << 7; w1: spell | pos_pk << 16}:
   // state 0 = the ability has yet to start, 1 = it has returned.  The ability itself starts on run()'s next turn, so
   // that the card code exists once, in the handler.
+#if MSB_WE_ANY
+  // (no worlds on the record that builds this text: ctx_enter is nothing).  h: a header word that is valid here -- in the default
+  // build a placeholder: hw_fault / hw_depth read H_FAULT / H_DEPTH here
+  MSB_HD MSB_INL void call_run_ability(Wk& k, int e, int spell, int pos_pk, bool src) { run_ability_enter(k, e, spell, pos_pk, src, hdr_word()); }
+  MSB_HD MSB_INL void run_ability_enter(Wk& k, int e, int spell, int pos_pk, bool src, const uint64_t h) {
+    if (hw_fault(h)) return;
+    const int d = hw_depth(h);
+#else
   MSB_HD MSB_INL void call_run_ability(Wk& k, int e, int spell, int pos_pk, bool src) {
     const int sv = e >= 0 ? ctx_enter(e) : -1;   // the wrapper works on self.player.board (card.py:54-60)
     if (fault()) return;
     wk_push_ctx(k, sv);
     const int d = m.ld8(H_DEPTH);
+#endif
     if (d >= MAX_DEPTH || !wk_reserve(k)) {
       MSB_COUNT_MAX(12, k.base + k.sp - k.seg);
       set_fault(d >= MAX_DEPTH ? FAULT_DEPTH : FAULT_WORK_STACK);
@@ -1727,7 +1851,14 @@ struct Engine {
         M::trace_ability(spell & 0xff, -1);
         ability_spell(k, spell & 0xff, spell >> 8, pos_pk);
       }
+#if MSB_WE_ANY
+    }
+    const uint64_t h = hdr_word();   // the fault of the ability and the count behind it (default build: a placeholder, each read where it stands)
+    if (hdr_st(hdr) == 0) {
+      if (hw_fault(h)) return;
+#else
       if (fault()) return;
+#endif
       if (k.sp - 1 != top) {   // still running: its frames are above this one, which resumes behind them
         m.sk_st(top, hdr | (1u << 8));
         return;
@@ -1735,7 +1866,11 @@ struct Engine {
     }
     // the ability has returned, card.py:54-60
     m.st8(H_RESOLVING, 0);
+#if MSB_WE_ANY
+    const int n = hw_trig_n(h);
+#else
     const int n = m.ld8(H_TRIG_N);
+#endif
     if (n == 0) {
       m.st8(H_DEPTH, d);
       k.sp = top - 1;
@@ -1766,6 +1901,36 @@ struct Engine {
 
   // Unit.deal_damage unit.py:205-219 / Structure.deal_damage structure.py:52-63.  The reference returns the amount
   // dealt; the one caller that uses it (cards/u405.py) takes min(amount, strength) itself (EACH_DMG_HEAL).
+#if MSB_WE_ANY
+  // The header word for the fault, the trigger count and resolving; the granule once for strength, kind and (for the destroy
+  // behind it) position.  A trigger that is pushed and popped at once leaves H_TRIG_N as it was: only its entry is stored.
+  MSB_HD MSB_INL void call_entity_damage(Wk& k, int e, int amount, bool pending, bool src) {
+    const uint64_t h = hdr_word();   // (default build: a placeholder; fault, count, resolving and cp are read where hw_* stand)
+    if (hw_fault(h)) return;
+    EImg g = ei_load(e);
+    int s = ei_str(g, e);
+    if (s - amount < 0) amount = s;
+    e_set_dmg(e, amount);
+    s -= amount;
+    e_set_str(e, s);
+    ei_put_str(g, s);
+    if (!pending && s <= 0) {
+      destroy_known(k, e, src, g, h);
+    } else if (s > 0 && kind_trigger(ei_kind(g, e)) == TR_AFTER_SURVIVING) {
+      const int n = hw_trig_n(h);   // push_trigger
+      if (n >= TRIG_CAP) {
+        set_fault(FAULT_TRIG_STACK);
+        return;
+      }
+      trig_put(n, e, src);
+      if (hw_resolving(h)) {        // pop_trigger does nothing
+        m.st8(H_TRIG_N, n + 1);
+        return;
+      }
+      run_ability_enter(k, e, -1, PK_NONE, src, h);
+    }
+  }
+#else
   MSB_HD MSB_INL void call_entity_damage(Wk& k, int e, int amount, bool pending, bool src) {
     const int sv = ctx_enter(e);
     if (fault()) return;
@@ -1783,6 +1948,7 @@ struct Engine {
       call_pop_trigger(k);
     }
   }
+#endif
   // X.deal_damage(amount, source=...) where X = board.at(point): unit, structure or Player
   MSB_HD MSB_INL void call_damage(Wk& k, int who, int amount, bool src) {
     if (who >= AT_PLAYER) {
@@ -1805,6 +1971,40 @@ struct Engine {
   }
   // Unit.destroy unit.py:221-231 / Structure.destroy structure.py:65-69.  Frame F_DESTROY_TAIL: what a unit's destroy
   // does once its ON_DEATH ability has returned.
+#if MSB_WE_ANY
+  MSB_HD MSB_INL void call_destroy(Wk& k, int e, bool src) {
+    const uint64_t h = hdr_word();   // (default build: a placeholder; fault, count, resolving and cp are read where hw_* stand)
+    if (hw_fault(h)) return;
+    destroy_known(k, e, src, ei_load(e), h);
+  }
+  // g: e's granule as it stands; h: a header word that is valid here, without a fault (default build: a placeholder)
+  MSB_HD MSB_INL void destroy_known(Wk& k, int e, bool src, const EImg& g, const uint64_t h) {
+    const int kind = ei_kind(g, e);
+    if (kind & EK_UNIT) {
+      board_set(tile_p(ei_tile(g, e)), -1);
+      m.st8g(eg(e), EO_PATHN, 0);
+      e_set_dmg(e, ei_str(g, e));
+      if (kind_card_trigger(kind) == TR_ON_DEATH) {
+        const int n = hw_trig_n(h);   // push_trigger
+        if (n >= TRIG_CAP) {
+          set_fault(FAULT_TRIG_STACK);
+          return;
+        }
+        trig_put(n, e, src);
+        if (!hw_resolving(h)) {   // pop_trigger() runs this ability now (H_TRIG_N stays): the rest of destroy waits for it
+          wk_push(k, mk_hdr(F_DESTROY_TAIL, 0, 0, 0));
+          run_ability_enter(k, e, -1, PK_NONE, src, h);
+          return;
+        }
+        m.st8(H_TRIG_N, n + 1);
+      }
+    } else {
+      e_set_dmg(e, ei_str(g, e));
+      board_set(tile_p(ei_tile(g, e)), -1);
+    }
+    front_line_core(hw_cp(h) == 0 ? hw_remote(h) : hw_local(h), hw_local(h));   // recalc_front_after_destroy
+  }
+#else
   MSB_HD MSB_INL void call_destroy(Wk& k, int e, bool src) {
     const int sv = ctx_enter(e);
     if (fault()) return;
@@ -1829,6 +2029,7 @@ struct Engine {
       recalc_front_after_destroy();
     }
   }
+#endif
   // status methods, unit.py:239-275.  Calling them on a Structure raises AttributeError.
   MSB_HD MSB_INL bool need_unit(int e) {
     if (e < 0 || e >= AT_PLAYER || !e_is_unit(e)) {
@@ -1869,7 +2070,13 @@ struct Engine {
     set_path_impl(e, on_play);
     ctx_leave(sv);
   }
+#if MSB_WE_IMG && MSB_WIDE_PATH
+  MSB_HD MSB_A_SETPATH void set_path_impl(int e, bool on_play) { set_path_known(e, on_play, m.ld32g(eg(e), 0)); }
+  // ge: word 0 of e's granule as it stands (Unit.play has just stored it)
+  MSB_HD MSB_A_SETPATH void set_path_known(int e, bool on_play, const uint32_t ge) {
+#else
   MSB_HD MSB_A_SETPATH void set_path_impl(int e, bool on_play) {
+#endif
     MSB_SCOPE(PS_SET_PATH);
 #if MSB_WIDE_PATH
     // The first word of the unit's granule once for its position, movement and flags (one more byte for the confused count: the
@@ -1877,7 +2084,9 @@ struct Engine {
     // two board-row words (the unit's own row holds both neighbours); the owners of the up to three entities there read
     // together; "already a destination" asked of a tile mask kept beside the packed list.  A row off the board reads as empty.
     static_assert(EO_CARD == 0 && EO_FLAGS == 1 && EO_POS == 2 && EO_MOV == 3, "word 0 of an entity");
+#if !MSB_WE_IMG
     const uint32_t ge = m.ld32g(eg(e), 0);   // {card, flags, pos, mov}
+#endif
     P position = tile_p((int)(ge >> 16) & 0xff);
     int confused_cached = e_st(e, ST_CONFUSED);
     const int owner = (int)(ge >> 8) & EF_OWNER;
@@ -2023,10 +2232,16 @@ struct Engine {
   static constexpr int MV_PLAYED = 0x80;
   // the entry of move(): the world of the unit, the recursion guard.  Returns the depth outside, -1 if the step has faulted.
   MSB_HD MSB_INL int move_enter(Wk& k, int e) {
+#if MSB_WE_ANY
+    const uint64_t h = hdr_word();   // fault and depth (default build: a placeholder, each read where it stands; no worlds here: ctx_enter is nothing)
+    if (hw_fault(h)) return -1;
+    const int d = hw_depth(h);
+#else
     const int sv = ctx_enter(e);
     if (fault()) return -1;
     wk_push_ctx(k, sv);
     const int d = m.ld8(H_DEPTH);
+#endif
     if (d >= MAX_DEPTH || !wk_reserve(k)) {
       MSB_COUNT_MAX(12, k.base + k.sp - k.seg);
       set_fault(d >= MAX_DEPTH ? FAULT_DEPTH : FAULT_WORK_STACK);
@@ -2048,6 +2263,206 @@ struct Engine {
     k.sp += 3;
     wk_push(k, mk_hdr(F_MOVE, MV_START, e, played));
   }
+#if MSB_WE_ANY
+  // The moving unit's granule is read once where the handler starts or resumes (g) and again behind every nested call that
+  // came back at once (MV_CALLED); the handler's own stores to it are repeated on the image, so that the quiet move -- MV_ENTRY,
+  // MV_POISONED, MV_BEFORE_MOVING, MV_STEP, advance, next_step / done -- asks LDS for the unit's fields once.  What a move wants
+  // of the header (the phase, the fault behind a call) and of the unit ahead stays a read per field: held in registers across the
+  // handler -- two more words, four for the unit ahead, one for what stands at the destination -- each of them cost k_play<8,5>
+  // 16 B of private segment.
+  MSB_HD MSB_INL void h_move(Wk& k, uint32_t hdr) {
+    if (hdr_st(hdr) == MV_START) {
+      const int e0 = hdr_a(hdr), played = hdr_b(hdr) & MV_PLAYED;
+      k.sp -= 4;
+      const int d0 = move_enter(k, e0);
+      if (d0 < 0) return;
+      k.sp += 4;
+      hdr = mk_hdr(F_MOVE, MV_ENTRY, e0, d0 | played);
+    }
+    const int top = k.sp - 1;
+    const int e = hdr_a(hdr), d = hdr_b(hdr) & 0x7f;
+    const int played_tail = hdr_b(hdr) & MV_PLAYED;
+    uint32_t path = 0, w2 = 0;
+    int cached = 0;
+    if (hdr_st(hdr) != MV_ENTRY) {   // a move that has waited: its locals
+      path = m.sk_ld(top - 1);
+      w2 = m.sk_ld(top - 2);
+      cached = (int)(int16_t)(m.sk_ld(top - 3) & 0xffffu);
+    }
+    int i = (int)(w2 & 7), n = (int)((w2 >> 3) & 7), current_id = (int)((w2 >> 8) & 0xff), target = (int)((w2 >> 16) & 0xff);
+    int flags = (int)(w2 >> 24);
+    EImg g = ei_load(e);
+    const int trig = kind_trigger(ei_kind(g, e));
+    int next = MV_DONE;
+    P dest{0, 0};
+    int owner = 0, tp = 0;
+#define MV_WAIT(s_)  \
+  do {               \
+    next = (s_);     \
+    goto wait;       \
+  } while (0)
+#define MV_CALLED(s_)                        \
+  do {                                       \
+    if (fault()) return;                     \
+    if (k.sp - 1 != top) MV_WAIT(s_);        \
+    g = ei_load(e);                          \
+  } while (0)
+#define MV_DISABLED() (ei_st(g, e, ST_DISABLED) > 0)
+#define MV_UNCONFUSE()                                   \
+  do {                                                   \
+    const int c_ = ei_st(g, e, ST_CONFUSED);             \
+    if (c_ > 0) {                                        \
+      m.st8g(eg(e), EO_ST + ST_CONFUSED, c_ - 1);        \
+      ei_put8(g, EO_ST + ST_CONFUSED, c_ - 1);           \
+    }                                                    \
+  } while (0)
+    switch (hdr_st(hdr)) {
+      case MV_ENTRY:
+        current_id = (ei_moveid(g, e) + 1) & 0xff;
+        m.st8g(eg(e), EO_MOVEID, current_id);
+        ei_put8(g, EO_MOVEID, current_id);
+        if (phase() == PH_TURN_START) {
+          if (ei_st(g, e, ST_POISONED) > 0) {
+            call_entity_damage(k, e, 1, false, false);
+            MV_CALLED(MV_POISONED);
+          } else if (ei_st(g, e, ST_VITALIZED) > 0) {
+            const int s1 = ei_str(g, e) + 1;
+            e_set_str(e, s1);
+            ei_put_str(g, s1);
+          }
+        }
+        // fall through
+      case MV_POISONED:
+        if (phase() == PH_TURN_START && ei_st(g, e, ST_FROZEN) > 0) {
+          const int c = ei_st(g, e, ST_FROZEN);   // e_st_remove of a count that is positive
+          m.st8g(eg(e), EO_ST + ST_FROZEN, c - 1);
+          ei_put8(g, EO_ST + ST_FROZEN, c - 1);
+          goto done;
+        }
+        if (ei_pathn(g, e) == 0) goto done;
+        if (trig == TR_BEFORE_MOVING && !MV_DISABLED()) {
+          call_run_ability(k, e, -1, PK_NONE, true);
+          if (fault()) return;
+          MV_WAIT(MV_BEFORE_MOVING);
+        }
+        // fall through
+      case MV_BEFORE_MOVING:
+        if (ei_st(g, e, ST_FROZEN) > 0) goto done;
+        // `for destination in self.path` iterates the list object bound now (fact #5)
+        n = ei_pathn(g, e);
+        path = e_path(e);
+        i = 0;
+        // fall through
+      case MV_STEP:
+        if (i >= n) goto done;
+        dest = p_unpack((path >> (8 * i)) & 0xff);
+        owner = ei_flags(g, e) & EF_OWNER;  // self.player is re-read by the reference; convert() may change it
+        flags = 0;
+        if (dest.y < 0 || dest.y > 4) {
+          if (trig == TR_BEFORE_ATTACKING && !MV_DISABLED()) {
+            call_run_ability(k, e, -1, p_pack(dest), true);
+            if (fault()) return;
+            MV_WAIT(MV_BASE_HIT);
+          }
+          goto base_hit;
+        }
+        target = at(dest);
+        if (target == AT_NONE) goto advance;
+        tp = e_owner(target);
+        if (tp == owner && dest.x == tile_p(ei_tile(g, e)).x) goto done;
+        if (!(ei_st(g, e, ST_CONFUSED) > 0 || tp != owner)) goto advance;
+        if (trig == TR_BEFORE_ATTACKING && !MV_DISABLED()) {
+          call_run_ability(k, e, -1, p_pack(dest), true);
+          if (fault()) return;
+          MV_WAIT(MV_FIGHT);
+        }
+        MSB_COUNT_EVENT(51);
+        goto fight_known;
+      case MV_BASE_HIT:
+        dest = p_unpack((path >> (8 * i)) & 0xff);
+      base_hit:
+        MSB_COUNT_EVENT(50);
+        tp = dest.y < 0 ? remote() : local();
+        player_deal_damage(tp, ei_str(g, e));
+        if (pl_base(tp) > 0) {
+          call_destroy(k, e, false);
+          MV_CALLED(MV_DONE);
+        }
+        goto done;
+      case MV_FIGHT:
+        dest = p_unpack((path >> (8 * i)) & 0xff);
+        MSB_COUNT_EVENT(51);
+        target = at(dest);
+        if (target == AT_NONE) goto advance;
+      fight_known:
+        cached = e_str(target);   // target_strength_cached
+        flags = ((e_trigger(target) == TR_ON_DEATH && !e_disabled(target)) ? 2 : 0) |
+                ((trig == TR_ON_DEATH && !MV_DISABLED()) ? 4 : 0);
+        call_entity_damage(k, target, ei_str(g, e), (flags & 2) != 0, false);
+        MV_CALLED(MV_STRUCK);
+        // fall through
+      case MV_STRUCK:
+        call_entity_damage(k, e, cached, (flags & 4) != 0, false);
+        MV_CALLED(MV_STRUCK_BACK);
+        // fall through
+      case MV_STRUCK_BACK:
+        if (e_str(target) <= 0 && (flags & 2)) {
+          call_destroy(k, target, false);
+          MV_CALLED(MV_TARGET_DEAD);
+        }
+        // fall through
+      case MV_TARGET_DEAD:
+        if (ei_str(g, e) <= 0 && (flags & 4)) {
+          call_destroy(k, e, false);
+          MV_CALLED(MV_SELF_DEAD);
+        }
+        // fall through
+      case MV_SELF_DEAD:
+        flags |= 1;   // is_attacked
+      advance:
+        MSB_COUNT_EVENT(52);
+        dest = p_unpack((path >> (8 * i)) & 0xff);
+        if (current_id != ei_moveid(g, e)) goto done;
+        if (at(dest) == AT_NONE && ei_str(g, e) > 0) {
+          board_set(tile_p(ei_tile(g, e)), -1);
+          board_set(dest, e);
+          ei_put8(g, EO_POS, p_tile(dest));
+          const int o = ei_flags(g, e) & EF_OWNER;
+          if (pl_front(o) > dest.y) set_pl_front(o, dest.y > 1 ? dest.y : 1);
+          if ((flags & 1) && trig == TR_AFTER_ATTACKING && !MV_DISABLED()) {
+            call_run_ability(k, e, -1, PK_NONE, true);
+            if (fault()) return;
+            MV_WAIT(MV_AFTER_ATTACK);
+          }
+          MV_UNCONFUSE();
+        }
+        goto next_step;
+      case MV_AFTER_ATTACK:
+        MV_UNCONFUSE();
+      next_step:
+        i++;
+        if (i < n) MV_WAIT(MV_STEP);   // the next destination: a backward jump, through run()
+        goto done;
+      default:   // MV_DONE
+        break;
+    }
+  done:
+    m.st8(H_DEPTH, d);
+    if (played_tail) m.st8g(eg(e), EO_FLAGS, ei_flags(g, e) & ~EF_RESOLVING_PLAY);   // Unit.play's last line
+    k.sp = top - 3;
+    return;
+  wait:
+    m.sk_st(top - 1, path);
+    m.sk_st(top - 2, (uint32_t)(i & 7) | ((uint32_t)(n & 7) << 3) | ((uint32_t)(current_id & 0xff) << 8) | ((uint32_t)(target & 0xff) << 16) |
+                         ((uint32_t)(flags & 0xff) << 24));
+    m.sk_st(top - 3, (uint32_t)(cached & 0xffff));
+    m.sk_st(top, mk_hdr(F_MOVE, next, e, d | played_tail));
+#undef MV_WAIT
+#undef MV_CALLED
+#undef MV_DISABLED
+#undef MV_UNCONFUSE
+  }
+#else
   MSB_HD MSB_INL void h_move(Wk& k, uint32_t hdr) {
     if (hdr_st(hdr) == MV_START) {
       // the frame holds nothing yet: take it off, enter (which may leave a world mark where it was), put it back
@@ -2217,14 +2632,27 @@ struct Engine {
 #undef MV_WAIT
 #undef MV_CALLED
   }
+#endif
 
   // Unit.play, unit.py:66-76: the ON_PLAY ability, then the move, whose frame also carries play()'s last line (MV_PLAYED)
   MSB_HD MSB_INL void call_unit_play(Wk& k, int e, P position) {
+#if MSB_WE_IMG && MSB_WIDE_PATH
+    // word 0 of the granule once: the flag and the position go back as one word, which set_path then need not read; the kind
+    // byte is asked for with it
+    const uint32_t w0 = ((m.ld32g(eg(e), 0) | ((uint32_t)EF_RESOLVING_PLAY << 8)) & ~0xff0000u) | ((uint32_t)(p_tile(position) & 0xff) << 16);
+    const int kind = e_kind(e);
+    m.st32g(eg(e), 0, w0);
+    board_put(p_tile(position), e);
+    set_path_known(e, true, w0);
+    if (fault()) return;
+    if (kind_card_trigger(kind) == TR_ON_PLAY) {
+#else
     e_set_flag(e, EF_RESOLVING_PLAY, true);
     board_set(position, e);
     set_path(e, true);
     if (fault()) return;
     if (e_card_trigger(e) == TR_ON_PLAY) {
+#endif
       call_move_later(k, e, MV_PLAYED);   // below the ability: starts when the ability has returned
       call_run_ability(k, e, -1, PK_NONE, true);
     } else {
@@ -2842,8 +3270,14 @@ struct Engine {
 #else
     run(k);
 #endif
+#if MSB_WE_HDR
+    const uint64_t ht = hdr_word();   // the fault and the side to play for the base test
+    if (hw_fault(ht)) return action == 155 ? k.result : 0;
+    if (action != 155) k.result = (pl_base(hw_remote(ht)) <= 0 ? 1 : 0) | (have_winner() ? 2 : 0);
+#else
     if (fault()) return action == 155 ? k.result : 0;   // 0 if the play raised; what was computed before the turn was passed on otherwise
     if (action != 155) k.result = (pl_base(remote()) <= 0 ? 1 : 0) | (have_winner() ? 2 : 0);
+#endif
     if (m.ld8(H_RNGOVER)) set_fault(FAULT_RNG_OVERRUN);
     return k.result;
   }

@@ -205,6 +205,31 @@ constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
 #ifndef MSB_WIDE_PATH
 #define MSB_WIDE_PATH 1
 #endif
+// The header fields and the entity fields that move, damage, destroy and the ability call ask for, out of one read each
+// (rules.h hdr_word / hw_*, ei_load / ei_*): bytes 0..7 of the record as one 64-bit word, the entity's granule as one 16-byte
+// read.  Standard record only: on the records with worlds ctx_enter / ctx_leave swap header bytes and the board under such a
+// value, and they keep the per-field reads, as they keep the list loops.  0 builds the per-field text everywhere;
+// tests/wide_ent_check.cpp compiles the core once with each text into one program and holds one against the other, so the 0
+// text always compiles.  The two parts have a switch each (profiles/wide_ent_ab.txt).  The entity image is the part that is
+// built.  The header word is built only with -DMSB_WIDE_ENT_HDR=1: alone it separates from the per-field text (C2 +3.0 %), next to
+// the image it costs 1.0 % (table 2 of that file), and no group of its sites put in alone does better, so it stays out; the same host program holds its text against the other two.
+#ifndef MSB_WIDE_ENT
+#define MSB_WIDE_ENT 1
+#endif
+#ifndef MSB_WIDE_ENT_HDR
+#define MSB_WIDE_ENT_HDR 0
+#endif
+#ifndef MSB_WIDE_ENT_IMG
+#define MSB_WIDE_ENT_IMG MSB_WIDE_ENT
+#endif
+#if defined(MSB_EXT) && MSB_EXT
+#define MSB_WE_HDR 0
+#define MSB_WE_IMG 0
+#else
+#define MSB_WE_HDR MSB_WIDE_ENT_HDR
+#define MSB_WE_IMG MSB_WIDE_ENT_IMG
+#endif
+#define MSB_WE_ANY (MSB_WE_HDR || MSB_WE_IMG)
 constexpr int LDS_RECORDS = WK_OVF_LDS + 16;        // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
