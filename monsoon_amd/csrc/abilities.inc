@@ -187,20 +187,19 @@ MSB_HD MSB_INL void h_each(Wk& k, const uint32_t hdr) {
       break;
     case EACH_COMMAND_B203: {   // cards/b203.py:17-21
       const int t = at(l.at(i));
-      if (!need_unit(t)) break;
-      if (e_confused(t)) deconfuse(t);
+      if (!deconfuse_if_confused(t)) break;
       if (fault()) break;
       call_command(k, t);
     } break;
     case EACH_U018: {   // cards/u018.py:22-25
       Tgt t = mk_tgt(TK_ANY, TS_ENEMY);
       t = tgt_base(t);
-      const PList l2 = get_targets(cp(), t, PK_NONE);
-      call_damage(k, at(choice_point(l2)), 2, true);
+      const Pick q = targets_pick(cp(), t, PK_NONE);   // (the enemy base is always in it)
+      call_damage(k, at(choice_tile(q)), 2, true);
     } break;
     case EACH_UE01: {   // cards/ue01.py:16-20
-      const PList l2 = get_targets(arg, mk_tgt(TK_UNIT, TS_ENEMY), PK_NONE);
-      if (l2.n() > 0) call_damage(k, at(choice_point(l2)), 1, true);
+      const Pick q = targets_pick(arg, mk_tgt(TK_UNIT, TS_ENEMY), PK_NONE);
+      if (q.n() > 0) call_damage(k, at(choice_tile(q)), 1, true);
       else skip = true;
     } break;
     case EACH_U017: {   // cards/u017.py:29-35
@@ -213,12 +212,12 @@ MSB_HD MSB_INL void h_each(Wk& k, const uint32_t hdr) {
       P pos{0, 0};
       bool has_pos = false;
       if (ci.tgt.has) {
-        const PList l2 = get_targets(cp(), mk_tgt(ci.tgt), PK_NONE);
-        if (l2.n() == 0) {
+        const Pick q = targets_pick(cp(), mk_tgt(ci.tgt), PK_NONE);
+        if (q.n() == 0) {
           set_fault(FAULT_PY_EXCEPTION);   // random.choice([]) raises
           break;
         }
-        pos = choice_point(l2);
+        pos = choice_tile(q);
         has_pos = true;
       }
       arg |= 1 << oi;
@@ -321,7 +320,18 @@ MSB_HD MSB_INL void h_after(Wk& k, const uint32_t hdr) {
     }                                                                      \
     return k.sp;                                                           \
   }
+// X.heal(amount); X.vitalize() on one entity (a card body is a macro argument and can hold no #if): on the image where
+// MSB_WIDE_AB_ST is built (rules.h heal_vitalize), the two calls as the cards spell them where it is not
+#if MSB_AB_ST
+#define MSB_HEAL_VITALIZE(who, amount) heal_vitalize(who, amount, false)
+#define MSB_HEAL_VITALIZE_CHECKED(who, amount) heal_vitalize(who, amount, true)
+#else
+#define MSB_HEAL_VITALIZE(who, amount) { int t = who; heal(t, amount); vitalize(t); }
+#define MSB_HEAL_VITALIZE_CHECKED(who, amount) { int t = who; heal(t, amount); if (!fault()) vitalize(t); }
+#endif
 #include "ability_cases.inc"
+#undef MSB_HEAL_VITALIZE
+#undef MSB_HEAL_VITALIZE_CHECKED
 #undef MSB_CARD
 #undef MSB_CARD_K
 #undef MSB_SPELL

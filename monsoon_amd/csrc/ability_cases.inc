@@ -194,12 +194,8 @@ MSB_CARD_K(C_B304,  // cards/b304.py:12-13
     // ------------------------------------------------------------------ units
 )
 MSB_CARD(C_U007, {  // cards/u007.py:13-22
-      l = sel_targets(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_ENEMY));
-      if (l.n() > 0) {
-        int t = at(choice_point(l));
-        heal(t, 5);
-        vitalize(t);
-      }
+      const Pick q = shape_pick(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_ENEMY));
+      if (q.n() > 0) MSB_HEAL_VITALIZE(at(choice_tile(q)), 5);
     } break;
 )
 MSB_CARD_K(C_U017, {  // cards/u017.py:18-35: play up to 8 mana of spells from hand, free, in shuffled order
@@ -240,8 +236,8 @@ MSB_CARD_K(C_U018, {  // cards/u018.py:13-25
     } break;
 )
 MSB_CARD(C_U021, {  // cards/u021.py:13-20
-      l = get_targets(dpov, mk_tgt(TK_UNIT, TS_FRIENDLY), p_pack(mypos));
-      if (l.n() > 0) heal(at(choice_point(l)), 5);
+      const Pick q = targets_pick(dpov, mk_tgt(TK_UNIT, TS_FRIENDLY), p_pack(mypos));
+      if (q.n() > 0) heal(at(choice_tile(q)), 5);
     } break;
 )
 MSB_CARD_K(C_U026, {  // cards/u026.py:13-17
@@ -288,8 +284,8 @@ MSB_CARD(C_U055, {  // cards/u055.py:12-19
 )
 MSB_CARD(C_U061, {  // cards/u061.py:12-22
       confuse(e);
-      l = get_targets(dpov, mk_tgt(TK_UNIT, TS_FRIENDLY), p_pack(mypos));
-      if (l.n() > 0) confuse(at(choice_point(l)));
+      const Pick q = targets_pick(dpov, mk_tgt(TK_UNIT, TS_FRIENDLY), p_pack(mypos));
+      if (q.n() > 0) confuse(at(choice_tile(q)));
       gain_speed(e, 2);
     } break;
 )
@@ -314,9 +310,9 @@ MSB_CARD_K(C_U074, {  // cards/u074.py:12-19
 MSB_CARD_K(C_U076, {  // cards/u076.py:14-25
       Tgt t = mk_tgt(TK_UNIT, TS_ANY);
       t = tgt_xtypes(t, 1 << UT_DRAGON);
-      l = sel_targets(SH_SURROUNDING, mypos, dpov, t);
-      if (l.n() > 0) {
-        int target = at(choice_point(l));
+      const Pick q = shape_pick(SH_SURROUNDING, mypos, dpov, t);
+      if (q.n() > 0) {
+        int target = at(choice_tile(q));
         call_after(k, AFTER_U076, e, target, me);   // behind the damage: a dragon where the target died
         call_damage(k, target, 6, true);
       }
@@ -343,8 +339,8 @@ MSB_CARD(C_U106, {  // cards/u106.py:13-18
 )
 MSB_CARD(C_U111, {  // cards/u111.py:13-21
       for (int k = 0; k < 10 && !fault(); k++) {
-        l = sel_targets(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_FRIENDLY));
-        if (l.n() > 0) heal(at(choice_point(l)), 1);
+        const Pick q = shape_pick(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_FRIENDLY));
+        if (q.n() > 0) heal(at(choice_tile(q)), 1);
       }
     } break;
 )
@@ -386,16 +382,16 @@ MSB_CARD_K(C_U302, {  // cards/u302.py:12-22
 MSB_CARD(C_U305, {  // cards/u305.py:13-21
       Tgt t = mk_tgt(TK_UNIT, TS_FRIENDLY);
       t = tgt_types(t, 1 << UT_CONSTRUCT);
-      l = sel_targets(SH_BORDERING, mypos, dpov, t);
-      if (l.n() > 0) {
-        heal(at(choice_point(l)), 4);
+      const Pick q = shape_pick(SH_BORDERING, mypos, dpov, t);
+      if (q.n() > 0) {
+        heal(at(choice_tile(q)), 4);
         heal(e, 4);
       }
     } break;
 )
 MSB_CARD_K(C_U306, {  // cards/u306.py:13-20
-      l = get_targets(dpov, mk_tgt(TK_ANY, TS_FRIENDLY), p_pack(mypos));
-      if (l.n() > 0) call_damage(k, at(choice_point(l)), 1, true);
+      const Pick q = targets_pick(dpov, mk_tgt(TK_ANY, TS_FRIENDLY), p_pack(mypos));
+      if (q.n() > 0) call_damage(k, at(choice_tile(q)), 1, true);
     } break;
 )
 MSB_CARD(C_U310, {  // cards/u310.py:13-40  (raises UnboundLocalError when nothing is pushable)
@@ -425,8 +421,8 @@ MSB_CARD(C_U310, {  // cards/u310.py:13-40  (raises UnboundLocalError when nothi
     } break;
 )
 MSB_CARD(C_U313, {  // cards/u313.py:13-22
-      l = sel_targets(SH_SURROUNDING, mypos, dpov, mk_tgt(TK_UNIT, TS_FRIENDLY));
-      if (l.n() > 0) heal(at(choice_point(l)), 5);
+      const Pick q = shape_pick(SH_SURROUNDING, mypos, dpov, mk_tgt(TK_UNIT, TS_FRIENDLY));
+      if (q.n() > 0) heal(at(choice_tile(q)), 5);
       heal(e, 5);
     } break;
 )
@@ -445,8 +441,8 @@ MSB_CARD(C_U316, {  // cards/u316.py:13-25
     } break;
 )
 MSB_CARD(C_U320, {  // cards/u320.py:13-20
-      l = sel_targets(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_FRIENDLY));
-      if (l.n() > 0) heal(at(choice_point(l)), 4);
+      const Pick q = shape_pick(SH_SURROUNDING, mypos, me, mk_tgt(TK_UNIT, TS_FRIENDLY));
+      if (q.n() > 0) heal(at(choice_tile(q)), 4);
     } break;
 )
 MSB_CARD_K(C_U401, {  // cards/u401.py:13-24
@@ -539,8 +535,8 @@ MSB_CARD(C_UA20, {  // cards/ua20.py:21-32 (needs the extended record's deck cap
 MSB_CARD(C_UD01, {  // cards/ud01.py:13-20
       Tgt t = mk_tgt(TK_UNIT, TS_FRIENDLY);
       t = tgt_types(t, 1 << UT_DRAGON);
-      l = get_targets(me, t, PK_NONE);
-      if (l.n() > 0) heal(at(choice_point(l)), 7);
+      const Pick q = targets_pick(me, t, PK_NONE);
+      if (q.n() > 0) heal(at(choice_tile(q)), 7);
     } break;
 )
 MSB_CARD_K(C_UD02, {  // cards/ud02.py:13-20
@@ -556,8 +552,8 @@ MSB_CARD(C_UD31, {  // cards/ud31.py:13-25
       if (p_is_base(position) || t < 0 || t >= AT_PLAYER || !e_is_unit(t)) break;
       Tgt tg = mk_tgt(TK_UNIT, TS_FRIENDLY);
       tg = tgt_types(tg, 1 << UT_DRAGON);
-      l = sel_targets(SH_SURROUNDING, mypos, me, tg);
-      if (l.n() > 0) heal(at(choice_point(l)), 2);
+      const Pick q = shape_pick(SH_SURROUNDING, mypos, me, tg);
+      if (q.n() > 0) heal(at(choice_tile(q)), 2);
       heal(e, 2);
     } break;
 )
@@ -678,14 +674,12 @@ MSB_SPELL(C_S004, {  // cards/s004.py:14-23
     } break;
 )
 MSB_SPELL(C_S007, {  // cards/s007.py:13-16
-      int t = at(position);
-      heal(t, 7);
-      if (!fault()) vitalize(t);
+      MSB_HEAL_VITALIZE_CHECKED(at(position), 7);
     } break;
 )
 MSB_SPELL(C_S012, {  // cards/s012.py:13-18
-      l = empty_within_front_line(me);
-      if (l.n() > 0) spawn_token_unit(me, choice_point(l), 5, UT_KNIGHT);
+      const Pick q = empty_front_pick(me);
+      if (q.n() > 0) spawn_token_unit(me, choice_tile(q), 5, UT_KNIGHT);
     } break;
 )
 MSB_SPELL_K(C_S013, {  // cards/s013.py:13-26
@@ -766,9 +760,7 @@ MSB_SPELL(C_S403, {  // cards/s403.py:13-22
       t = tgt_status(t, 1 << ST_POISONED);
       l = get_targets(dpov, t, PK_NONE);
       for (int i = 0; i < l.n() && !fault(); i++) {
-        int u = at(l.at(i));
-        heal(u, 5);
-        if (!fault()) vitalize(u);
+        MSB_HEAL_VITALIZE_CHECKED(at(l.at(i)), 5);
       }
     } break;
 )

@@ -1637,6 +1637,64 @@ struct Engine {
   // numpy RandomState.choice(list) / shuffle(list)
   MSB_HD MSB_INL int choice_index(int n) { return rng_randint(0, n); }
   MSB_HD MSB_INL P choice_point(PList l) { return l.at(choice_index(l.n())); }
+#if MSB_AB_PICK
+  // random.choice over a target list that is built for nothing else (state.h MSB_WIDE_AB_PICK).  The list is the hit mask in
+  // ascending or descending tile order with the descriptor's bases behind the tiles (hit_list, get_targets_impl), so element r
+  // is the r-th set bit counted from the low or the high end, or a base: a Pick is that list before it is packed.  n() is the
+  // list's length, choice_tile() the one draw choice_point makes over it.  Callers test n() > 0 where the card tests the list.
+  // Not for SH_FRONT / SH_BEHIND, whose lists are sorted again by row.
+  struct Pick {
+    uint32_t hit;
+    int bases;
+    bool asc;
+    MSB_HD MSB_INL int n() const { return __builtin_popcount(hit) + (bases & 1) + ((bases >> 1) & 1); }
+  };
+  MSB_HD MSB_INL P choice_tile(uint32_t hit, const int bases, const bool asc) {
+    const int nt = __builtin_popcount(hit);
+    int r = choice_index(nt + (bases & 1) + ((bases >> 1) & 1));
+    if ((unsigned)r < (unsigned)nt) {
+      if (!asc) r = nt - 1 - r;
+      for (; r > 0; r--) hit &= hit - 1;
+      return tile_p(__builtin_ctz(hit));
+    }
+    return base_point((bases & 1) && r == nt, asc);
+  }
+  MSB_HD MSB_INL P choice_tile(const Pick& q) { return choice_tile(q.hit, q.bases, q.asc); }
+  // get_targets(pov, t, exclude_pk) as a Pick
+  MSB_HD MSB_A_TARGETS Pick targets_pick(int pov, Tgt t, int exclude_pk) {
+    MSB_SCOPE(PS_GET_TARGETS);
+    const bool asc = (pov == local());
+    uint32_t tiles = 0xFFFFFu;
+    int bases = target_bases(t);
+    exclude_point(exclude_pk, asc, tiles, bases);
+    return Pick{get_targets_hit(pov, t, tiles), bases, asc};
+  }
+  // shape_targets(shape, c, pov, t, PK_NONE) as a Pick
+  MSB_HD MSB_A_SHAPE Pick shape_pick(int shape, P c, int pov, Tgt t) {
+    MSB_SCOPE(PS_GET_TARGETS);
+    const bool asc = (pov == local());
+    int bases = target_bases(t);
+    if (bases && !shape_base_rule(shape))
+      bases &= (in_shape(shape, c, pov, base_point(true, asc)) ? 1 : 0) | (in_shape(shape, c, pov, base_point(false, asc)) ? 2 : 0);
+    return Pick{get_targets_hit(pov, t, shape_mask(shape, c, pov)), bases, asc};
+  }
+  // Player.get_within_front_line's empty tiles as a Pick (abilities.inc empty_within_front_line: the player's ORDER sets the
+  // rows and the direction)
+  MSB_HD MSB_INL Pick empty_front_pick(int order) {
+    const int fl = pl_front(order);
+    return Pick{~occ_mask() & (order == 0 ? 0xFFFFFu & ~rows_below(fl) : rows_below(fl + 1)), 0, order == 0};
+  }
+#else
+  // -DMSB_WIDE_AB_PICK=0 and the records with worlds: a Pick is the list, the draw is choice_point's
+  struct Pick {
+    PList l;
+    MSB_HD MSB_INL int n() const { return l.n(); }
+  };
+  MSB_HD MSB_INL P choice_tile(const Pick& q) { return choice_point(q.l); }
+  MSB_HD MSB_INL Pick targets_pick(int pov, Tgt t, int exclude_pk) { return Pick{get_targets(pov, t, exclude_pk)}; }
+  MSB_HD MSB_INL Pick shape_pick(int shape, P c, int pov, Tgt t) { return Pick{shape_targets(shape, c, pov, t, PK_NONE)}; }
+  MSB_HD MSB_INL Pick empty_front_pick(int order) { return Pick{empty_within_front_line(order)}; }
+#endif
   MSB_HD MSB_A_SHUFFLE PList shuffle(PList l) {
     for (int i = l.n() - 1; i >= 1; i--) {
       int j = (int)rng_interval((uint32_t)i);
@@ -2038,6 +2096,81 @@ struct Engine {
     }
     return true;
   }
+#if MSB_AB_ST
+  // The same methods on the entity image (state.h MSB_WIDE_AB_ST): the target's granule is read once, need_unit's kind byte,
+  // disable's has_ability, the counts and the strength come out of it, and each changed byte is stored once and repeated on the
+  // image, so that a second effect on the same entity (heal then vitalize) works on what the first left.  Faults and bytes are
+  // the per-field text's: a count of 255 is left alone with FAULT_STATUS_SAT, a removal at 0 with FAULT_PY_EXCEPTION.
+  MSB_HD MSB_INL bool ei_need_unit(int e, EImg& g) {
+    if (e < 0 || e >= AT_PLAYER) {
+      set_fault(FAULT_PY_EXCEPTION);
+      return false;
+    }
+    g = ei_load(e);
+    if (!(ei_kind(g, e) & EK_UNIT)) {
+      set_fault(FAULT_PY_EXCEPTION);
+      return false;
+    }
+    return true;
+  }
+  MSB_HD MSB_INL void ei_st_add(int e, EImg& g, int s) {
+    const int c = ei_st(g, e, s);
+    if (c >= 255) {
+      set_fault(FAULT_STATUS_SAT);
+      return;
+    }
+    m.st8g(eg(e), EO_ST + s, c + 1);
+    ei_put8(g, EO_ST + s, c + 1);
+  }
+  MSB_HD MSB_INL void ei_st_remove(int e, EImg& g, int s) {
+    const int c = ei_st(g, e, s);
+    if (c == 0) {
+      set_fault(FAULT_PY_EXCEPTION);
+      return;
+    }
+    m.st8g(eg(e), EO_ST + s, c - 1);
+    ei_put8(g, EO_ST + s, c - 1);
+  }
+  MSB_HD MSB_INL void ei_poison(int e, EImg& g) {
+    if (ei_st(g, e, ST_VITALIZED) > 0) ei_st_remove(e, g, ST_VITALIZED);
+    ei_st_add(e, g, ST_POISONED);
+  }
+  MSB_HD MSB_INL void ei_vitalize(int e, EImg& g) {
+    if (ei_st(g, e, ST_POISONED) > 0) ei_st_remove(e, g, ST_POISONED);
+    ei_st_add(e, g, ST_VITALIZED);
+  }
+  MSB_HD MSB_INL void freeze(int e) {
+    EImg g;
+    if (ei_need_unit(e, g)) ei_st_add(e, g, ST_FROZEN);
+  }
+  MSB_HD MSB_INL void poison(int e) {
+    EImg g;
+    if (ei_need_unit(e, g)) ei_poison(e, g);
+  }
+  MSB_HD MSB_INL void vitalize(int e) {
+    EImg g;
+    if (ei_need_unit(e, g)) ei_vitalize(e, g);
+  }
+  MSB_HD MSB_INL void confuse(int e) {
+    EImg g;
+    if (ei_need_unit(e, g)) ei_st_add(e, g, ST_CONFUSED);
+  }
+  MSB_HD MSB_INL void deconfuse(int e) {
+    EImg g;
+    if (ei_need_unit(e, g)) ei_st_remove(e, g, ST_CONFUSED);
+  }
+  MSB_HD MSB_INL void disable(int e) {  // unit.py:269-271: only classes that override the ability
+    EImg g;
+    if (ei_need_unit(e, g) && (ei_kind(g, e) & EK_ABILITY)) ei_st_add(e, g, ST_DISABLED);
+  }
+  // `if unit.is_confused: unit.deconfuse()` of a unit that need_unit has yet to pass (cards/b203.py:19-20)
+  MSB_HD MSB_INL bool deconfuse_if_confused(int e) {
+    EImg g;
+    if (!ei_need_unit(e, g)) return false;
+    if (ei_st(g, e, ST_CONFUSED) > 0) ei_st_remove(e, g, ST_CONFUSED);
+    return true;
+  }
+#else
   MSB_HD MSB_INL void freeze(int e) {
     if (need_unit(e)) e_st_add(e, ST_FROZEN);
   }
@@ -2060,6 +2193,34 @@ struct Engine {
   MSB_HD MSB_INL void disable(int e) {  // unit.py:269-271: only classes that override the ability
     if (need_unit(e) && e_has_ability(e)) e_st_add(e, ST_DISABLED);
   }
+  MSB_HD MSB_INL bool deconfuse_if_confused(int e) {
+    if (!need_unit(e)) return false;
+    if (e_confused(e)) deconfuse(e);
+    return true;
+  }
+#endif
+  // X.heal(amount); X.vitalize() of X = board.at(point) (cards/u007.py:20-21; with `checked`, the spells' form: the second call
+  // only where no fault stands, cards/s007.py:15-16, cards/s403.py:20-21).  The cards name it through MSB_HEAL_VITALIZE /
+  // MSB_HEAL_VITALIZE_CHECKED (abilities.inc), which spell the two calls out where this text is not built.
+#if MSB_AB_ST
+  MSB_HD MSB_INL void heal_vitalize(int who, int amount, bool checked) {
+    if (who >= 0 && who < AT_PLAYER) {
+      EImg g = ei_load(who);
+      const int s = ei_str(g, who) + amount;
+      e_set_str(who, s);
+      ei_put_str(g, s);
+      if (checked && fault()) return;
+      if (!(ei_kind(g, who) & EK_UNIT)) {
+        set_fault(FAULT_PY_EXCEPTION);
+        return;
+      }
+      ei_vitalize(who, g);
+      return;
+    }
+    heal(who, amount);   // a base or an empty tile: the per-field calls
+    if (!checked || !fault()) vitalize(who);
+  }
+#endif
 
   // ------------------------------------------------------------------------------------------
   // Movement
@@ -2667,10 +2828,17 @@ struct Engine {
   MSB_HD MSB_INL bool e_resolving_play(int e) const { return (e_flags(e) & EF_RESOLVING_PLAY) != 0; }
   // Unit.gain_speed, unit.py:277-280
   MSB_HD MSB_INL void gain_speed(int e, int amount) {
+#if MSB_AB_SPEED
+    // word 0 of the granule once: the path is computed for movement + amount as set_path would read it back (a byte), the
+    // resolving flag comes out of the same word, and EO_MOV is neither stored nor restored
+    const uint32_t w0 = m.ld32g(eg(e), 0);
+    set_path_known(e, ((w0 >> 8) & EF_RESOLVING_PLAY) != 0, (w0 & 0x00ffffffu) | ((((w0 >> 24) + (uint32_t)amount) & 0xffu) << 24));
+#else
     int mv = e_mov(e);
     m.st8g(eg(e), EO_MOV, mv + amount);
     set_path(e, e_resolving_play(e));
     m.st8g(eg(e), EO_MOV, mv);
+#endif
   }
   // Unit.command, unit.py:282-289.  Frame F_CMD_TAIL {hdr: e, fixedly_forward as it was}: behind the move.
   MSB_HD MSB_INL void call_command(Wk& k, int e) {
@@ -3441,12 +3609,12 @@ struct Engine {
         if (enemies.at(k).y == 4) bbe.push_raw(enemies.get(k));
       if (ci.kind == KIND_SPELL) {
         if (!ci.tgt.has) return 64 + 21 * index;
-        PList t = get_targets(cp(), mk_tgt(ci.tgt), PK_NONE);
+        const Pick t = targets_pick(cp(), mk_tgt(ci.tgt), PK_NONE);
         if (t.n() == 0) {
           set_fault(FAULT_PY_EXCEPTION);   // random.choice([]) raises
           return 155;
         }
-        P p = choice_point(t);
+        P p = choice_tile(t);
         return p_valid(p) ? 65 + 21 * index + (4 - p.y) * 4 + p.x : 155;
       } else if (ci.kind == KIND_UNIT && bbe.n() > 0) {
         PList cand;

@@ -230,6 +230,36 @@ constexpr int DRAW_HINT_LDS = WK_OVF_LDS + 8;
 #define MSB_WE_IMG MSB_WIDE_ENT_IMG
 #endif
 #define MSB_WE_ANY (MSB_WE_HDR || MSB_WE_IMG)
+// The short effects of an ability on the same whole words (rules.h, abilities.inc, ability_cases.inc): standard record only, for
+// the reason above.  Three parts, a switch each; with all three at 0 the per-field text is built everywhere, and
+// tests/wide_ab_check.cpp compiles the core once with each text into one program and holds one against the other.
+//   MSB_WIDE_AB_ST     freeze, poison, vitalize, confuse, deconfuse, disable and heal-then-vitalize read the target's granule once
+//                      (ei_load): kind, counts and strength come out of the image, each changed byte goes back once.  Needs the
+//                      entity image.
+//   MSB_WIDE_AB_SPEED  Unit.gain_speed hands word 0 with the raised movement to set_path_known: no store and restore of EO_MOV,
+//                      the resolving flag out of the same word.  Needs the entity image and MSB_WIDE_PATH.
+//   MSB_WIDE_AB_PICK   random.choice over a target list asked of the hit mask (choice_tile: the r-th set bit, the bases behind
+//                      the tiles) where the list was built for nothing else.  Needs MSB_TARGET_SCAN.
+// Built: the pick alone.  The other two were measured next to it and do not separate from it (profiles/wide_ab_ab.txt), so they
+// stay switches that are not built; the same host program holds their text against the per-field text.
+#ifndef MSB_WIDE_AB_ST
+#define MSB_WIDE_AB_ST 0
+#endif
+#ifndef MSB_WIDE_AB_SPEED
+#define MSB_WIDE_AB_SPEED 0
+#endif
+#ifndef MSB_WIDE_AB_PICK
+#define MSB_WIDE_AB_PICK 1
+#endif
+#if defined(MSB_EXT) && MSB_EXT
+#define MSB_AB_ST 0
+#define MSB_AB_SPEED 0
+#define MSB_AB_PICK 0
+#else
+#define MSB_AB_ST (MSB_WIDE_AB_ST && MSB_WE_IMG)
+#define MSB_AB_SPEED (MSB_WIDE_AB_SPEED && MSB_WE_IMG && MSB_WIDE_PATH)
+#define MSB_AB_PICK (MSB_WIDE_AB_PICK && MSB_TARGET_SCAN)
+#endif
 constexpr int LDS_RECORDS = WK_OVF_LDS + 16;        // first LDS byte the kernels may use for records
 // The work stack of the rules core (rules.h "Control flow"): up to SK_CAP 32-bit words per game.  On the device a lane's
 // stack lives in SKW words of LDS (lane-interleaved like the record); whenever fewer than SK_NEED of them are free before
