@@ -9,7 +9,11 @@ ue01) runs at least once in the committed steps of those games.  What the games 
 states: a status at 255, a poisoned unit that is vitalized, u061 with no other friendly unit (no draw), a pick whose draw lands
 on a base, gain_speed from the back row, of a unit with nothing around it and of a confused unit.  Each is asserted on the
 oracle to be what it is named after; then monsoon_step of the device must give the oracle's fault code and canonical hash for
-every (state, action)."""
+every (state, action).
+
+Which element a pick draws, at every list length and under both list orders, and the call sites these games do not reach
+(u076 u111 u305 u306 u313 u320 ud31, EACH_U017, the scripted bot's spell target): tests/test_pick_sites_gpu.py over the case
+table of tests/pick_sites.py."""
 import numpy as np
 import pytest
 

@@ -22,7 +22,12 @@ what those games do not reach; reference() steps each on the recursive oracle an
     row4-speed-*   u050 placed on its owner's back row with nothing ahead: it gains three steps and stands three rows on
     alone-speed-*  u053 placed with nothing around it: it gains two steps
 disable() on a unit without an ability cannot be reached by a step (ua07, the one card that disables, has an ability): the
-host program tests/wide_ab_check.cpp holds it."""
+host program tests/wide_ab_check.cpp holds it.
+
+The games say that a pick ran, not which element of which list it drew.  Every call site of the pick -- the ten these games and
+states do not reach among them (u076 u111 u305 u306 u313 u320 ud31, u018 beyond base-pick-*, EACH_U017, the scripted bot's spell
+target) -- is stepped from described states on every index of the draw, under both list orders where a step reaches them, by
+tests/pick_sites.py (tests/test_pick_sites_cpu.py, tests/test_pick_sites_gpu.py)."""
 import numpy as np
 
 import oracle_lib
