@@ -892,6 +892,41 @@ int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_d
 int monsoon_env_load_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev,
                          int32_t m, uint8_t* loaded_dev);
 
+/* Determinized forks (information-set search).  An entry is the TRUE game: loaded as it is, a fork plays with the opponent's
+ * hand and deck face up and with the game's own future draws, random picks and bot choices.  monsoon_env_load_determinized_dev
+ * is monsoon_env_load_dev that draws again what an observer cannot see -- same arguments, same skipped pairs, same meaning
+ * of loaded_dev, same views, same asynchrony (no allocation, host copy or synchronisation: it captures into a graph); three
+ * launches.  Entries stay interchangeable with monsoon_env_load_dev, and monsoon_version() is the same.
+ *
+ * Pair j has the seed s = seeds_dev[j] and the observer O = observers_dev[j] (0 or 1: that side; 255: the side to move in
+ * the entry's state; observers_dev NULL = 255 for every pair).  An observer byte other than 0, 1 or 255 skips the pair
+ * (loaded 0, the slot and its views untouched).  An entry whose episode has ended or has its end pending is loaded
+ * verbatim: nothing is left to search.  Otherwise, by `what`:
+ *
+ *  MONSOON_DET_STREAM (1), every record build.  The loaded slot's stream is numpy.random.RandomState(s): its raw state
+ *    and its first two tempered blocks, the slot's stream cursor at block 0, word 0 -- what a new episode of seed s starts
+ *    with.  Nothing else differs from monsoon_env_load_dev.
+ *  MONSOON_DET_STREAM | MONSOON_DET_HAND (3), standard record only.  In addition the hand of the hidden side S = 1 - O is
+ *    drawn again from its hand and deck.  Its hand entries, in record order, whose flags carry neither the alias flag nor
+ *    the kept-strength flag (b305's returned object: the observer watched it return, it stays where it is) are the k
+ *    movable places; with the d deck entries behind them they form A, L = k + d long.  For i = 0 .. k-1:
+ *    r = hash32(s, i, 0xD7) (monsoon_amd/fitness.py hash32), j = i + ((r * (L - i)) >> 32), swap A[i], A[j]; then A is
+ *    written back to the same places.  The 4-byte entries {card, cost, flags, x} move whole; the two counts and the
+ *    twelve age bytes stay (an age belongs to its deck position).  The hand becomes a uniformly chosen k-subset of the
+ *    hidden cards in uniform order -- uniform, not weighted by the draw's ages, which the observer does not know
+ *    (DESIGN.md §9).  k = 0 or L <= 1 changes nothing.  monsoon_amd.vec_env.determinize_order recomputes the permutation.
+ *    What O sees -- its own block, the board, mana, bases, the last plays -- is the entry's: the observation of a slot
+ *    loaded with O = 255 is the one monsoon_env_load_dev gives.
+ *
+ * MONSOON_ERR_ARG in addition to monsoon_env_load_dev's cases: seeds_dev NULL; what outside {1, 3}; MONSOON_DET_HAND on the
+ * extended or the large build (the message names the standard record). */
+#define MONSOON_DET_STREAM 1
+#define MONSOON_DET_HAND 2
+int monsoon_env_load_determinized_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev,
+                                      const int32_t* dst_dev, int32_t m, const uint32_t* seeds_dev /* DEVICE uint32[m] */,
+                                      const uint8_t* observers_dev /* DEVICE uint8[m]; NULL = 255 for all */, int32_t what,
+                                      uint8_t* loaded_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,45 +12,6 @@ using namespace msbk;
 
 namespace {
 
-static_assert(SW * 4 == STATE_BYTES, "the record's stride is the record");
-constexpr int SNAP_PASS = 10;   // granules per lane and pass: 9 cover the standard body (515), 10 the extended one (618); large: 2 passes
-
-// Body granule i of slot g: the record, then rng_mt, then rng_out.
-__device__ MSB_INL u32x4* slot_granule(const DevBuffers& b, const int g, const int i) {
-  uint32_t* p = i < SG                 ? b.state + (size_t)g * SW + 4 * i
-                : i < SG + SNAP_MT_G ? b.rng_mt + (size_t)g * MT_N + 4 * (i - SG)
-                                     : b.rng_out + (size_t)g * RNG_WORDS + 4 * (i - SG - SNAP_MT_G);
-  return (u32x4*)p;
-}
-
-// SAVE: body of slot g -> ent; else ent -> body of slot g.
-template <bool SAVE>
-__device__ MSB_INL void copy_body(const DevBuffers& b, const int g, u32x4* ent, const int lane) {
-  u32x4* body = ent + SNAP_HEAD_G;
-  for (int base = 0; base < SNAP_BODY_G; base += 64 * SNAP_PASS) {
-    u32x4 r[SNAP_PASS];
-#pragma unroll
-    for (int j = 0; j < SNAP_PASS; j++) {
-      const int i = base + 64 * j + lane;
-      if (i < SNAP_BODY_G) r[j] = SAVE ? *slot_granule(b, g, i) : body[i];
-    }
-#pragma unroll
-    for (int j = 0; j < SNAP_PASS; j++) {
-      const int i = base + 64 * j + lane;
-      if (i < SNAP_BODY_G) {
-        if (SAVE) body[i] = r[j];
-        else *slot_granule(b, g, i) = r[j];
-      }
-    }
-  }
-}
-
-#define SNAP_WAVE_LOOP()                                                                                \
-  const int lane = (int)threadIdx.x & 63;                                                               \
-  const int wave0 = __builtin_amdgcn_readfirstlane((int)blockIdx.x * SNAP_WAVES + ((int)threadIdx.x >> 6)); \
-  const int waves = (int)gridDim.x * SNAP_WAVES;                                                        \
-  for (int j = wave0; j < m; j += waves)
-
 // Entry j = slot slots[j] (null: slot j).  A slot outside [0, n) leaves an entry with a zero header, which never loads.
 __global__ void __launch_bounds__(64 * SNAP_WAVES) k_env_save(DevBuffers b, EnvDev v, int n, u32x4* entries, const int32_t* slots, int m,
                                                               uint32_t version) {
@@ -77,6 +38,8 @@ __global__ void __launch_bounds__(64 * SNAP_WAVES) k_env_save(DevBuffers b, EnvD
 // lane's: src, dst, the header granule and the cursor word are read at one address by all lanes and made uniform.  Of the
 // meta row the episode's fields are taken (result, fault, last_action, flags, steps, rng); the players' rows, the schedule
 // index and the look-ahead statistics (p1, p2, match, decided, lookahead, la_fault) stay the destination's.
+// (env_snap.h restates the checks and the head copy as snap_load_entry / snap_load_slot for k_env_load_det,
+// env_determinize.hip; called from here they change this kernel's register allocation, and its code is kept as it was.)
 __global__ void __launch_bounds__(64 * SNAP_WAVES) k_env_load(DevBuffers b, EnvDev v, int n, const u32x4* entries, int n_entries,
                                                               const int32_t* src, const int32_t* dst, int m, uint8_t* loaded, uint32_t version) {
   SNAP_WAVE_LOOP() {

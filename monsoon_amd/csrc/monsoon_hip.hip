@@ -24,6 +24,7 @@
 #include "host_mem.h"
 #include "kernels.h"
 #include "replay_log.h"
+#include "seed_game.h"
 
 using namespace msb;
 using namespace msbk;
@@ -65,28 +66,7 @@ __device__ MSB_INL void api_store(uint32_t* dst) {
   for (int c = 0; c < SG; c++) d4[c] = *(MSB_AS_LDS const u32x4*)ApiMem::b(c * 16);
 }
 
-// init_genrand(seed) into t[0..623] (a serial recurrence: lane 0)
-__device__ inline void wave_init_genrand(MSB_AS_LDS uint32_t* t, uint32_t seed, int lane) {
-  if (lane == 0) {
-    uint32_t x = seed;
-    t[0] = x;
-    for (int i = 1; i < MT_N; i++) {
-      x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)i;
-      t[i] = x;
-    }
-  }
-  __syncthreads();
-}
-
-// game g's stream = RandomState(seed): the raw state and its first two tempered blocks (t = 624 words of LDS)
-__device__ inline void wave_seed_game(const DevBuffers& b, int g, uint32_t seed, MSB_AS_LDS uint32_t* t, int lane) {
-  wave_init_genrand(t, seed, lane);
-  uint32_t* mt = b.rng_mt + (size_t)g * MT_N;
-  for (int k = lane; k < MT_N; k += 64) mt[k] = t[k];
-  __syncthreads();
-  wave_refill(b, g, 0, t, lane);
-  wave_refill(b, g, 1, t, lane);
-}
+// (wave_init_genrand, wave_seed_game: seed_game.h)
 
 __global__ void __launch_bounds__(64) k_seed(DevBuffers b, int g0, int n, const uint32_t* seeds) {
   // one wavefront per game (games g0 .. g0+n-1, seeds[0..n-1]): init_genrand is a serial recurrence (lane 0), the two
@@ -2807,24 +2787,58 @@ int monsoon_env_save_dev(monsoon_t* h, void* entries_dev, const int32_t* slots_d
   return MONSOON_OK;
 }
 
+// What both loads refuse of their common arguments (null: nothing).
+static const char* load_args_bad(const monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* dst_dev, int32_t m) {
+  if (!entries_dev) return "entries_dev is NULL";
+  if ((uintptr_t)entries_dev & 15) return "entries_dev must be 16-byte aligned";
+  if (m < 0 || n_entries < 0) return "m < 0 or n_entries < 0";
+  if (!dst_dev && m > h->env_n) return "m > n without dst_dev";
+  if (m > h->cfg.max_games) return "m > max_games";
+  return nullptr;
+}
+
 // Two launches on the handle's stream, the copy (k_env_load) and the views of the loaded slots (k_env_view): no
 // allocation, copy or synchronisation (graph-capturable).
 int monsoon_env_load_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev, int32_t m,
                          uint8_t* loaded_dev) {
   if (!h) return MONSOON_ERR_ARG;
   if (int rc = require_env(h, "monsoon_env_load_dev")) return rc;
-  const char* bad = nullptr;
-  if (!entries_dev) bad = "entries_dev is NULL";
-  else if ((uintptr_t)entries_dev & 15) bad = "entries_dev must be 16-byte aligned";
-  else if (m < 0 || n_entries < 0) bad = "m < 0 or n_entries < 0";
-  else if (!dst_dev && m > h->env_n) bad = "m > n without dst_dev";
-  else if (m > h->cfg.max_games) bad = "m > max_games";
-  if (bad) return bad_arg(h, "monsoon_env_load_dev", bad);
+  if (const char* bad = load_args_bad(h, entries_dev, n_entries, dst_dev, m)) return bad_arg(h, "monsoon_env_load_dev", bad);
   if (m == 0) return MONSOON_OK;
   HIP_TRY(h, bind_device(h));
   uint8_t* flags = loaded_dev ? loaded_dev : h->d_snap_flag;
   monsoon_env_snap_ops()->load(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, n_entries, src_dev, dst_dev, m, flags,
                                (uint32_t)monsoon_version());
+  LAUNCH_LANES(h, k_env_view, m, h->b, h->env, m, dst_dev, flags);
+  HIP_TRY(h, hipGetLastError());
+  return MONSOON_OK;
+}
+
+// Three launches on the handle's stream -- the copy (k_env_load_det), the re-draw and the new stream of the loaded pairs
+// (k_env_determinize, env_determinize.hip), the views (k_env_view): no allocation, copy or synchronisation
+// (graph-capturable).
+int monsoon_env_load_determinized_dev(monsoon_t* h, const void* entries_dev, int32_t n_entries, const int32_t* src_dev, const int32_t* dst_dev,
+                                      int32_t m, const uint32_t* seeds_dev, const uint8_t* observers_dev, int32_t what, uint8_t* loaded_dev) {
+  if (!h) return MONSOON_ERR_ARG;
+  if (int rc = require_env(h, "monsoon_env_load_determinized_dev")) return rc;
+  const char* bad = load_args_bad(h, entries_dev, n_entries, dst_dev, m);
+  if (!bad) {
+    if (!seeds_dev) bad = "seeds_dev is NULL";
+    else if (what != MONSOON_DET_STREAM && what != (MONSOON_DET_STREAM | MONSOON_DET_HAND))
+      bad = "what is MONSOON_DET_STREAM (1) or MONSOON_DET_STREAM | MONSOON_DET_HAND (3)";
+#if defined(MSB_EXT) && MSB_EXT
+    else if (what & MONSOON_DET_HAND)
+      bad = "MONSOON_DET_HAND needs the standard record: this build lists object ids, which the re-draw does not move (MONSOON_DET_STREAM alone works)";
+#endif
+  }
+  if (bad) return bad_arg(h, "monsoon_env_load_determinized_dev", bad);
+  if (m == 0) return MONSOON_OK;
+  HIP_TRY(h, bind_device(h));
+  uint8_t* flags = loaded_dev ? loaded_dev : h->d_snap_flag;
+  const EnvDetOps* o = monsoon_env_det_ops();
+  o->load(snap_grid(h, m), h->stream, h->b, h->env, h->env_n, entries_dev, n_entries, src_dev, dst_dev, m, observers_dev, flags,
+          (uint32_t)monsoon_version());
+  o->determinize(h->stream, h->b, entries_dev, src_dev, dst_dev, m, seeds_dev, observers_dev, what, flags);
   LAUNCH_LANES(h, k_env_view, m, h->b, h->env, m, dst_dev, flags);
   HIP_TRY(h, hipGetLastError());
   return MONSOON_OK;

@@ -490,6 +490,16 @@ class BatchEngine:
                                                ctypes.c_void_p(dst_ptr or None), int(m), ctypes.c_void_p(loaded_ptr or None)),
                  "monsoon_env_load_dev")
 
+    def env_load_determinized_dev(self, entries_ptr, n_entries, src_ptr, dst_ptr, m, seeds_ptr, observers_ptr, what, loaded_ptr):
+        """monsoon_env_load_determinized_dev: env_load_dev that draws again what the observer cannot see -- seeds_ptr =
+        device uint32[m], observers_ptr = device uint8[m] or 0 (the side to move), what = 1 (the stream) or 3 (the stream
+        and the hidden hand).  Asynchronous on the handle's stream."""
+        self._ck(self.lib.monsoon_env_load_determinized_dev(self.h, ctypes.c_void_p(entries_ptr), int(n_entries), ctypes.c_void_p(src_ptr or None),
+                                                            ctypes.c_void_p(dst_ptr or None), int(m), ctypes.c_void_p(seeds_ptr or None),
+                                                            ctypes.c_void_p(observers_ptr or None), int(what),
+                                                            ctypes.c_void_p(loaded_ptr or None)),
+                 "monsoon_env_load_determinized_dev")
+
     def stream_ptr(self):
         """The hipStream_t the handle launches on (monsoon_stream), as an integer."""
         return self.lib.monsoon_stream(self.h) or 0

@@ -8,7 +8,8 @@ opponent can also be the reference's HeuristicAgent with GA weights ("heuristic"
 `OpponentExplore` makes that opponent epsilon-greedy with an epsilon per slot (`reset(opponent_explore=...)`,
 `set_opponent_explore` between steps, `opponent_explored` for the counts, `opponent_explore_draws` for the draws); with
 `temperature=` its exploring decisions draw from the softmax over their scores, a temperature per slot.
-`snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device.
+`snapshot` / `restore` keep slots and put them back -- into the same slot (rewind) or into many (fork) -- on the device;
+`determinize` is the restore of an information-set search: it draws again what the side to move cannot see.
 Episode decks come from the reset decks, from a pool, or from a deck schedule (`reset(deck_schedule=...)`: the GA's
 exploit / explore / balance curriculum, drawn on the device per episode; `set_deck_schedule` moves its generation).
 torch is used for device memory and stream ordering only; there is no CPU fallback.
@@ -112,6 +113,28 @@ def opponent_explore_draws(seed, episode_seeds, k):
     return hash32_array(seed, episode_seeds, k, 0), hash32_array(seed, episode_seeds, k, 1)
 
 
+DETERMINIZE = {"stream": 1, "hand": 3}   # what -> MONSOON_DET_STREAM, MONSOON_DET_STREAM | MONSOON_DET_HAND
+
+
+def determinize_order(seed, n_movable, n_deck):
+    """The permutation VecEnv.determinize(what="hand") applies to the hidden side's cards for the seed `seed`
+    (include/monsoon.h, monsoon_env_load_determinized_dev; csrc/determinize.h): with A = the n_movable movable hand entries
+    in record order followed by the n_deck deck entries, the re-dealt list is A[order] -- order[:n_movable] is the new hand.
+    An int64 array of n_movable + n_deck indices, recomputed on the host: r = hash32(seed, i, 0xD7),
+    j = i + ((r * (L - i)) >> 32), swap places i and j, for i < n_movable."""
+    k, d = int(n_movable), int(n_deck)
+    if not (0 <= k <= 5 and 0 <= d <= 12):
+        raise ValueError(f"a hand holds 0..5 cards and a deck 0..12, got {n_movable}, {n_deck}")
+    order = np.arange(k + d, dtype=np.int64)
+    if k:
+        i = np.arange(k, dtype=np.uint64)
+        r = hash32_array(int(seed) & 0xFFFFFFFF, i, 0xD7).astype(np.uint64)
+        j = i + ((r * (np.uint64(k + d) - i)) >> np.uint64(32))
+        for a, b in zip(range(k), j.astype(np.int64)):
+            order[[a, b]] = order[[b, a]]
+    return order
+
+
 class EnvSnapshot:
     """Saved slots of a VecEnv (VecEnv.snapshot): data is a uint8 CUDA tensor [cap][entry_bytes], count the entries in
     use (the first `count` rows), extended the record build that wrote them, entry_bytes that build's entry size.  The
@@ -158,6 +181,7 @@ class VecEnv:
         self._after = {}          # obs -> ((n, K), tensors, _lib.EnvAfter): the latest shape per obs flag, reused until it changes
         self._schedule = None     # the deck_schedule given to reset (a DeckEvolutionConfig or a dict) while a schedule-mode env is loaded
         self._decks = None        # decks()' tensor
+        self._observers = {}      # (m, side) -> determinize's observer bytes for an int observer
 
     def close(self):
         if self.engine is not None:
@@ -509,6 +533,13 @@ class VecEnv:
                 or d.shape[1] != snap.entry_bytes or not d.is_contiguous() or d.data_ptr() % 16 or not 0 <= snap.count <= d.shape[0]):
             raise ValueError(f"snapshot data must be a contiguous uint8 CUDA tensor [cap][{snap.entry_bytes}] on device {self.device}")
 
+    def _check_loaded(self, loaded, m):
+        import torch
+        if loaded is not None:
+            if (not isinstance(loaded, torch.Tensor) or loaded.dtype not in (torch.uint8, torch.bool) or not loaded.is_cuda
+                    or loaded.device.index != self.device or loaded.shape != (m,) or not loaded.is_contiguous()):
+                raise ValueError(f"loaded must be a contiguous uint8 or bool CUDA tensor of shape ({m},) on device {self.device}")
+
     def restore(self, snap, src=None, dst=None, loaded=None):
         """Load saved slots (monsoon_env_load_dev): for every j, slot dst[j] becomes entry src[j] of snap (int32 CUDA
         tensors of one length m; None = j: without dst m <= n, without both m = len(snap)).  The same src may appear many
@@ -536,14 +567,75 @@ class VecEnv:
             raise ValueError(f"{m} entries into {self.n} slots: give dst")
         if m > self.engine.max_games:
             raise ValueError(f"at most max_slots = {self.engine.max_games} pairs per call")
-        if loaded is not None:
-            if (not isinstance(loaded, torch.Tensor) or loaded.dtype not in (torch.uint8, torch.bool) or not loaded.is_cuda
-                    or loaded.device.index != self.device or loaded.shape != (m,) or not loaded.is_contiguous()):
-                raise ValueError(f"loaded must be a contiguous uint8 or bool CUDA tensor of shape ({m},) on device {self.device}")
+        self._check_loaded(loaded, m)
         if m:
             self._on_env_stream(lambda: self.engine.env_load_dev(snap.data.data_ptr(), snap.count, 0 if src is None else src.data_ptr(),
                                                                  0 if dst is None else dst.data_ptr(), m,
                                                                  0 if loaded is None else loaded.data_ptr()))
+        return self.views
+
+    def determinize(self, snap, seeds, src=None, dst=None, observer=None, what="hand", loaded=None):
+        """restore() that draws again what an observer cannot see (monsoon_env_load_determinized_dev): the fork of an
+        information-set search.  snap, src, dst and loaded are restore's, with restore's rules and skipped pairs.  seeds is
+        a contiguous CUDA tensor [m] of 32-bit seeds, one per pair: int32 holding the uint32's bits (the seed s >= 2**31 is
+        s - 2**32; torch.from_numpy(np.asarray(s, dtype=np.uint32).view(np.int32)) makes it), or torch.uint32 where torch has
+        it.  The tensor is read on the device by every call, so a captured call sees the seeds written into it since.
+
+        what="stream": the loaded slot's stream becomes numpy.random.RandomState(seeds[j]) at its start, so its draws,
+        random picks and scripted-bot choices are a fresh sample and no longer the real game's.  what="hand" (standard
+        record only) also re-deals the hidden side's hand uniformly from its hand and deck (determinize_order gives the
+        permutation; b305's returned object stays).  The hidden side is the one that `observer` is not: None = the side to
+        move in the entry's state, 0 / 1 = that side for every pair, or a uint8 CUDA tensor [m] of 0 / 1 / 255 (255 = the
+        side to move; any other byte skips the pair).  An entry whose episode has ended or has its end pending loads as
+        restore loads it.  With observer None the views of a loaded slot are those restore gives: what the side to move sees
+        does not change.  Nothing of decks() changes.
+
+        Returns the view tensors.  Three launches on the env's stream; with an int observer a tensor [m] is allocated on the
+        first call per (m, observer) and kept, so a later call allocates nothing and can be captured.  Stream ordering as in
+        step.  ValueError for what="hand" on VecEnv(extended != 0) (use what="stream") and for arguments of wrong type,
+        dtype, device or shape; MonsoonError before reset."""
+        import torch
+        if what not in DETERMINIZE:
+            raise ValueError(f"what must be one of {sorted(DETERMINIZE)}, got {what!r}")
+        if what == "hand" and int(self.extended) != 0:
+            raise ValueError(f'what="hand" re-deals the standard record\'s hand and deck entries; this VecEnv is of record build '
+                             f'{int(self.extended)}, whose lists hold object ids: use what="stream"')
+        if isinstance(observer, bool) or not (observer is None or isinstance(observer, (int, torch.Tensor))):
+            raise ValueError("observer must be None, 0, 1 or a uint8 CUDA tensor")
+        if isinstance(observer, int) and observer not in (0, 1):
+            raise ValueError(f"observer must be None, 0, 1 or a uint8 CUDA tensor, got {observer}")
+        if self.views is None:
+            raise MonsoonError("VecEnv.determinize before reset")
+        self._check_snapshot(snap)
+        m = None
+        if src is not None:
+            src, m = self._index(src, "src")
+        if dst is not None:
+            dst, m = self._index(dst, "dst", m)
+        if m is None:
+            m = snap.count
+        if dst is None and m > self.n:
+            raise ValueError(f"{m} entries into {self.n} slots: give dst")
+        if m > self.engine.max_games:
+            raise ValueError(f"at most max_slots = {self.engine.max_games} pairs per call")
+        seed_types = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+        if (not isinstance(seeds, torch.Tensor) or seeds.dtype not in seed_types or not seeds.is_cuda or seeds.device.index != self.device
+                or seeds.shape != (m,) or not seeds.is_contiguous()):
+            raise ValueError(f"seeds must be a contiguous int32 (the uint32's bits) or uint32 CUDA tensor of shape ({m},) on device {self.device}")
+        if isinstance(observer, torch.Tensor):
+            if (observer.dtype != torch.uint8 or not observer.is_cuda or observer.device.index != self.device or observer.shape != (m,)
+                    or not observer.is_contiguous()):
+                raise ValueError(f"observer must be a contiguous uint8 CUDA tensor of shape ({m},) on device {self.device}")
+        elif observer is not None:
+            key = (m, observer)
+            if key not in self._observers:
+                self._observers[key] = torch.full((m,), observer, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            observer = self._observers[key]
+        self._check_loaded(loaded, m)
+        if m:
+            self._on_env_stream(lambda: self.engine.env_load_determinized_dev(
+                snap.data.data_ptr(), snap.count, 0 if src is None else src.data_ptr(), 0 if dst is None else dst.data_ptr(), m,
+                seeds.data_ptr(), 0 if observer is None else observer.data_ptr(), DETERMINIZE[what], 0 if loaded is None else loaded.data_ptr()))
         return self.views
 
     def state_hash(self):
@@ -551,4 +643,4 @@ class VecEnv:
         return self.engine.state_hash()
 
 
-__all__ = ["VecEnv", "EnvSnapshot", "OpponentExplore", "opponent_explore_draws", "OPPONENTS", "MonsoonError", "select_actions"]
+__all__ = ["VecEnv", "EnvSnapshot", "OpponentExplore", "opponent_explore_draws", "determinize_order", "DETERMINIZE", "OPPONENTS", "MonsoonError", "select_actions"]
